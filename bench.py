@@ -2,6 +2,14 @@
 """bench.py -- LORB_SLAM matcher + local-BA hot path on MI355X (one process per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|shared|rehearse]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets the workload up, runs W untimed and
+K timed steps, writes the last step's results if `--dump-outputs DIR` is given (DIR/<name>.npy,
+float32 / float64, see dump_outputs) and prints the JSON line (`value`, `ms_per_step`, `check`, ...).
+Everything else described below -- the per-kernel profile pass and the rooflines, the CPU baselines
+and the c2 / c3 / c1 / c4x8 / drop-in / shared sub-records -- runs only with `--full` (the `--no-*`
+switches then drop single parts of it); without `--full` those keys of the line are null.
 
 Launch.  The driver starts N>1 ranks itself (`torch.distributed.run ... bench.py --gpus N`).  When
 `--gpus N > 1` is given without WORLD_SIZE in the environment, this script starts the N ranks
@@ -22,7 +30,7 @@ a synthetic stream every step (lorb_map_step_dev, the chained LocalMapping step)
      is built on the device (one small readback),
   4. 10 Levenberg-Marquardt iterations of BA::LocalPoseOptimization on the window (50 optimised
      KFs + 5 fixed, ~10,000 points, ~75,000 observations), tolerances 0, float write-back.
-`value` = LM iterations/s over all GPUs.  The same run also times the BASELINE C2 matcher
+`value` = LM iterations/s over all GPUs.  With `--full` the same run also times the BASELINE C2 matcher
 config (batched 2000x2000 top-2 + ratio test) and reports it as the `c2` sub-record, so both
 halves of the metric ("ORB matches/sec + local-BA iterations/sec") come from one driver run.
 
@@ -194,6 +202,34 @@ def kernel_times(ctx, ids):
     return out
 
 
+DUMP_CAP = 64 << 20  # bytes of .npy data one --dump-outputs run may write
+
+
+def dump_outputs(path, arrays, prefix=""):
+    """Write {name: array} as path/<prefix><name>.npy.  float32 and integers of at most 16 bits are
+    stored as float32, everything else (int32, float64) as float64, so every value is kept exactly.
+    Above DUMP_CAP bytes in all, every array is cut to the same fraction of its elements: a sample
+    of its flattened values at sorted indices drawn from a fixed seed (the same indices every run)."""
+    os.makedirs(path, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        small = a.dtype == np.float32 or a.dtype == np.bool_ or (a.dtype.kind in "iu" and a.dtype.itemsize <= 2)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float32 if small else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    for i, (name, a) in enumerate(sorted(conv.items())):
+        if total > DUMP_CAP:
+            keep = int(a.size * (DUMP_CAP / total))
+            idx = np.sort(np.random.default_rng(20240 + i).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{prefix}{name}.npy"), a)
+
+
+def summary_array(s):
+    """a BA summary as numbers: iterations, successful steps, initial cost, final cost"""
+    return np.array([s["iterations"], s["successful_steps"], s["initial_cost"], s["final_cost"]], np.float64)
+
+
 # ------------------------------------------------------------------------------------------
 def workload_c4(ctx, args, rank):
     """The chained LocalMapping step on an HBM-resident map (lorb_map_step_dev), one map per window:
@@ -264,6 +300,20 @@ def workload_c4(ctx, args, rank):
                                      "ba_iterations": st["summary"]["iterations"]})
         return out
 
+    def outputs():
+        """every window's map after the last step (lorb_map_read, what a caller of the step gets):
+        optimised and fixed poses, points with their descriptors, the observations, the last
+        keyframe's matches and the last BA's summary"""
+        out = {}
+        for i, m in enumerate(maps):
+            st = m.read()
+            p = f"w{i}_" if W > 1 else ""
+            for k in ("pose", "fixed_pose", "point", "point_desc", "obs_point", "obs_kf", "obs_frame", "obs_uv",
+                      "match_train"):
+                out[p + k] = st[k]
+            out[p + "summary"] = summary_array(st["summary"])
+        return out
+
     c = maps[0].counts()
     n_obs, n_pts = c["observations"], c["points"]
     F = maps[0].W
@@ -291,7 +341,7 @@ def workload_c4(ctx, args, rank):
         for c in ctxs:
             c.sync()
 
-    return dict(step=step, check=check, sync=sync, maps=maps, ba_iters=10.0 * W, matches=float(W * nq), pairs=float(W) * nq * n_pts,
+    return dict(step=step, check=check, outputs=outputs, sync=sync, maps=maps, ba_iters=10.0 * W, matches=float(W * nq), pairs=float(W) * nq * n_pts,
                 plan_ms=0.0, create_ms=create_ms, cleanup=cleanup, kspec=kspec, traffic_key="c4_chain",
                 config={"workload": "c4_local_mapping_step_chained", "windows_per_gpu": W, "kf": F,
                         **({"map_groups": f"{len(groups)} x {G} windows (lorb_map_group), one stream each"} if groups else {}),
@@ -598,6 +648,10 @@ def workload_c3(ctx, args, rank):
         _, _, summ = plan.read()
         return {"ba_final_cost": summ[0]["final_cost"], "ba_iterations": summ[0]["iterations"]}
 
+    def outputs():
+        poses, pts, summ = plan.read()
+        return {"pose": poses[0], "point": pts[0], "summary": summary_array(summ[0])}
+
     def cleanup():
         plan.close()
         for x in arrays.values():
@@ -622,8 +676,8 @@ def workload_c3(ctx, args, rank):
                           "sample": f"{nn} solves on {nt} threads (independent windows; {nt} = the box's per-GPU CPU share), {dn:.1f}s"},
                 "host_cpu": model, "host_cpus_available": avail}
 
-    return dict(step=step, check=check, ba_iters=10.0, matches=0.0, pairs=0.0, plan_ms=plan_ms, cleanup=cleanup,
-                kspec=kspec, traffic_key="c3", window=w, n_poses=F,
+    return dict(step=step, check=check, outputs=outputs, ba_iters=10.0, matches=0.0, pairs=0.0, plan_ms=plan_ms,
+                cleanup=cleanup, kspec=kspec, traffic_key="c3", window=w, n_poses=F,
                 config={"workload": "c3_local_ba", "kf": F, "fixed_kf": 2, "points": n_pts, "observations": n_obs,
                         "window_observations": int((np.asarray(w["obs_frame"]) >= 0).sum()), "lm_iterations": 10,
                         "step": "device-built plan of the resident window + 10 LM its from the initial values"},
@@ -696,6 +750,12 @@ def workload_shared(ctx, args, rank, D, comm):
         return {"n_matches": int(nm.numpy()[0]), "ba_final_cost": summ[0]["final_cost"],
                 "ba_iterations": summ[0]["iterations"]}
 
+    def outputs():
+        """this rank's share: its query rows' match results and its shard's poses and points"""
+        poses, pts, summ = plan.read()
+        out = {k: o.numpy()[:b - a] for k, o in zip(("cc_train", "cc_dist", "match_train"), outs)}
+        return dict(out, n_matches=nm.numpy(), pose=poses[0], point=pts[0], summary=summary_array(summ[0]))
+
     def cleanup():
         plan.close()
         for x in (dq, dt, nm, *outs, *arrays.values()):
@@ -706,8 +766,8 @@ def workload_shared(ctx, args, rank, D, comm):
     bw = 6 * 8 - 1
     kspec = ba_kspec(1, len(sh["obs_point"]), len(sh["point_init"]), 50, bw)  # this rank's shard
     # whole-job units: the shared window's iterations / matches are counted once (rank 0 only)
-    return dict(step=step, check=check, ba_iters=10.0 if rank == 0 else 0.0, matches=float(nq) if rank == 0 else 0.0,
-                pairs=float(b - a) * nt, plan_ms=plan_ms, cleanup=cleanup, kspec=kspec,
+    return dict(step=step, check=check, outputs=outputs, ba_iters=10.0 if rank == 0 else 0.0,
+                matches=float(nq) if rank == 0 else 0.0, pairs=float(b - a) * nt, plan_ms=plan_ms, cleanup=cleanup, kspec=kspec,
                 traffic_key=f"shared_w{world}", n_ranks=world, window=win, n_poses=50,
                 config={"workload": "c5_shared_window", "kf": 50, "fixed_kf": 5, "points": len(win["point_init"]),
                         "observations": n_obs, "lm_iterations": 10, "new_kf_keypoints": nq,
@@ -760,7 +820,11 @@ def workload_c2(ctx, args, rank):
         for a in (dq, dt, dl, acc, *outs):
             a.free()
 
-    return dict(step=step, check=lambda: {"accepted": int(acc.numpy().sum())}, ba_iters=0.0, matches=float(nq),
+    def outputs():
+        names = ("best_idx", "best_dist", "best_level", "second_dist", "second_level")
+        return dict({k: o.numpy() for k, o in zip(names, outs)}, accepted=acc.numpy())
+
+    return dict(step=step, check=lambda: {"accepted": int(acc.numpy().sum())}, outputs=outputs, ba_iters=0.0, matches=float(nq),
                 pairs=float(nq) * 2000, plan_ms=0.0, cleanup=cleanup, kspec={}, traffic_key="c2",
                 config={"workload": "c2_bf_top2_ratio", "pairs_per_gpu": B, "unique_pairs": U, "nq": 2000, "nt": 2000},
                 cpu=cpu)
@@ -783,7 +847,7 @@ def workload_rehearse(ctx, args, rank):
     def step():
         for _ in range(4):
             a @ a
-    return dict(step=step, check=lambda: {}, ba_iters=1.0, matches=0.0, pairs=0.0, plan_ms=0.0,
+    return dict(step=step, check=lambda: {}, outputs=lambda: {"product": a @ a}, ba_iters=1.0, matches=0.0, pairs=0.0, plan_ms=0.0,
                 cleanup=lambda: None, kspec={}, traffic_key=None,
                 config={"workload": "rehearsal_cpu_no_gpu"}, cpu=None)
 
@@ -1047,6 +1111,10 @@ def main():
     ap.add_argument("--no-c1", action="store_true", help="skip the C1 per-frame tracking sub-record")
     ap.add_argument("--no-c4x8", action="store_true", help="skip the 8-windows-per-GPU C4 sub-record")
     ap.add_argument("--c4x8-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the profile pass (rooflines), the CPU baselines and the sub-records")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1089,23 +1157,28 @@ def main():
               "rehearse": workload_rehearse}[args.workload](ctx, args, D.rank)
 
     elapsed = timed(ctx, D, wl, args.steps, args.warmup)
+    if args.dump_outputs:  # the state the last timed step left, before anything else steps the workload
+        dump_outputs(args.dump_outputs, wl["outputs"](), f"rank{D.rank}_" if D.world > 1 else "")
     check = wl["check"]()
     rwin = check.pop("_window", None) if isinstance(check, dict) else None
     if rwin is None and wl.get("window") is not None:
         rwin = wl["window"]
-    kt, pn = ({}, 1) if rehearse else profile_pass(ctx, wl, args.steps)
+    # everything from here to the line is --full's: runs of their own beside the headline's
+    full = args.full
+    kt, pn = profile_pass(ctx, wl, args.steps) if (full and not rehearse) else ({}, 1)
     total_iters = D.reduce(wl["ba_iters"] * args.steps, "SUM")
     total_matches = D.reduce(wl["matches"] * args.steps, "SUM")
-    cpu = wl["cpu"]() if (D.rank == 0 and not args.no_cpu_baseline and D.world == 1 and wl["cpu"]) else None
+    cpu = wl["cpu"]() if (full and D.rank == 0 and not args.no_cpu_baseline and D.world == 1 and wl["cpu"]) else None
     if cpu is not None and args.workload == "c4":
         cpu["c1"] = cpu_baseline_c1(max(2.0, args.cpu_budget / 2))
-    c2 = sub_c2(ctx, D, args) if (args.workload == "c4" and not args.no_c2) else None
-    dropin = sub_dropin(ctx, D, args) if (args.workload == "c4" and not args.no_dropin) else None
-    c1 = sub_c1(ctx, D, args) if (args.workload == "c4" and not args.no_c1) else None
-    c3 = sub_c3(ctx, D, args) if (args.workload == "c4" and not args.no_c3) else None
-    c4x8 = sub_c4x8_run(ctx, D, args) if (args.workload == "c4" and args.windows == 1 and not args.no_c4x8) else None
+    subs = full and args.workload == "c4"
+    c2 = sub_c2(ctx, D, args) if (subs and not args.no_c2) else None
+    dropin = sub_dropin(ctx, D, args) if (subs and not args.no_dropin) else None
+    c1 = sub_c1(ctx, D, args) if (subs and not args.no_c1) else None
+    c3 = sub_c3(ctx, D, args) if (subs and not args.no_c3) else None
+    c4x8 = sub_c4x8_run(ctx, D, args) if (subs and args.windows == 1 and not args.no_c4x8) else None
     shared = None
-    if args.workload in ("c4", "rehearse") and not args.no_shared:
+    if full and args.workload in ("c4", "rehearse") and not args.no_shared:
         # the shared-window sub-record's communicator is created here, after the headline (which has
         # no collective: independent windows per rank), so that a communicator failure costs the
         # sub-record, not the headline line
@@ -1136,7 +1209,8 @@ def main():
             "roofline_iteration": (roofline_iteration(rwin, wl.get("n_poses", wl["config"].get("kf", 50)),
                                                       elapsed / args.steps * 1e3 / max(wl["ba_iters"], 1.0),
                                                       wl["traffic_key"])
-                                   if rwin is not None and wl["ba_iters"] > 0 else None),
+                                   if full and rwin is not None and wl["ba_iters"] > 0 else None),
+            "full": full,
             "cpu_baseline": cpu, "c2": c2, "c3": c3, "c4x8": c4x8, "dropin_local_ba": dropin, "shared": shared, "c1": c1,
             "check": check,
         }

@@ -50,11 +50,12 @@ def flip_bits(rng, desc, max_flips):
     out = desc.copy()
     n = len(desc)
     nf = rng.integers(0, max_flips + 1, size=n)
-    for i in range(n):
-        if nf[i]:
-            bits = rng.choice(256, size=nf[i], replace=False)
-            for b in bits:
-                out[i, b >> 3] ^= np.uint8(1 << (b & 7))
+    rows = np.nonzero(nf)[0]
+    if len(rows):
+        # the rows' draws in row order (the generator's stream is the same as row by row), then
+        # every flip at once: unbuffered, several bits of a row may fall into one byte
+        bits = np.concatenate([rng.choice(256, size=k, replace=False) for k in nf[rows].tolist()])
+        np.bitwise_xor.at(out, (np.repeat(rows, nf[rows]), bits >> 3), (1 << (bits & 7)).astype(np.uint8))
     return out
 
 
@@ -546,8 +547,12 @@ def mapping_sequence(seed=4, n_kf=50, n_fixed=5, n_new=189, obs_lens=(7, 8), ste
     out = []
     for i in range(steps):
         t = n_kf + i
-        reob = np.nonzero((created < t) & (created + length > t))[0]
-        new = np.nonzero(created == t)[0]
+        # points lie in creation order, n_new per keyframe: those still seen at t were created in
+        # (t - lmax, t) and those created at t follow them (a slice, so a step costs the same however
+        # long the stream is)
+        lo, hi = (t - lmax - first) * n_new, (t - first) * n_new
+        reob = lo + np.nonzero((created[lo:hi] < t) & (created[lo:hi] + length[lo:hi] > t))[0]
+        new = np.arange(hi, hi + n_new)
         uv_r, _ = project(t, reob)
         uv_n, z_n = project(t, new)
         n_d = max(0, n_kps - len(reob) - len(new))

@@ -8,7 +8,7 @@ NOSUB="--no-c2 --no-dropin --no-shared --no-c3 --no-c1 --no-c4x8 --no-cpu-baseli
 for r in $(seq ${ROUNDS:-2}); do
   for wl in ${WL:-c4}; do
     for v in $VARIANTS; do
-      LORB_LIB_PATH=$R/variants/liblorb_$v.so tools/gpu_step.sh 200 $O/abv_${v}_${wl}_$r.log python bench.py --workload $wl $NOSUB --steps ${STEPS:-30} || exit $?
+      LORB_LIB_PATH=$R/variants/liblorb_$v.so tools/gpu_step.sh 200 $O/abv_${v}_${wl}_$r.log python bench.py --full --workload $wl $NOSUB --steps ${STEPS:-30} || exit $?
       python - "$O/abv_${v}_${wl}_$r.log" "$v" "$wl" >> $O/abv_summary.txt <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

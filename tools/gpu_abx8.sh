@@ -7,7 +7,7 @@ O=$R/gpurun_out; mkdir -p $O
 NOSUB="--no-c2 --no-dropin --no-shared --no-c3 --no-c1 --no-cpu-baseline"
 for r in $(seq ${ROUNDS:-2}); do
   for v in $VARIANTS; do
-    LORB_LIB_PATH=$R/variants/liblorb_$v.so tools/gpu_step.sh 300 $O/abx8_${v}_$r.log python bench.py $NOSUB --steps ${STEPS:-100} || exit $?
+    LORB_LIB_PATH=$R/variants/liblorb_$v.so tools/gpu_step.sh 300 $O/abx8_${v}_$r.log python bench.py --full $NOSUB --steps ${STEPS:-100} || exit $?
     python - "$O/abx8_${v}_$r.log" "$v" >> $O/abx8_summary.txt <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

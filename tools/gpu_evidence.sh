@@ -28,7 +28,7 @@ if [ -z "$NO_TESTS" ]; then
   rc=$?; [ $rc -gt 1 ] && exit $rc
 fi
 if [ -z "$NO_BENCH" ]; then
-  tools/gpu_step.sh 400 $O/${RD}_bench.log python bench.py
+  tools/gpu_step.sh 400 $O/${RD}_bench.log python bench.py --full
   rc=$?; [ $rc -gt 1 ] && exit $rc
 fi
 [ -n "$NO_PROF" ] && exit $fail
@@ -43,7 +43,7 @@ for key in $WORKLOADS; do
     shared_w1) wl=shared; extra= ;;
     *) wl=$key; extra= ;;
   esac
-  B="$R/bench.py --workload $wl --no-cpu-baseline $extra"
+  B="$R/bench.py --full --workload $wl --no-cpu-baseline $extra"
   tools/gpu_step.sh 300 $O/${RD}_prof_${key}_stats.log rocprofv3 --kernel-trace --stats -d $P/$key/stats -o ${RD}_${key} \
     --output-format csv -- python3 $B --steps 10 --warmup 2 || exit $?
   tools/gpu_step.sh 120 $O/${RD}_prof_${key}_fetch.log rocprofv3 --pmc FETCH_SIZE -d $P/$key/fetch -o ${RD}_${key}_fetch \
@@ -55,7 +55,7 @@ done
 if [ -z "$NO_MFMA" ]; then
   tools/gpu_step.sh 120 $O/${RD}_pmc_mfma.log rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU \
     SQ_BUSY_CYCLES SQ_WAVES -d $P/mfma -o ${RD}_mfma --output-format csv \
-    -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline $NOSUB || exit $?
+    -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $NOSUB || exit $?
 fi
 if [ -n "$C1" ]; then
   tools/gpu_step.sh 300 $O/${RD}_prof_c1.log rocprofv3 --kernel-trace --memory-copy-trace --stats -d $P/c1 -o ${RD}_c1 \

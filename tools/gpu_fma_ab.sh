@@ -12,7 +12,7 @@ for v in main nofma; do
   for wl in c4 c3 shared; do
     extra=$NOSUB; [ "$wl" = c4 ] || extra="--no-cpu-baseline"
     LORB_LIB_PATH=$lib tools/gpu_step.sh 300 $O/${v}_${wl}.log rocprofv3 --kernel-trace --stats -d $O/$v/$wl -o ${v}_${wl} \
-      --output-format csv -- python3 $R/bench.py --workload $wl $extra --steps 20 --warmup 3 || exit $?
+      --output-format csv -- python3 $R/bench.py --full --workload $wl $extra --steps 20 --warmup 3 || exit $?
   done
 done
 exit 0

@@ -8,5 +8,5 @@ tools/gpu_step.sh 300 $O/g1_ba.log python -u -m pytest tests/test_gpu_ba.py test
 rc=$?; [ $rc -gt 1 ] && exit $rc
 tools/gpu_step.sh 400 $O/g1_rest.log python -u -m pytest tests -m gpu -q --timeout 200 --timeout-method thread --deselect tests/test_gpu_ba.py --deselect tests/test_gpu_solver.py --deselect tests/test_gpu_map.py
 rc2=$?; [ $rc2 -gt 1 ] && exit $rc2
-tools/gpu_step.sh 300 $O/g1_bench.log python bench.py || exit $?
+tools/gpu_step.sh 300 $O/g1_bench.log python bench.py --full || exit $?
 exit $(( rc | rc2 ))

@@ -547,7 +547,9 @@ int lorb_ba_plan_info(lorb_ba_plan* plan, int32_t* info, int32_t n);
 /* the last solve's per-iteration records of window w (at most min(cap, LORB_LM_TRACE_CAP)); *n_out =
  * records written.  Synchronises. */
 int lorb_ba_plan_trace(lorb_ba_plan* plan, int32_t window, lorb_lm_iteration* out, int32_t cap, int32_t* n_out);
-/* diagnostics: Cholesky phase stamps of window 0 (non-zero only in LORB_CHOL_STAMPS builds) */
+/* diagnostics: the plan's stamp buffer -- the two-sided Cholesky's event trace of window 0 (512
+ * entries, LORB_CHOL_TRACE builds) or k_ba_ls's phase stamps (8 per point group, LORB_LS_STAMPS
+ * builds); 8 entries nothing writes in a regular build */
 int lorb_ba_plan_debug_stamps(lorb_ba_plan* plan, unsigned long long* out8);
 /* Plan group: the LM solves of several plans on ONE ctx launched as one set of kernels (one launch per
  * kernel for all members, one captured graph), as a plan of several windows is -- for independent

@@ -1,27 +1,31 @@
-"""FP64 contraction A/B at the ISA level: compiles lorb_ba.hip for gfx950 to
-assembly twice -- as built (`#pragma clang fp contract(fast)`) and with -DLORB_NO_CONTRACT -- and
+"""FP64 contraction A/B at the ISA level: compiles the BA units (lorb_ba*.hip)
+for gfx950 to assembly twice -- as built (`#pragma clang fp contract(fast)`) and with -DLORB_NO_CONTRACT -- and
 prints, per kernel, the FP64 fused multiply-adds (v_fma_f64, v_fmac_f64) against the separate
 v_mul_f64 / v_add_f64 instructions.  Static counts (instructions in the code, not executed).
 
     python tools/isa_fma.py > profiles/r05/fma_isa.txt"""
+import glob
 import os
 import re
 import subprocess
 import sys
 import tempfile
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lorb_slam_amd", "csrc", "lorb_ba.hip")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lorb_slam_amd", "csrc")
+SRCS = sorted(glob.glob(os.path.join(CSRC, "lorb_ba*.hip")))
 KERNELS = ("k_ba_ls", "k_ba_red", "k_ba_bs2", "k_ba_chol_2s", "k_ba_lin", "k_ba_schur", "k_ba_backsub", "k_ba_pose_only",
            "k_ba_lm_end")
 
 
 def asm(flags):
+    text = ""
     with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "ba.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-                        "-ffp-contract=off", *flags, SRC, "-o", out], check=True, cwd=os.path.dirname(SRC),
-                       stderr=subprocess.DEVNULL)
-        return open(out).read()
+        for src in SRCS:
+            out = os.path.join(d, os.path.basename(src)[:-4] + ".s")
+            subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
+                            "-ffp-contract=off", *flags, src, "-o", out], check=True, cwd=CSRC, stderr=subprocess.DEVNULL)
+            text += open(out).read()
+    return text
 
 
 def counts(text):

@@ -281,6 +281,71 @@ void ProjectPoseOptimization(lorb_ctx* ctx, FrameT* F) {
   FT::set_pose(F, T, R);  // Frame::SetPose(T, R) -> Rodrigues -> mTcw (src/frame.cpp:577-594)
 }
 
+// ---- VisualOdometry::EstimatePoseMotion's body, src/visual_odometry.cpp:124-137 ------------
+// SearchByProjection(cur, last, 15), the <= 20 retry at 30 over emptied slots, and
+// ProjectPoseOptimization(cur) as ONE call (lorb_track_motion): both frames are gathered once and
+// the retry decision and the residual gathering happen on the device.  The caller has set cur's
+// pose to the motion model's prediction (:119).  Applies what the reference's three calls would
+// have written: the slots (emptied first when the retry ran) and, unless both passes found <= 20
+// matches, the optimised pose.  Returns what EstimatePoseMotion returns; *nmatches = nMatches.
+template <class FrameT>
+bool EstimatePoseMotion(lorb_ctx* ctx, FrameT* cur, FrameT* last, size_t* nmatches = nullptr) {
+  using FT = FrameTraits<FrameT>;
+  using P = typename FT::point_type;
+  using PT = PointTraits<P>;
+  lorb_frame_params fp = frame_params(cur);
+  float Tcur[16], Tlast[16], rt[6];
+  FT::Tcw(cur, Tcur);
+  FT::Tcw(last, Tlast);
+  FT::pose_vectors(cur, rt, rt + 3);  // mRvec, mTvec (src/bundle_adjust.cpp:163-168)
+  KeypointsSoA k = gather_keypoints(cur);
+  std::vector<uint8_t> st = gather_slot_state(cur);
+  const size_t nk = FT::num_keypoints(cur), nl = FT::num_keypoints(last);
+  std::vector<float> slot_pos(3 * nk + 3, 0.f);  // the points the slots hold before the call
+  for (size_t j = 0; j < nk; ++j)
+    if (P* p = FT::map_point(cur, j)) PT::pos(p, &slot_pos[3 * j]);
+  std::vector<uint8_t> has(nl, 0), out(nl, 0), lk(nl, 0), ldesc(32 * nl, 0);
+  std::vector<float> pos(3 * nl, 0.f), ang(nl, 0.f);
+  std::vector<int32_t> oct(nl, 0);
+  std::vector<P*> mps(nl, nullptr);
+  for (size_t i = 0; i < nl; ++i) {
+    P* p = FT::map_point(last, i);
+    float kx, ky;
+    FT::keypoint(last, i, &kx, &ky, &oct[i], &ang[i]);
+    if (!p) continue;
+    mps[i] = p; has[i] = 1; out[i] = FT::outlier(last, i) ? 1 : 0;
+    lk[i] = PT::num_obs(p) > 0 ? 1 : 0;
+    PT::pos(p, &pos[3 * i]);
+    PT::descriptor(p, &ldesc[32 * i]);
+  }
+  lorb_last_frame L;
+  L.n = (int32_t)nl; L.Tcw = Tlast; L.has_mp = has.data(); L.outlier = out.data(); L.mp_locked = lk.data();
+  L.mp_pos = pos.data(); L.mp_desc = ldesc.data(); L.octave = oct.data(); L.angle = ang.data();
+  lorb_keypoints kv = k.view();
+  lorb_track_motion_params par;
+  par.th_first = 15.0f; par.th_retry = 30.0f; par.min_matches = 20;
+  par.fy_eff = fp.fx;  // PoseCost quirk: v uses fx, src/bundle_adjust.cpp:51
+  lorb_lm_options opt;
+  lorb_lm_options_default(&opt);
+  std::vector<int32_t> assign(nk + 1);
+  lorb_track_motion_result res;
+  check(ctx, lorb_track_motion(ctx, &fp, Tcur, rt, &kv, nk ? st.data() : nullptr, nk ? slot_pos.data() : nullptr, &L,
+                               &par, &opt, assign.data(), &res, nullptr),
+        "lorb_track_motion");
+  if (res.pass != 1)  // the retry ran: std::fill(mvpMapPoints, NULL), src/visual_odometry.cpp:128
+    for (size_t j = 0; j < nk; ++j) FT::set_map_point(cur, j, (P*)nullptr);
+  for (size_t j = 0; j < nk; ++j) {
+    if (assign[j] == LORB_ASSIGN_NULL) FT::set_map_point(cur, j, (P*)nullptr);
+    else if (assign[j] >= 0) FT::set_map_point(cur, j, mps[assign[j]]);
+  }
+  if (nmatches) *nmatches = (size_t)(res.pass == 1 ? res.nmatches_first : res.nmatches_retry);
+  if (res.pass == 0) return false;
+  const float R[3] = {(float)res.pose[0], (float)res.pose[1], (float)res.pose[2]};
+  const float T[3] = {(float)res.pose[3], (float)res.pose[4], (float)res.pose[5]};
+  FT::set_pose(cur, T, R);  // Frame::SetPose(T, R), src/bundle_adjust.cpp:198-201
+  return true;
+}
+
 // ---- BA::LocalPoseOptimization(Frame*), src/bundle_adjust.cpp:207-330 ---------------------
 // Observation source: the reference reads GetKps2d()[idx] (src/bundle_adjust.cpp:285,295),
 // which is empty on the live path (UB); we use GetKp2d(idx) as ProjectPoseOptimization does

@@ -184,6 +184,17 @@ int lorb_search_by_projection_frame(lorb_ctx* ctx,
                                     const lorb_keypoints* cur_kps, const uint8_t* cur_slot_state,
                                     const lorb_last_frame* last, float th,
                                     int32_t* assign, int32_t* nmatches);
+/* device-pointer variant: every array of d_cur_kps, d_cur_slot_state (NULL => all EMPTY) and every
+ * array of d_last except d_last->Tcw is a DEVICE pointer; the structs, cur_Tcw, d_last->Tcw and th
+ * are host values.  Outputs d_assign (n ints) and d_nmatches (one int) on the device.  Asynchronous
+ * on the ctx stream while n_last * n_cur <= 8M (larger calls read the candidate count back once).
+ * A last-frame point whose octave is outside [0, cur->n_levels) is treated as having no map point
+ * (the host form rejects such a call instead). */
+int lorb_search_by_projection_frame_dev(lorb_ctx* ctx,
+                                        const lorb_frame_params* cur, const float cur_Tcw[16],
+                                        const lorb_keypoints* d_cur_kps, const uint8_t* d_cur_slot_state,
+                                        const lorb_last_frame* d_last, float th,
+                                        int32_t* d_assign, int32_t* d_nmatches);
 
 /* ----------------------------------------------------------------------------------------
  * (a5) Matcher::SearchByProjection(Frame* F, const std::set<MapPoint*>&, const float th)
@@ -447,6 +458,67 @@ typedef struct lorb_pose_problem_batch {
 int lorb_ba_pose_only(lorb_ctx* ctx, const lorb_pose_problem_batch* prob,
                       const lorb_lm_options* opt, double* pose_out, float* Tcw_out,
                       lorb_ba_summary* summaries);
+/* device-pointer variant: the five arrays of d_prob (res_off included) are DEVICE pointers,
+ * n_frames a host value; d_pose_out (n_frames x 6 doubles) and d_summaries (n_frames records) are
+ * written on the device.  Asynchronous on the ctx stream. */
+int lorb_ba_pose_only_dev(lorb_ctx* ctx, const lorb_pose_problem_batch* d_prob,
+                          const lorb_lm_options* opt, double* d_pose_out, lorb_ba_summary* d_summaries);
+
+/* ----------------------------------------------------------------------------------------
+ * VisualOdometry::EstimatePoseMotion (src/visual_odometry.cpp:117-138) as ONE call: a4 at
+ * th_first; if that finds <= min_matches, every slot is emptied and a4 runs again at th_retry
+ * (its codes then replace the first pass's); if the pass that counts found > min_matches, a12
+ * (BA::ProjectPoseOptimization, src/bundle_adjust.cpp:158-202) over the slots that hold a map
+ * point afterwards.  The retry decision and the residual gathering happen on the device: nothing
+ * is read back between the first launch and the last.
+ *
+ * Residuals, one per slot j holding a map point after the matching, in ascending j, observation
+ * (x[j], y[j]):  pass 1: assign[j] >= 0 -> last.mp_pos[assign[j]];  assign[j] == UNCHANGED and
+ * slot_state[j] != EMPTY -> slot_pos[j];  NULL -> none.  pass 2 (and 0): assign[j] >= 0 only.
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_track_motion_params {
+  float th_first;        /* 15 */
+  float th_retry;        /* 30 */
+  int32_t min_matches;   /* 20: a pass stands when it finds MORE than this */
+  float fy_eff;          /* PoseCost's v focal length: fx for the reference's quirk (see a12) */
+} lorb_track_motion_params;
+
+typedef struct lorb_track_motion_result {
+  int32_t pass;            /* 1: first radius stood; 2: the retry stood; 0: both found <= min_matches
+                              (the reference returns false and never optimises) */
+  int32_t nmatches_first;
+  int32_t nmatches_retry;  /* -1 when the retry did not run */
+  int32_t n_residuals;     /* slots holding a map point after the matching (not nmatches: two
+                              last-frame points can win the same slot) */
+  double pose[6];          /* the optimised (mRvec | mTvec); pass 0: pose_init widened to double */
+  lorb_ba_summary summary; /* pass 0: zeroed, as a12's empty problem */
+} lorb_track_motion_result;
+
+/* Device form.  cur, cur_Tcw (the predicted pose the matcher projects with), pose_init (the same
+ * pose as mRvec | mTvec), the structs, d_last->Tcw, par and opt are host values; every array of
+ * d_cur_kps and d_last, d_slot_state and d_slot_pos are DEVICE pointers.  d_slot_state NULL means
+ * all EMPTY (the live path); d_slot_pos (n x 3: the position of the map point a non-empty slot
+ * holds) may be NULL only then.  Outputs on the device: d_assign (n ints, the codes of the pass
+ * that counts; pass 0: the retry's) and d_result (one record).  Asynchronous on the ctx stream: no
+ * host readback and no stream synchronise while n_last * n_cur <= 8M.  Last-frame points whose
+ * octave is outside [0, cur->n_levels) are treated as having no map point. */
+int lorb_track_motion_dev(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16],
+                          const float pose_init[6], const lorb_keypoints* d_cur_kps,
+                          const uint8_t* d_slot_state, const float* d_slot_pos,
+                          const lorb_last_frame* d_last, const lorb_track_motion_params* par,
+                          const lorb_lm_options* opt, int32_t* d_assign,
+                          lorb_track_motion_result* d_result);
+/* Host-array form (synchronous): the same with host arrays; one staging of every input, the same
+ * launches, one fetch of assign + record.  Octaves outside [0, LORB_MAX_LEVELS) are rejected as a4
+ * does (those from cur->n_levels up are inactive, as in the device form: both forms give the same
+ * bits).  Tcw_out (optional, 16 floats): Frame::SetPose write-back of the rounded pose (pass 0: of
+ * pose_init). */
+int lorb_track_motion(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16],
+                      const float pose_init[6], const lorb_keypoints* cur_kps,
+                      const uint8_t* slot_state, const float* slot_pos,
+                      const lorb_last_frame* last, const lorb_track_motion_params* par,
+                      const lorb_lm_options* opt, int32_t* assign,
+                      lorb_track_motion_result* result, float* Tcw_out);
 
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.

@@ -101,6 +101,21 @@ class KeypointsDev(C.Structure):  # lorb_keypoints with device pointers
                 ("angle", C.c_void_p), ("u_right", C.c_void_p), ("desc", C.c_void_p)]
 
 
+class LastFrameDev(C.Structure):  # lorb_last_frame with device arrays (Tcw stays a host pointer)
+    _fields_ = [("n", C.c_int32), ("Tcw", f32p), ("has_mp", C.c_void_p), ("outlier", C.c_void_p),
+                ("mp_locked", C.c_void_p), ("mp_pos", C.c_void_p), ("mp_desc", C.c_void_p), ("octave", C.c_void_p),
+                ("angle", C.c_void_p)]
+
+
+class PoseProblemBatchDev(C.Structure):  # lorb_pose_problem_batch with device arrays
+    _fields_ = [("n_frames", C.c_int32), ("res_off", C.c_void_p), ("intr", C.c_void_p), ("pose_init", C.c_void_p),
+                ("pts3d", C.c_void_p), ("obs2d", C.c_void_p)]
+
+
+class TrackMotionParams(C.Structure):  # lorb_track_motion_params
+    _fields_ = [("th_first", C.c_float), ("th_retry", C.c_float), ("min_matches", C.c_int32), ("fy_eff", C.c_float)]
+
+
 class LMOptions(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int32), ("function_tolerance", C.c_double),
                 ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
@@ -126,6 +141,11 @@ class BASummary(C.Structure):
         return {"iterations": self.iterations, "successful_steps": self.successful_steps,
                 "termination": TERM_NAMES.get(self.termination, self.termination),
                 "initial_cost": self.initial_cost, "final_cost": self.final_cost}
+
+
+class TrackMotionResult(C.Structure):  # lorb_track_motion_result
+    _fields_ = [("pass_", C.c_int32), ("nmatches_first", C.c_int32), ("nmatches_retry", C.c_int32),
+                ("n_residuals", C.c_int32), ("pose", C.c_double * 6), ("summary", BASummary)]
 
 
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}

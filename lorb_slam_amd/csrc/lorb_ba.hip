@@ -1069,25 +1069,24 @@ constexpr int kPoRegRes = 2 * kPoThreads;  // residuals per frame held in regist
 // a small batch's residual offsets as a kernel argument: the residual loads need no round trip first
 constexpr int kPoArgF = 16;
 struct PoOff { int n; int off[kPoArgF + 1]; };
-__global__ __launch_bounds__(kPoThreads) void k_ba_pose_only(PoOff aoff, const int32_t* __restrict__ res_off,
-                                                             const float* __restrict__ intr,
-                                                             const float* __restrict__ pose_init,
-                                                             const float* __restrict__ pts3d,
-                                                             const float* __restrict__ obs2d, LMOpt o,
-                                                             double* __restrict__ pose_out,
-                                                             lorb_ba_summary* __restrict__ sums) {
+// The solve of one frame by one kPoThreads workgroup: residuals [0, nres), residual r fetched by
+// load(r, X, uv) (as doubles).  k_ba_pose_only reads them from the batch's arrays, k_track_tail from
+// the slots its own compaction listed.  pose_init: 6 floats; pose_out: 6 doubles; sum: one record.
+// An empty problem leaves the pose as given and a zeroed summary.
+template <class Load>
+__device__ __forceinline__ void po_run(int nres, double fx, double fyv, double cx, double cy,
+                                       const float* pose_init, const LMOpt& o, Load load,
+                                       double* __restrict__ pose_out, lorb_ba_summary* __restrict__ sum) {
   __shared__ double s_nv[2][kPoW][28];
   __shared__ double s_cv[2][kPoW];
-  const int f = blockIdx.x;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int r0 = aoff.n ? aoff.off[f] : res_off[f], r1 = aoff.n ? aoff.off[f + 1] : res_off[f + 1];
-  const double fx = intr[4 * f], fyv = intr[4 * f + 1], cx = intr[4 * f + 2], cy = intr[4 * f + 3];
+  const int r0 = 0, r1 = nres;
   double xs[6], xn[6], sc[6], JtJ[21], Jtr[6];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) { xs[k] = (double)pose_init[6 * f + k]; xn[k] = xs[k]; sc[k] = 1.0; }
+  for (int k = 0; k < 6; ++k) { xs[k] = (double)pose_init[k]; xn[k] = xs[k]; sc[k] = 1.0; }
   if (r1 == r0) {
-    if (t < 6) pose_out[6 * f + t] = xs[t];
-    if (t == 0) { lorb_ba_summary z = {}; sums[f] = z; }
+    if (t < 6) pose_out[t] = xs[t];
+    if (t == 0) { lorb_ba_summary z = {}; *sum = z; }
     return;
   }
   double radius = o.init_radius, df = 2.0;
@@ -1101,10 +1100,7 @@ __global__ __launch_bounds__(kPoThreads) void k_ba_pose_only(PoOff aoff, const i
   double cX[kPoC][3], cuv[kPoC][2];
 #pragma unroll
   for (int q = 0; q < kPoC; ++q) {
-    const int r = min(r0 + t + kPoThreads * q, r1 - 1);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) cX[q][k] = pts3d[3 * r + k];
-    cuv[q][0] = obs2d[2 * r]; cuv[q][1] = obs2d[2 * r + 1];
+    load(min(r0 + t + kPoThreads * q, r1 - 1), cX[q], cuv[q]);
   }
   for (;;) {
     if (relin) {
@@ -1128,8 +1124,9 @@ __global__ __launch_bounds__(kPoThreads) void k_ba_pose_only(PoOff aoff, const i
       for (int q = 0; q < kPoC; ++q)
         if (r0 + t + kPoThreads * q < r1) acc(cX[q], cuv[q][0], cuv[q][1]);
       for (int r = r0 + t + kPoThreads * kPoC; r < r1; r += kPoThreads) {
-        const double X[3] = {pts3d[3 * r], pts3d[3 * r + 1], pts3d[3 * r + 2]};
-        acc(X, obs2d[2 * r], obs2d[2 * r + 1]);
+        double X[3], uv[2];
+        load(r, X, uv);
+        acc(X, uv[0], uv[1]);
       }
       wave_sum_all<28>(v);
       if (lane == 0) {
@@ -1241,9 +1238,9 @@ __global__ __launch_bounds__(kPoThreads) void k_ba_pose_only(PoOff aoff, const i
           cv += 0.5 * (rr[0] * rr[0] + rr[1] * rr[1]);
         }
       for (int r = r0 + t + kPoThreads * kPoC; r < r1; r += kPoThreads) {
-        const double X[3] = {pts3d[3 * r], pts3d[3 * r + 1], pts3d[3 * r + 2]};
-        double rr[2];
-        residual_s(R, xn + 3, X, fx, fyv, cx, cy, obs2d[2 * r], obs2d[2 * r + 1], rr);
+        double X[3], uv[2], rr[2];
+        load(r, X, uv);
+        residual_s(R, xn + 3, X, fx, fyv, cx, cy, uv[0], uv[1], rr);
         cv += 0.5 * (rr[0] * rr[0] + rr[1] * rr[1]);
       }
     }
@@ -1278,13 +1275,94 @@ __global__ __launch_bounds__(kPoThreads) void k_ba_pose_only(PoOff aoff, const i
   }
 #pragma unroll
   for (int k = 0; k < 6; ++k)
-    if (t == k) pose_out[6 * f + k] = xs[k];
+    if (t == k) pose_out[k] = xs[k];
   if (t == 0) {
     lorb_ba_summary sm;
     sm.iterations = iter; sm.successful_steps = n_success; sm.termination = term; sm.pad_ = 0;
     sm.initial_cost = initial_cost; sm.final_cost = cost;
-    sums[f] = sm;
+    *sum = sm;
   }
+}
+__global__ __launch_bounds__(kPoThreads) void k_ba_pose_only(PoOff aoff, const int32_t* __restrict__ res_off,
+                                                             const float* __restrict__ intr,
+                                                             const float* __restrict__ pose_init,
+                                                             const float* __restrict__ pts3d,
+                                                             const float* __restrict__ obs2d, LMOpt o,
+                                                             double* __restrict__ pose_out,
+                                                             lorb_ba_summary* __restrict__ sums) {
+  const int f = blockIdx.x;
+  const int r0 = aoff.n ? aoff.off[f] : res_off[f], r1 = aoff.n ? aoff.off[f + 1] : res_off[f + 1];
+  const float* P = pts3d + 3 * (size_t)r0;
+  const float* U = obs2d + 2 * (size_t)r0;
+  po_run(r1 - r0, intr[4 * f], intr[4 * f + 1], intr[4 * f + 2], intr[4 * f + 3], pose_init + 6 * f, o,
+         [&](int r, double (&X)[3], double (&uv)[2]) {
+#pragma unroll
+           for (int k = 0; k < 3; ++k) X[k] = P[3 * r + k];
+           uv[0] = U[2 * r]; uv[1] = U[2 * r + 1];
+         },
+         pose_out + 6 * f, sums + f);
+}
+
+// The tail of the motion-tracking chain (VisualOdometry::EstimatePoseMotion after its matcher
+// calls), one workgroup: which pass counts (pass 1 unless it found <= min_matches, then the retry,
+// which must itself find more), the final assign codes, the slots holding a map point afterwards
+// compacted in ascending slot order by a workgroup scan (src/bundle_adjust.cpp:173-186 walks the
+// slots in order), and the pose-only LM over them.  The first kPoRegRes residuals are listed by slot
+// in LDS and each thread loads its own straight into the registers the LM keeps them in; later ones
+// go through a list in global memory written before the barrier that ends the compaction.
+__global__ __launch_bounds__(kPoThreads) void k_track_tail(lorb::TrackTail a, LMOpt o) {
+  __shared__ int s_slot[kPoRegRes];
+  __shared__ int wsum[kPoW];
+  const int t = threadIdx.x;
+  const int nm1 = *a.nm1;
+  const bool retry = nm1 <= a.min_matches;
+  const int nm2 = retry ? *a.nm2 : -1;
+  const int pass = !retry ? 1 : (nm2 > a.min_matches ? 2 : 0);
+  const int* code = retry ? a.assign2 : a.assign;
+  int nres = 0;
+  for (int c0 = 0; c0 < a.nk; c0 += kPoThreads) {
+    const int j = c0 + t;
+    int cd = LORB_ASSIGN_NULL;
+    bool has = false;
+    if (j < a.nk) {
+      cd = code[j];
+      has = cd >= 0 || (!retry && cd == LORB_ASSIGN_UNCHANGED && a.slot_state && a.slot_state[j] != LORB_SLOT_EMPTY);
+      if (retry) a.assign[j] = cd;
+      if (a.assign_out) a.assign_out[j] = cd;
+    }
+    int tot;
+    const int r = nres + lorb::block_excl_scan<kPoThreads>(has ? 1 : 0, wsum, &tot);
+    if (has) {
+      if (r < kPoRegRes) {
+        s_slot[r] = j;
+      } else {
+        const float* X = cd >= 0 ? a.last_pos + 3 * (size_t)cd : a.slot_pos + 3 * (size_t)j;
+        float* L = a.list + 5 * (size_t)r;
+        L[0] = X[0]; L[1] = X[1]; L[2] = X[2]; L[3] = a.x[j]; L[4] = a.y[j];
+      }
+    }
+    nres += tot;
+  }
+  __syncthreads();  // s_slot and the list are complete (the scan's barriers order the loop itself)
+  if (t == 0) {
+    a.rec->pass = pass; a.rec->nmatches_first = nm1; a.rec->nmatches_retry = nm2; a.rec->n_residuals = nres;
+  }
+  po_run(pass ? nres : 0, a.fx, a.fy_eff, a.cx, a.cy, a.pose_init, o,
+         [&](int r, double (&X)[3], double (&uv)[2]) {
+           if (r < kPoRegRes) {
+             const int j = s_slot[r], cd = code[j];
+             const float* Xp = cd >= 0 ? a.last_pos + 3 * (size_t)cd : a.slot_pos + 3 * (size_t)j;
+#pragma unroll
+             for (int k = 0; k < 3; ++k) X[k] = Xp[k];
+             uv[0] = a.x[j]; uv[1] = a.y[j];
+           } else {
+             const float* L = a.list + 5 * (size_t)r;
+#pragma unroll
+             for (int k = 0; k < 3; ++k) X[k] = L[k];
+             uv[0] = L[3]; uv[1] = L[4];
+           }
+         },
+         a.rec->pose, &a.rec->summary);
 }
 
 LMOpt to_dev_opt(const lorb_lm_options* o) {
@@ -2777,6 +2855,12 @@ int ba_plan_result64_dev(lorb_ba_plan* P, double* d_out) {
   LORB_CHECK_LAUNCH(P->ctx);
   return LORB_OK;
 }
+int launch_track_tail(lorb_ctx* ctx, const TrackTail& t, const lorb_lm_options* opt) {
+  hipLaunchKernelGGL(k_track_tail, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, to_dev_opt(opt));
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
+
 }  // namespace lorb
 
 namespace {
@@ -3482,6 +3566,21 @@ int lorb_ba_pose_only(lorb_ctx* ctx, const lorb_pose_problem_batch* prob,
       const float T[3] = {(float)pose_out[6 * f + 3], (float)pose_out[6 * f + 4], (float)pose_out[6 * f + 5]};
       lorb_pose_to_Tcw(R, T, Tcw_out + 16 * f);
     }
+  return LORB_OK;
+}
+
+int lorb_ba_pose_only_dev(lorb_ctx* ctx, const lorb_pose_problem_batch* d_prob, const lorb_lm_options* opt,
+                          double* d_pose_out, lorb_ba_summary* d_summaries) {
+  if (!ctx || !d_prob || !opt) return LORB_E_INVALID;
+  const int nf = d_prob->n_frames;
+  if (nf <= 0) return LORB_OK;
+  if (!d_prob->res_off || !d_prob->intr || !d_prob->pose_init || !d_pose_out || !d_summaries)
+    return lorb::set_error(ctx, LORB_E_INVALID, "null array");
+  // the offsets live on the device: the kernel reads them from memory (aoff.n == 0)
+  PoOff aoff{};
+  hipLaunchKernelGGL(k_ba_pose_only, dim3(nf), dim3(kPoThreads), 0, ctx->stream, aoff, d_prob->res_off, d_prob->intr,
+                     d_prob->pose_init, d_prob->pts3d, d_prob->obs2d, to_dev_opt(opt), d_pose_out, d_summaries);
+  LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
 }
 

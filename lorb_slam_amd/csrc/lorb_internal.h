@@ -49,6 +49,9 @@ struct lorb_ctx {
   void* io_out_dev = nullptr;
   size_t io_out_sz = 0;
   bool io_pending = false;  // an InPack pull may still read the staging (cleared by OutPack::fetch)
+  // S_TM_ZERO as last cleared: an all-EMPTY slot-state array nothing ever writes (lorb_track_motion*)
+  void* zero_ss = nullptr;
+  size_t zero_ss_sz = 0;
 };
 
 namespace lorb {
@@ -381,6 +384,25 @@ __device__ __forceinline__ void unproject_point(float fx, float fy, float cx, fl
 // cv::Mat::inv() of a 4x4 CV_32F (hal::LU32f), host side (lorb_window.hip)
 bool inv4_lu32f(const float* A, float* out);
 
+// The tail of the motion-tracking chain (lorb_track_motion*, lorb_window.hip): one launch of
+// k_track_tail (lorb_ba.hip) after both a4 passes -- pass decision, final assign, residual
+// compaction, pose-only LM, result record.  All pointers are device pointers.
+struct TrackTail {
+  int nk;
+  const int *nm1, *nm2;          // the passes' match counts (nm2 is read only if the retry ran)
+  const int *assign2;            // pass 2's codes (pass 1's are already in assign)
+  int* assign;                   // nk: pass 1's codes on entry, the codes that count on exit
+  const uint8_t* slot_state;     // null: all EMPTY
+  const float *slot_pos, *last_pos, *x, *y;
+  int min_matches;
+  float fx, fy_eff, cx, cy, pose_init[6];
+  float* list;                   // 5 floats per slot (point | observation): residuals past the
+                                 // LM's register-resident ones
+  lorb_track_motion_result* rec; // the record (device memory, or the mapped result block)
+  int* assign_out;               // non-null: the final codes are also stored here (mapped block)
+};
+int launch_track_tail(lorb_ctx* ctx, const TrackTail& t, const lorb_lm_options* opt);
+
 // Four counters (plain POD: HIP's int4 member proxies are avoided in arithmetic-heavy code).
 struct I4 {
   int v[4];
@@ -428,6 +450,8 @@ enum {
   S_W0 = 14, S_W1, S_W2, S_W3, S_W4, S_W5, S_W6, S_W7, S_W8, S_W9,
   S_KP = 24,   /* 10 slots: keypoint upload + grid */
   S_WX = 34,   /* 8 slots: windowed-matcher scratch */
+  S_TM = 88,   /* 3 slots: motion-tracking chain (pass 2's codes + both counts, the residual list, the host form's codes) */
+  S_TM_ZERO = 91, /* all-EMPTY slot states: zeroed when (re)allocated, never written */
   S_BF_TKEY = 120, /* crossCheck per-train keys: all-ones between calls (the merge resets them) */
   S_IO_IN = 121,   /* InPack device block */
   S_IO_OUT = 122,  /* OutPack device block */

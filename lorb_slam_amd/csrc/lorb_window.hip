@@ -30,6 +30,7 @@ struct WinParams {  // per-call scalars (device copy of lorb_frame_params)
   float th;
   int mode_forward, mode_backward;  // a4 only
   float Rcw[9], tcw[3];             // a4 only
+  int oct_limit;                    // a4 only: a last-frame point with an octave outside [0, oct_limit) is inactive
 };
 
 __device__ __forceinline__ int hamming(const uint4* a, const uint4* b) {
@@ -372,10 +373,14 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_cand_frame(KpDev K, WinPara
                                                     const int* __restrict__ loct,
                                                     const uint4* __restrict__ ldesc,
                                                     int* __restrict__ cand_cnt, const int* __restrict__ cand_off,
-                                                    int2* __restrict__ cand, int stride = 0) {
+                                                    int2* __restrict__ cand, int stride = 0,
+                                                    const int* __restrict__ skip_unless = nullptr, int skip_max = 0) {
+  // a predicated pass (the motion chain's retry): runs only if *skip_unless <= skip_max
+  if (skip_unless && *skip_unless > skip_max) return;
   const int i = blockIdx.x * kCandWaves + (threadIdx.x >> 6);
   // the query's inputs requested first (GRID: they arrive while the keypoints are staged)
-  const FrameQuery q = frame_query(min(i, nl - 1), has_mp, outlier, pos, loct);
+  FrameQuery q = frame_query(min(i, nl - 1), has_mp, outlier, pos, loct);
+  q.act = q.act && (unsigned)q.o < (unsigned)P.oct_limit;
   if constexpr (GRID) {
     __shared__ KpLds L;
     K = stage_grid<64 * kCandWaves>(K, P.fp, L);
@@ -603,7 +608,9 @@ __global__ __launch_bounds__(1024) void k_resolve(int np, int nk, const int* __r
                                                   int* __restrict__ res, int* __restrict__ claim,
                                                   int* __restrict__ assign, int* __restrict__ bins,
                                                   int* __restrict__ nulls, int* __restrict__ nmatches, int lds_mode,
-                                                  int stride = 0, int* __restrict__ out = nullptr) {
+                                                  int stride = 0, int* __restrict__ out = nullptr,
+                                                  const int* __restrict__ skip_unless = nullptr, int skip_max = 0) {
+  if (skip_unless && *skip_unless > skip_max) return;  // a predicated pass, as k_cand_frame
   // the working set in LDS (dynamic shared memory) as far as it fits (resolve_lds_mode), else global
   extern __shared__ int s_dyn[];
   int* wassign = assign;
@@ -755,6 +762,139 @@ int kps_finish(lorb_ctx* ctx, const lorb::InPack& in, const KpParts& p, int n, i
   return LORB_OK;
 }
 
+// a4's per-call scalars.  src/matcher.cpp:74-87: motion direction from the two poses (cv::gemm:
+// double accumulation)
+WinParams frame_params_a4(const lorb_frame_params* cur, const float* cur_Tcw, const float* last_Tcw, float th,
+                          int oct_limit) {
+  WinParams P{};
+  P.fp = *cur;
+  P.th = th;
+  P.oct_limit = std::min(std::max(oct_limit, 0), LORB_MAX_LEVELS);
+  const float* T = cur_Tcw;
+  const float Rcw[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+  const float tcw[3] = {T[3], T[7], T[11]};
+  memcpy(P.Rcw, Rcw, sizeof(Rcw));
+  memcpy(P.tcw, tcw, sizeof(tcw));
+  float twc[3];
+  for (int i = 0; i < 3; i++) {
+    const double s = (double)Rcw[i] * tcw[0] + (double)Rcw[3 + i] * tcw[1] + (double)Rcw[6 + i] * tcw[2];
+    twc[i] = (float)(-s);
+  }
+  const float* L = last_Tcw;
+  const double s2 = (double)L[8] * twc[0] + (double)L[9] * twc[1] + (double)L[10] * twc[2];
+  const float tlc2 = (float)(s2 + (double)L[11]);
+  P.mode_forward = tlc2 > cur->b;
+  P.mode_backward = -tlc2 > cur->b;
+  return P;
+}
+
+struct LastDev {  // lorb_last_frame's arrays on the device
+  int n;
+  const uint8_t *hm, *ol, *lk;
+  const float *pos, *la;
+  const int* lo;
+  const uint4* ld;
+};
+LastDev last_dev(const lorb_last_frame* l) {
+  return {l->n, l->has_mp, l->outlier, l->mp_locked, l->mp_pos, l->angle, l->octave,
+          reinterpret_cast<const uint4*>(l->mp_desc)};
+}
+KpDev kp_dev(const lorb_keypoints* k, const uint8_t* slot_state) {
+  KpDev K;
+  K.x = k->x; K.y = k->y; K.angle = k->angle; K.uR = k->u_right; K.octave = k->octave;
+  K.desc = reinterpret_cast<const uint4*>(k->desc); K.slot_state = slot_state;
+  K.cell_off = nullptr; K.cell_idx = nullptr; K.n = k->n;
+  return K;
+}
+// argument checks shared by the device-pointer a4 and the motion chain
+int frame_dev_check(lorb_ctx* ctx, const lorb_frame_params* cur, const lorb_keypoints* k, const lorb_last_frame* l) {
+  const int nk = k->n, nl = l->n;
+  if (nk < 0 || nl < 0) return lorb::set_error(ctx, LORB_E_INVALID, "negative sizes");
+  if (cur->n_levels < 1 || cur->n_levels > LORB_MAX_LEVELS)
+    return lorb::set_error(ctx, LORB_E_INVALID, "n_levels %d out of range", cur->n_levels);
+  if (!l->Tcw || (nk > 0 && (!k->x || !k->y || !k->octave || !k->angle || !k->desc)) ||
+      (nl > 0 && (!l->has_mp || !l->mp_locked || !l->mp_pos || !l->mp_desc || !l->octave || !l->angle)))
+    return lorb::set_error(ctx, LORB_E_INVALID, "null array");
+  return LORB_OK;
+}
+// n all-EMPTY slot states: a buffer cleared when it is (re)allocated and never written afterwards
+int empty_slots(lorb_ctx* ctx, int n, const uint8_t** out) {
+  uint8_t* z;
+  LORB_TRY(lorb::scratch_t(ctx, S_TM_ZERO, (size_t)std::max(n, 1), &z));
+  if (ctx->zero_ss != z || ctx->zero_ss_sz != ctx->scratch_sz[S_TM_ZERO]) {  // a grown buffer may reuse the address
+    LORB_HIP(ctx, hipMemsetAsync(z, 0, ctx->scratch_sz[S_TM_ZERO], ctx->stream));
+    ctx->zero_ss = z;
+    ctx->zero_ss_sz = ctx->scratch_sz[S_TM_ZERO];
+  }
+  *out = z;
+  return LORB_OK;
+}
+
+// The launches of one a4 pass on device-resident inputs, shared by the host-array call, the
+// device-pointer call and the motion chain: the keypoint grid where the candidate kernel does not
+// build its own (once per *K: a second pass over the same keypoints reuses it), the candidate lists
+// (one strided pass up to kCandStrided entries, else count / scan / write), the resolver.  dassign
+// (nk ints) and dnm get the codes and the count; out (or null) is the mapped result block of a
+// host-array call.  skip_unless: a predicated pass, whose kernels return at once unless
+// *skip_unless <= skip_max.  The working buffers (S_WX, S_W9) are the same for every pass.
+int a4_issue(lorb_ctx* ctx, KpDev* K, const WinParams& P, const LastDev& L, int* dassign, int* dnm, int* out,
+             const int* skip_unless = nullptr, int skip_max = 0) {
+  const int nk = K->n, nl = L.n;
+  // a query has at most nk candidates: up to kCandStrided entries one pass writes them at i * nk
+  // (no count pass, no scan); past it the count / scan / write passes size the list exactly
+  const bool strided = (size_t)nl * (size_t)nk <= kCandStrided;
+  const bool lds_grid = strided && nk <= kStageKps;  // the candidate kernel builds the grid itself
+  if (!lds_grid && !K->cell_off) {
+    int *cell_off, *cell_idx, *kp_cell;
+    LORB_TRY(lorb::scratch_t(ctx, S_KP + 7, kCells + 1, &cell_off));
+    LORB_TRY(lorb::scratch_t(ctx, S_KP + 8, (size_t)std::max(nk, 1), &cell_idx));
+    LORB_TRY(lorb::scratch_t(ctx, S_KP + 9, (size_t)std::max(nk, 1), &kp_cell));
+    hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(1024), 0, ctx->stream, K->x, K->y, nk, P.fp, cell_off, cell_idx, kp_cell);
+    LORB_CHECK_LAUNCH(ctx);
+    K->cell_off = cell_off; K->cell_idx = cell_idx;
+  }
+  int *cnt, *off, *res, *claim, *bins, *nulls;
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 0, (size_t)nl + 1, &cnt));
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 1, (size_t)nl + 1, &off));
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 2, (size_t)nl + 1, &res));
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 3, (size_t)nk + 1, &claim));
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 5, (size_t)nl + 1, &bins));
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 6, (size_t)nk + 1, &nulls));
+  const unsigned g = lorb::ceil_div(std::max(nl, 1), kCandWaves);
+  int2* cand;
+  if (strided) {
+    LORB_TRY(lorb::scratch_t(ctx, S_W9, std::max<size_t>((size_t)nl * nk, 1), &cand));
+    if (nl > 0) {
+      lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
+      if (lds_grid)
+        hipLaunchKernelGGL((k_cand_frame<true, true>), dim3(g), dim3(256), 0, ctx->stream, *K, P, nl, L.hm, L.ol, L.pos,
+                           L.lo, L.ld, cnt, (const int*)nullptr, cand, nk, skip_unless, skip_max);
+      else
+        hipLaunchKernelGGL(k_cand_frame<true>, dim3(g), dim3(256), 0, ctx->stream, *K, P, nl, L.hm, L.ol, L.pos, L.lo,
+                           L.ld, cnt, (const int*)nullptr, cand, nk, skip_unless, skip_max);
+    }
+  } else {
+    if (nl > 0) {
+      lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
+      hipLaunchKernelGGL(k_cand_frame<false>, dim3(g), dim3(256), 0, ctx->stream, *K, P, nl, L.hm, L.ol, L.pos, L.lo,
+                         L.ld, cnt, (const int*)nullptr, (int2*)nullptr, 0, skip_unless, skip_max);
+    }
+    // a skipped pass leaves cnt as the pass before wrote it: the scan then sizes a list nobody fills
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, nl, off);
+    LORB_TRY(alloc_candidates(ctx, off + nl, (size_t)nl * (size_t)nk, &cand));
+    if (nl > 0)
+      hipLaunchKernelGGL(k_cand_frame<true>, dim3(g), dim3(256), 0, ctx->stream, *K, P, nl, L.hm, L.ol, L.pos, L.lo,
+                         L.ld, cnt, off, cand, 0, skip_unless, skip_max);
+  }
+  size_t rlds = 0;
+  const int rmode = resolve_lds_mode(nl, nk, &rlds);
+  hipLaunchKernelGGL(k_resolve<1>, dim3(1), dim3(1024), rlds, ctx->stream, nl, nk,
+                     strided ? (const int*)cnt : (const int*)off, cand, L.lk, L.la, K->angle, res, claim, dassign, bins,
+                     nulls, dnm, rmode, strided ? nk : 0, out, skip_unless, skip_max);
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -848,25 +988,7 @@ int lorb_search_by_projection_frame(lorb_ctx* ctx, const lorb_frame_params* cur,
   for (int i = 0; i < nl; ++i)
     if (last->has_mp[i] && (last->octave[i] < 0 || last->octave[i] >= LORB_MAX_LEVELS))
       return lorb::set_error(ctx, LORB_E_INVALID, "last keypoint %d: octave %d out of range", i, last->octave[i]);
-  // src/matcher.cpp:74-87: motion direction from the two poses (cv::gemm: double accumulation)
-  WinParams P{};
-  P.fp = *cur;
-  P.th = th;
-  const float* T = cur_Tcw;
-  const float Rcw[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-  const float tcw[3] = {T[3], T[7], T[11]};
-  memcpy(P.Rcw, Rcw, sizeof(Rcw));
-  memcpy(P.tcw, tcw, sizeof(tcw));
-  float twc[3];
-  for (int i = 0; i < 3; i++) {
-    const double s = (double)Rcw[i] * tcw[0] + (double)Rcw[3 + i] * tcw[1] + (double)Rcw[6 + i] * tcw[2];
-    twc[i] = (float)(-s);
-  }
-  const float* L = last->Tcw;
-  const double s2 = (double)L[8] * twc[0] + (double)L[9] * twc[1] + (double)L[10] * twc[2];
-  const float tlc2 = (float)(s2 + (double)L[11]);
-  P.mode_forward = tlc2 > cur->b;
-  P.mode_backward = -tlc2 > cur->b;
+  const WinParams P = frame_params_a4(cur, cur_Tcw, last->Tcw, th, LORB_MAX_LEVELS);  // octaves checked above
   // every input in one pull, the result stored straight into pinned memory by k_resolve
   lorb::InPack in(ctx);
   KpParts kp;
@@ -875,63 +997,135 @@ int lorb_search_by_projection_frame(lorb_ctx* ctx, const lorb_frame_params* cur,
             i_pos = in.add_t(last->mp_pos, (size_t)nl * 3), i_ld = in.add_t(last->mp_desc, (size_t)nl * 32),
             i_lo = in.add_t(last->octave, nl), i_la = in.add_t(last->angle, nl);
   LORB_TRY(in.commit());
-  // a query has at most nk candidates: up to kCandStrided entries one pass writes them at i * nk
-  // (no count pass, no scan); past it the count / scan / write passes size the list exactly
-  const bool strided = (size_t)nl * (size_t)nk <= kCandStrided;
-  const bool lds_grid = strided && nk <= kStageKps;  // the candidate kernel builds the grid itself
   KpDev K;
-  LORB_TRY(kps_finish(ctx, in, kp, nk, S_KP, &K, cur, !lds_grid));
-  const uint8_t *hm = in.dev<uint8_t>(i_hm), *ol = in.dev<uint8_t>(i_ol), *lk = in.dev<uint8_t>(i_lk),
-                *ld = in.dev<uint8_t>(i_ld);
-  const float *pos = in.dev<float>(i_pos), *la = in.dev<float>(i_la);
-  const int* lo = in.dev<int>(i_lo);
-  int *cnt, *off, *res, *claim, *dassign, *dnm, *bins, *nulls;
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 0, (size_t)nl + 1, &cnt));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 1, (size_t)nl + 1, &off));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 2, (size_t)nl + 1, &res));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 3, (size_t)nk + 1, &claim));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 5, (size_t)nl + 1, &bins));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 6, (size_t)nk + 1, &nulls));
+  LORB_TRY(kps_finish(ctx, in, kp, nk, S_KP, &K, cur, false));  // a4_issue builds the grid where it needs one
+  const LastDev L = {nl, in.dev<uint8_t>(i_hm), in.dev<uint8_t>(i_ol), in.dev<uint8_t>(i_lk), in.dev<float>(i_pos),
+                     in.dev<float>(i_la), in.dev<int>(i_lo), in.dev<const uint4>(i_ld)};
+  int* dassign;
   LORB_TRY(lorb::scratch_t(ctx, S_WX + 4, (size_t)nk + 1, &dassign));
-  dnm = dassign + nk;
   lorb::OutPack out(ctx);
   const int o_as = out.add(sizeof(int) * ((size_t)nk + 1));
   LORB_TRY(out.alloc(true));  // k_resolve writes assign + count into the mapped block
-  const unsigned g = lorb::ceil_div(std::max(nl, 1), kCandWaves);
-  int2* cand;
-  if (strided) {
-    LORB_TRY(lorb::scratch_t(ctx, S_W9, std::max<size_t>((size_t)nl * nk, 1), &cand));
-    if (nl > 0) {
-      lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
-      if (lds_grid)
-        hipLaunchKernelGGL((k_cand_frame<true, true>), dim3(g), dim3(256), 0, ctx->stream, K, P, nl, hm, ol, pos, lo,
-                           reinterpret_cast<const uint4*>(ld), cnt, (const int*)nullptr, cand, nk);
-      else
-        hipLaunchKernelGGL(k_cand_frame<true>, dim3(g), dim3(256), 0, ctx->stream, K, P, nl, hm, ol, pos, lo,
-                           reinterpret_cast<const uint4*>(ld), cnt, (const int*)nullptr, cand, nk);
-    }
-  } else {
-    if (nl > 0) {
-      lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
-      hipLaunchKernelGGL(k_cand_frame<false>, dim3(g), dim3(256), 0, ctx->stream, K, P, nl, hm, ol, pos, lo,
-                         reinterpret_cast<const uint4*>(ld), cnt, (const int*)nullptr, (int2*)nullptr, 0);
-    }
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, nl, off);
-    LORB_TRY(alloc_candidates(ctx, off + nl, (size_t)nl * (size_t)nk, &cand));
-    if (nl > 0)
-      hipLaunchKernelGGL(k_cand_frame<true>, dim3(g), dim3(256), 0, ctx->stream, K, P, nl, hm, ol, pos, lo,
-                         reinterpret_cast<const uint4*>(ld), cnt, off, cand, 0);
-  }
-  size_t rlds = 0;
-  const int rmode = resolve_lds_mode(nl, nk, &rlds);
-  hipLaunchKernelGGL(k_resolve<1>, dim3(1), dim3(1024), rlds, ctx->stream, nl, nk,
-                     strided ? (const int*)cnt : (const int*)off, cand, lk,
-                     la, K.angle, res, claim, dassign, bins, nulls, dnm,
-                     rmode, strided ? nk : 0, out.dev<int>(o_as));
-  LORB_CHECK_LAUNCH(ctx);
+  LORB_TRY(a4_issue(ctx, &K, P, L, dassign, dassign + nk, out.dev<int>(o_as)));
   LORB_TRY(out.fetch());
   memcpy(assign, out.host<int>(o_as), sizeof(int) * nk);
   *nmatches = out.host<int>(o_as)[nk];
+  return LORB_OK;
+}
+
+int lorb_search_by_projection_frame_dev(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16],
+                                        const lorb_keypoints* d_cur_kps, const uint8_t* d_cur_slot_state,
+                                        const lorb_last_frame* d_last, float th, int32_t* d_assign,
+                                        int32_t* d_nmatches) {
+  if (!ctx || !cur || !cur_Tcw || !d_cur_kps || !d_last || !d_nmatches) return LORB_E_INVALID;
+  const int nk = d_cur_kps->n;
+  LORB_TRY(frame_dev_check(ctx, cur, d_cur_kps, d_last));
+  if (nk == 0) {
+    LORB_HIP(ctx, hipMemsetAsync(d_nmatches, 0, sizeof(int32_t), ctx->stream));
+    return LORB_OK;
+  }
+  if (!d_assign) return lorb::set_error(ctx, LORB_E_INVALID, "null array");
+  WinParams P = frame_params_a4(cur, cur_Tcw, d_last->Tcw, th, cur->n_levels);
+  const uint8_t* ss = d_cur_slot_state;
+  if (!ss) LORB_TRY(empty_slots(ctx, nk, &ss));
+  KpDev K = kp_dev(d_cur_kps, ss);
+  return a4_issue(ctx, &K, P, last_dev(d_last), d_assign, d_nmatches, nullptr);
+}
+
+// VisualOdometry::EstimatePoseMotion (src/visual_odometry.cpp:117-138) on device-resident data:
+// a4 at th_first into d_assign, a4 at th_retry over all-EMPTY slots into a buffer of its own --
+// always enqueued, its kernels returning at once unless the first pass found <= min_matches --
+// then the tail kernel (pass decision, final codes, residual gathering, pose-only LM).  The second
+// pass reuses the first's keypoint grid and working buffers (the stream orders them).
+static int track_motion_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const float* cur_Tcw,
+                              const float* pose_init, KpDev K, const float* slot_pos, const LastDev& L,
+                              const float* last_Tcw, const lorb_track_motion_params* par,
+                              const lorb_lm_options* opt, int* d_assign, lorb_track_motion_result* rec,
+                              int* assign_out) {
+  const int nk = K.n;
+  int* tm;  // pass 2's codes (nk) | its count | pass 1's count
+  float* list;
+  LORB_TRY(lorb::scratch_t(ctx, S_TM + 0, (size_t)nk + 2, &tm));
+  LORB_TRY(lorb::scratch_t(ctx, S_TM + 1, (size_t)std::max(nk, 1) * 5, &list));
+  int *nm2 = tm + nk, *nm1 = tm + nk + 1;
+  const uint8_t* given = K.slot_state;
+  if (nk == 0) {
+    LORB_HIP(ctx, hipMemsetAsync(nm2, 0, 2 * sizeof(int), ctx->stream));  // nothing to match: both passes find 0
+  } else {
+    const uint8_t* z;
+    LORB_TRY(empty_slots(ctx, nk, &z));
+    if (!given) K.slot_state = z;
+    LORB_TRY(a4_issue(ctx, &K, frame_params_a4(cur, cur_Tcw, last_Tcw, par->th_first, cur->n_levels), L, d_assign, nm1,
+                      nullptr));
+    K.slot_state = z;  // src/visual_odometry.cpp:128: the retry starts from emptied slots
+    LORB_TRY(a4_issue(ctx, &K, frame_params_a4(cur, cur_Tcw, last_Tcw, par->th_retry, cur->n_levels), L, tm, nm2, nullptr,
+                      nm1, par->min_matches));
+  }
+  lorb::TrackTail t{};
+  t.nk = nk; t.nm1 = nm1; t.nm2 = nm2; t.assign2 = tm; t.assign = d_assign;
+  t.slot_state = given; t.slot_pos = slot_pos; t.last_pos = L.pos; t.x = K.x; t.y = K.y;
+  t.min_matches = par->min_matches;
+  t.fx = cur->fx; t.fy_eff = par->fy_eff; t.cx = cur->cx; t.cy = cur->cy;
+  memcpy(t.pose_init, pose_init, sizeof(t.pose_init));
+  t.list = list; t.rec = rec; t.assign_out = assign_out;
+  return lorb::launch_track_tail(ctx, t, opt);
+}
+
+int lorb_track_motion_dev(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16],
+                          const float pose_init[6], const lorb_keypoints* d_cur_kps, const uint8_t* d_slot_state,
+                          const float* d_slot_pos, const lorb_last_frame* d_last,
+                          const lorb_track_motion_params* par, const lorb_lm_options* opt, int32_t* d_assign,
+                          lorb_track_motion_result* d_result) {
+  if (!ctx || !cur || !cur_Tcw || !pose_init || !d_cur_kps || !d_last || !par || !opt || !d_result) return LORB_E_INVALID;
+  LORB_TRY(frame_dev_check(ctx, cur, d_cur_kps, d_last));
+  if (par->min_matches < 0) return lorb::set_error(ctx, LORB_E_INVALID, "min_matches %d is negative", par->min_matches);
+  if ((d_cur_kps->n > 0 && !d_assign) || (d_slot_state && !d_slot_pos))
+    return lorb::set_error(ctx, LORB_E_INVALID, "null array");
+  return track_motion_issue(ctx, cur, cur_Tcw, pose_init, kp_dev(d_cur_kps, d_slot_state), d_slot_pos, last_dev(d_last),
+                            d_last->Tcw, par, opt, d_assign, d_result, nullptr);
+}
+
+int lorb_track_motion(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16], const float pose_init[6],
+                      const lorb_keypoints* cur_kps, const uint8_t* slot_state, const float* slot_pos,
+                      const lorb_last_frame* last, const lorb_track_motion_params* par, const lorb_lm_options* opt,
+                      int32_t* assign, lorb_track_motion_result* result, float* Tcw_out) {
+  if (!ctx || !cur || !cur_Tcw || !pose_init || !cur_kps || !last || !par || !opt || !result) return LORB_E_INVALID;
+  LORB_TRY(frame_dev_check(ctx, cur, cur_kps, last));
+  const int nk = cur_kps->n, nl = last->n;
+  if (par->min_matches < 0) return lorb::set_error(ctx, LORB_E_INVALID, "min_matches %d is negative", par->min_matches);
+  if ((nk > 0 && !assign) || (slot_state && !slot_pos)) return lorb::set_error(ctx, LORB_E_INVALID, "null array");
+  for (int i = 0; i < nl; ++i)
+    if (last->has_mp[i] && (last->octave[i] < 0 || last->octave[i] >= LORB_MAX_LEVELS))
+      return lorb::set_error(ctx, LORB_E_INVALID, "last keypoint %d: octave %d out of range", i, last->octave[i]);
+  // every input in one pull; the tail kernel stores assign and the record into the mapped block
+  lorb::InPack in(ctx);
+  KpParts kp;
+  kps_add(in, cur_kps, slot_state, kp);
+  const int i_sp = in.add_t(slot_state ? slot_pos : nullptr, (size_t)nk * 3);
+  const int i_hm = in.add_t(last->has_mp, nl), i_ol = in.add_t(last->outlier, nl), i_lk = in.add_t(last->mp_locked, nl),
+            i_pos = in.add_t(last->mp_pos, (size_t)nl * 3), i_ld = in.add_t(last->mp_desc, (size_t)nl * 32),
+            i_lo = in.add_t(last->octave, nl), i_la = in.add_t(last->angle, nl);
+  LORB_TRY(in.commit());
+  KpDev K;
+  LORB_TRY(kps_finish(ctx, in, kp, nk, S_KP, &K, cur, false));  // a4_issue builds the grid where it needs one
+  if (!slot_state) K.slot_state = nullptr;  // all EMPTY: the chain reads its own zeroed buffer
+  const LastDev L = {nl, in.dev<uint8_t>(i_hm), in.dev<uint8_t>(i_ol), in.dev<uint8_t>(i_lk), in.dev<float>(i_pos),
+                     in.dev<float>(i_la), in.dev<int>(i_lo), in.dev<const uint4>(i_ld)};
+  int* dassign;
+  LORB_TRY(lorb::scratch_t(ctx, S_TM + 2, (size_t)nk + 1, &dassign));
+  lorb::OutPack out(ctx);
+  const int o_rec = out.add(sizeof(lorb_track_motion_result)), o_as = out.add(sizeof(int) * ((size_t)nk + 1));
+  LORB_TRY(out.alloc(true));
+  LORB_TRY(track_motion_issue(ctx, cur, cur_Tcw, pose_init, K, in.dev<float>(i_sp), L, last->Tcw, par, opt, dassign,
+                              out.dev<lorb_track_motion_result>(o_rec), out.dev<int>(o_as)));
+  LORB_TRY(out.fetch());
+  if (nk > 0) memcpy(assign, out.host<int>(o_as), sizeof(int) * nk);
+  *result = *out.host<lorb_track_motion_result>(o_rec);
+  if (Tcw_out) {
+    const float R[3] = {(float)result->pose[0], (float)result->pose[1], (float)result->pose[2]};
+    const float T[3] = {(float)result->pose[3], (float)result->pose[4], (float)result->pose[5]};
+    lorb_pose_to_Tcw(R, T, Tcw_out);
+  }
   return LORB_OK;
 }
 

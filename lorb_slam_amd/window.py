@@ -98,6 +98,121 @@ def _track_local_map(self, fp, Tcw, kps, slot_state, pts, cos_limit=0.5, th=1.0)
     return out
 
 
+class _Staged:
+    """Device copies of host arrays for one call (freed by close())."""
+
+    def __init__(self, ctx):
+        self.ctx, self.arrs = ctx, []
+
+    def dev(self, a, dtype):
+        if a is None:
+            return None
+        d = self.ctx.to_device(np.ascontiguousarray(a, dtype))
+        self.arrs.append(d)
+        return d.ptr
+
+    def empty(self, shape, dtype):
+        d = self.ctx.empty(shape, dtype)
+        self.arrs.append(d)
+        return d
+
+    def keypoints(self, kps):
+        return A.KeypointsDev(len(kps["x"]), self.dev(kps["x"], np.float32), self.dev(kps["y"], np.float32),
+                              self.dev(kps["octave"], np.int32), self.dev(kps["angle"], np.float32),
+                              self.dev(kps.get("u_right"), np.float32), self.dev(kps["desc"], np.uint8))
+
+    def last_frame(self, last, keep):
+        T = keep.keep(A.f32(last["Tcw"]).reshape(16))
+        return A.LastFrameDev(len(last["has_mp"]), A.ptr(T, C.c_float), self.dev(last["has_mp"], np.uint8),
+                              self.dev(last.get("outlier"), np.uint8), self.dev(last["mp_locked"], np.uint8),
+                              self.dev(last["mp_pos"], np.float32), self.dev(last["mp_desc"], np.uint8),
+                              self.dev(last["octave"], np.int32), self.dev(last["angle"], np.float32))
+
+    def close(self):
+        for a in self.arrs:
+            a.free()
+
+
+def _search_by_projection_frame_dev(self, fp, cur_Tcw, cur_kps, cur_slot_state, last, th):
+    """lorb_search_by_projection_frame_dev on device copies of the inputs -> (assign, nmatches)."""
+    keep, st = A.KeepAlive(), _Staged(self)
+    try:
+        k, lf = st.keypoints(cur_kps), st.last_frame(last, keep)
+        ss = st.dev(cur_slot_state, np.uint8)
+        asg, nm = st.empty(max(k.n, 1), np.int32), st.empty(1, np.int32)
+        fps = A.make_frame_params(fp)
+        T = A.f32(cur_Tcw).reshape(16)
+        self.check(lib().lorb_search_by_projection_frame_dev(self._p, C.byref(fps), A.ptr(T, C.c_float), C.byref(k), ss,
+                                                             C.byref(lf), C.c_float(th), asg.ptr, nm.ptr),
+                   "lorb_search_by_projection_frame_dev")
+        return asg.numpy()[: k.n], int(nm.numpy()[0])
+    finally:
+        st.close()
+
+
+def _ba_pose_only_dev(self, pb, opt=None):
+    """lorb_ba_pose_only_dev on device copies of the batch -> (pose, summaries)."""
+    st = _Staged(self)
+    try:
+        nf = len(pb["res_off"]) - 1
+        d = A.PoseProblemBatchDev(nf, st.dev(pb["res_off"], np.int32), st.dev(pb["intr"], np.float32),
+                                  st.dev(pb["pose_init"], np.float32), st.dev(pb["pts3d"], np.float32),
+                                  st.dev(pb["obs2d"], np.float32))
+        opt = opt or A.LMOptions.default()
+        pose, summ = st.empty((max(nf, 1), 6), np.float64), st.empty(max(nf, 1) * C.sizeof(A.BASummary), np.uint8)
+        self.check(lib().lorb_ba_pose_only_dev(self._p, C.byref(d), C.byref(opt), pose.ptr, summ.ptr),
+                   "lorb_ba_pose_only_dev")
+        sums = (A.BASummary * max(nf, 1)).from_buffer_copy(summ.numpy().tobytes())
+        return pose.numpy()[:nf], [sums[i].as_dict() for i in range(nf)]
+    finally:
+        st.close()
+
+
+def _track_motion(self, fp, cur_Tcw, pose_init, cur_kps, slot_state, slot_pos, last, th_first=15.0, th_retry=30.0,
+                  min_matches=20, fy_eff=None, opt=None, device_resident=True):
+    """VisualOdometry::EstimatePoseMotion as one call (lorb_track_motion / lorb_track_motion_dev).
+    device_resident=True stages the inputs in device memory first and calls the _dev form.  Returns
+    assign, pass_, nmatches_first, nmatches_retry, n_residuals, pose, summary and Tcw."""
+    fps = A.make_frame_params(fp)
+    par = A.TrackMotionParams(th_first, th_retry, min_matches, fps.fx if fy_eff is None else fy_eff)
+    opt = opt or A.LMOptions.default()
+    T = A.f32(cur_Tcw).reshape(16)
+    pi = A.f32(pose_init).reshape(6)
+    nk = len(cur_kps["x"])
+    rec = A.TrackMotionResult()
+    Tout = np.zeros((4, 4), np.float32)
+    if device_resident:
+        keep, st = A.KeepAlive(), _Staged(self)
+        try:
+            k, lf = st.keypoints(cur_kps), st.last_frame(last, keep)
+            ss = st.dev(slot_state, np.uint8)
+            sp = st.dev(slot_pos, np.float32) if slot_state is not None else None
+            asg, drec = st.empty(max(nk, 1), np.int32), st.empty(C.sizeof(rec), np.uint8)
+            self.check(lib().lorb_track_motion_dev(self._p, C.byref(fps), A.ptr(T, C.c_float), A.ptr(pi, C.c_float),
+                                                   C.byref(k), ss, sp, C.byref(lf), C.byref(par), C.byref(opt), asg.ptr,
+                                                   drec.ptr), "lorb_track_motion_dev")
+            assign = asg.numpy()[:nk]
+            rec = A.TrackMotionResult.from_buffer_copy(drec.numpy().tobytes())
+        finally:
+            st.close()
+        rv, tv = A.f32(rec.pose[:3]), A.f32(rec.pose[3:])  # Frame::SetPose from the rounded pose
+        lib().lorb_pose_to_Tcw(A.ptr(rv, C.c_float), A.ptr(tv, C.c_float), A.ptr(Tout, C.c_float))
+    else:
+        keep = A.KeepAlive()
+        k, lf = A.make_keypoints(cur_kps, keep), A.make_last_frame(last, keep)
+        ss = keep.keep(A.u8(slot_state)) if slot_state is not None else None
+        sp = keep.keep(A.f32(slot_pos)) if slot_state is not None else None
+        assign = np.empty(max(nk, 1), np.int32)
+        self.check(lib().lorb_track_motion(self._p, C.byref(fps), A.ptr(T, C.c_float), A.ptr(pi, C.c_float), C.byref(k),
+                                           A.ptr(ss, C.c_uint8), A.ptr(sp, C.c_float), C.byref(lf), C.byref(par),
+                                           C.byref(opt), A.ptr(assign, C.c_int32), C.byref(rec),
+                                           A.ptr(Tout, C.c_float)), "lorb_track_motion")
+        assign = assign[:nk].copy()
+    return dict(assign=assign, pass_=rec.pass_, nmatches_first=rec.nmatches_first, nmatches_retry=rec.nmatches_retry,
+                n_residuals=rec.n_residuals, pose=np.array(rec.pose[:], np.float64), summary=rec.summary.as_dict(),
+                Tcw=Tout)
+
+
 def _compute_stereo_matches(self, fp, left, right, pyr_l, pyr_r, device_resident=False):
     """Frame::ComputeStereoMatches -> (u_right, depth).  device_resident=True stages every input in
     device memory first and calls lorb_compute_stereo_matches_dev (the async form)."""
@@ -243,6 +358,9 @@ Context.orb_fast_cells = _orb_fast_cells
 Context.orb_describe = _orb_describe
 Context.compute_stereo_matches = _compute_stereo_matches
 Context.track_local_map = _track_local_map
+Context.search_by_projection_frame_dev = _search_by_projection_frame_dev
+Context.ba_pose_only_dev = _ba_pose_only_dev
+Context.track_motion = _track_motion
 Context.search_by_projection_frame = _search_by_projection_frame
 Context.search_by_projection_local = _search_by_projection_local
 Context.is_in_frustum = _is_in_frustum

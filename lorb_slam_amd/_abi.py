@@ -68,16 +68,44 @@ class StereoKeys(C.Structure):
     _fields_ = [("n", C.c_int32), ("x", C.c_void_p), ("y", C.c_void_p), ("octave", C.c_void_p), ("desc", C.c_void_p)]
 
 
-def pack_pyramid(levels):
-    """list of 2-D uint8 images -> (one contiguous byte buffer, ImagePyramid with data=None)."""
+def pack_pyramid(levels, row_pad=0, fill=0):
+    """list of 2-D uint8 images -> (one contiguous byte buffer, ImagePyramid with data=None).
+    row_pad > 0 lays the levels out like padded cv::Mats: step = cols + row_pad bytes per row, and a
+    gap of 2 * row_pad + 3 bytes after every level; the pad and gap bytes hold `fill`."""
     p = ImagePyramid()
     p.n_levels = len(levels)
     off = 0
+    if row_pad <= 0:
+        for l, im in enumerate(levels):
+            p.offset[l], p.rows[l], p.cols[l], p.step[l] = off, im.shape[0], im.shape[1], im.shape[1]
+            off += im.size
+        buf = np.concatenate([np.ascontiguousarray(im, np.uint8).reshape(-1) for im in levels]) if levels else np.zeros(1, np.uint8)
+        return buf, p
     for l, im in enumerate(levels):
-        p.offset[l], p.rows[l], p.cols[l], p.step[l] = off, im.shape[0], im.shape[1], im.shape[1]
-        off += im.size
-    buf = np.concatenate([np.ascontiguousarray(im, np.uint8).reshape(-1) for im in levels]) if levels else np.zeros(1, np.uint8)
+        p.offset[l], p.rows[l], p.cols[l], p.step[l] = off, im.shape[0], im.shape[1], im.shape[1] + row_pad
+        off += im.shape[0] * (im.shape[1] + row_pad) + 2 * row_pad + 3
+    buf = np.full(max(off, 1), fill, np.uint8)
+    for l, im in enumerate(levels):
+        rows = buf[p.offset[l]:p.offset[l] + p.rows[l] * p.step[l]].reshape(p.rows[l], p.step[l])
+        rows[:, :p.cols[l]] = im
     return buf, p
+
+
+def strided_image(img):
+    """2-D uint8 image -> (array to keep alive, address of pixel (0, 0), rows, cols, step).  A view
+    whose rows are byte-contiguous but further apart than its width (e.g. big[:, :cols], a padded
+    cv::Mat) is passed as it is, step = its row stride; anything else is copied to step = cols."""
+    img = np.asarray(img)
+    if not (img.ndim == 2 and img.dtype == np.uint8 and img.shape[0] > 0 and img.shape[1] > 0 and
+            img.strides[1] == 1 and img.strides[0] >= img.shape[1]):
+        img = u8(img)
+    return img, img.ctypes.data, img.shape[0], img.shape[1], (img.strides[0] if img.ndim == 2 and img.size else 0)
+
+
+def image_bytes(img):
+    """The (rows - 1) * step + cols bytes a strided_image spans, as a flat copy."""
+    rows, cols, step = img.shape[0], img.shape[1], img.strides[0]
+    return np.lib.stride_tricks.as_strided(img, shape=((rows - 1) * step + cols,), strides=(1,)).copy()
 
 
 def make_stereo_keys(k, keep):

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from .runtime import Context, lib
+from .runtime import Context, LorbError, lib
 
 
 def _search_by_projection_frame(self, fp, cur_Tcw, cur_kps, cur_slot_state, last, th):
@@ -213,13 +213,14 @@ def _track_motion(self, fp, cur_Tcw, pose_init, cur_kps, slot_state, slot_pos, l
                 Tcw=Tout)
 
 
-def _compute_stereo_matches(self, fp, left, right, pyr_l, pyr_r, device_resident=False):
+def _compute_stereo_matches(self, fp, left, right, pyr_l, pyr_r, device_resident=False, row_pad=0, fill=255):
     """Frame::ComputeStereoMatches -> (u_right, depth).  device_resident=True stages every input in
-    device memory first and calls lorb_compute_stereo_matches_dev (the async form)."""
+    device memory first and calls lorb_compute_stereo_matches_dev (the async form).  row_pad > 0
+    pads the rows of both pyramids (A.pack_pyramid)."""
     fps = A.make_frame_params(fp)
     n = len(left["x"])
-    bl, pl = A.pack_pyramid(pyr_l)
-    br, pr = A.pack_pyramid(pyr_r)
+    bl, pl = A.pack_pyramid(pyr_l, row_pad, fill)
+    br, pr = A.pack_pyramid(pyr_r, row_pad, fill)
     if not device_resident:
         keep = A.KeepAlive()
         kl, kr = A.make_stereo_keys(left, keep), A.make_stereo_keys(right, keep)
@@ -252,10 +253,10 @@ def _compute_stereo_matches(self, fp, left, right, pyr_l, pyr_r, device_resident
     return out
 
 
-def _orb_describe(self, pyr, x, y, level, pattern, device_resident=False):
+def _orb_describe(self, pyr, x, y, level, pattern, device_resident=False, row_pad=0, fill=255):
     """ORBextractor descriptor stage -> (angle, desc).  device_resident=True stages the inputs in
-    device memory first and calls lorb_orb_describe_dev."""
-    buf, P = A.pack_pyramid(pyr)
+    device memory first and calls lorb_orb_describe_dev.  row_pad > 0 pads the pyramid's rows."""
+    buf, P = A.pack_pyramid(pyr, row_pad, fill)
     x, y, level, pattern = A.f32(x), A.f32(y), A.i32(level), A.i32(pattern).reshape(-1)
     n = len(x)
     if not device_resident:
@@ -278,11 +279,11 @@ def _orb_describe(self, pyr, x, y, level, pattern, device_resident=False):
     return out
 
 
-def _orb_fast_cells(self, pyr, ini_th=20, min_th=7, max_kp=200000, max_cells=4096):
+def _orb_fast_cells(self, pyr, ini_th=20, min_th=7, max_kp=200000, max_cells=4096, row_pad=0, fill=255):
     """FAST stage of ORBextractor::ComputeKeyPointsOctTree (src/ORBextractor.cpp:803-872): per-cell
     FAST with the empty-cell fallback.  Returns x, y, response (level coordinates) and the
-    cell_base / cell_off tables."""
-    buf, P = A.pack_pyramid(pyr)
+    cell_base / cell_off tables.  row_pad > 0 pads the pyramid's rows."""
+    buf, P = A.pack_pyramid(pyr, row_pad, fill)
     P.data = buf.ctypes.data
     x, y, r = np.zeros(max_kp, np.float32), np.zeros(max_kp, np.float32), np.zeros(max_kp, np.float32)
     base = np.zeros(len(pyr) + 1, np.int32)
@@ -297,10 +298,10 @@ def _orb_fast_cells(self, pyr, ini_th=20, min_th=7, max_kp=200000, max_cells=409
                 cell_off=off[:base[-1] + len(pyr)].copy())
 
 
-def _orb_detect(self, pyr, n_desired, scale_factors, ini_th=20, min_th=7, max_kp=100000):
+def _orb_detect(self, pyr, n_desired, scale_factors, ini_th=20, min_th=7, max_kp=100000, row_pad=0, fill=255):
     """ComputeKeyPointsOctTree without orientation (src/ORBextractor.cpp:799-892): FAST cells and
-    DistributeOctTree on the device."""
-    buf, P = A.pack_pyramid(pyr)
+    DistributeOctTree on the device.  row_pad > 0 pads the pyramid's rows."""
+    buf, P = A.pack_pyramid(pyr, row_pad, fill)
     P.data = buf.ctypes.data
     nd, sf = A.i32(n_desired), A.f32(scale_factors)
     x, y, sz, r = (np.zeros(max_kp, np.float32) for _ in range(4))
@@ -316,17 +317,84 @@ def _orb_detect(self, pyr, n_desired, scale_factors, ini_th=20, min_th=7, max_kp
                 level_off=lo)
 
 
-def _orb_extract(self, img, n_desired, scale_factors, pattern, ini_th=20, min_th=7, max_kp=100000):
-    """The whole ORBextractor::operator() (src/ORBextractor.cpp:1087-1151) on the device."""
-    img = A.u8(img)
+ORB_SENTINEL = 0xA5  # byte the device_resident extractor / pyramid pre-fill their device buffers with
+ORB_GUARD = 64        # extra keypoint slots / pyramid bytes allocated past what was asked for
+
+
+def orb_extract_capacity(rows, cols, n_desired, scale_factors):
+    """lorb_orb_extract_capacity -> (max_keypoints, pyramid_bytes)."""
+    nd, sf = A.i32(n_desired), A.f32(scale_factors)
+    cap, pb = C.c_int32(0), C.c_int64(0)
+    rc = lib().lorb_orb_extract_capacity(C.c_int32(rows), C.c_int32(cols), C.c_int32(len(sf)), A.ptr(sf, C.c_float),
+                                         A.ptr(nd, C.c_int32), C.byref(cap), C.byref(pb))
+    if rc != 0:
+        raise LorbError(f"lorb_orb_extract_capacity failed rc={rc}")
+    return cap.value, pb.value
+
+
+def _orb_extract_dev(self, img, step, nd, sf, pat, ini_th, min_th, max_keypoints, pyramid_bytes):
+    """lorb_orb_extract_dev on device copies of the image and pattern.  Every device output holds
+    ORB_GUARD more elements than the call is told about and starts as ORB_SENTINEL bytes; the whole
+    buffers come back under "raw" (and the pyramid buffer as "raw_pyramid")."""
+    rows, cols = img.shape
+    cap, pb = orb_extract_capacity(rows, cols, nd, sf)
+    cap = cap if max_keypoints is None else max_keypoints
+    pb = pb if pyramid_bytes is None else pyramid_bytes
+    st = _Staged(self)
+    try:
+        dimg, dpat = st.dev(A.image_bytes(img), np.uint8), st.dev(pat, np.int32)
+        shapes = dict(x=np.float32, y=np.float32, octave=np.int32, size=np.float32, angle=np.float32,
+                      response=np.float32)
+
+        def guarded(n, dtype):
+            d = self.to_device(np.full(n * np.dtype(dtype).itemsize, ORB_SENTINEL, np.uint8).view(dtype))
+            st.arrs.append(d)
+            return d
+
+        out = {k: guarded(max(cap, 0) + ORB_GUARD, dt) for k, dt in shapes.items()}
+        out["desc"] = guarded((max(cap, 0) + ORB_GUARD) * 32, np.uint8)
+        dpyr = guarded(max(pb, 0) + ORB_GUARD, np.uint8)
+        dlo, dn = guarded(len(sf) + 1 + ORB_GUARD, np.int32), guarded(1 + ORB_GUARD, np.int32)
+        self.check(lib().lorb_orb_extract_dev(
+            self._p, dimg, C.c_int32(rows), C.c_int32(cols), C.c_int32(step), C.c_int32(len(sf)), A.ptr(sf, C.c_float),
+            A.ptr(nd, C.c_int32), C.c_int32(ini_th), C.c_int32(min_th), dpat, C.c_int32(cap), dpyr.ptr, C.c_int64(pb),
+            out["x"].ptr, out["y"].ptr, out["octave"].ptr, out["size"].ptr, out["angle"].ptr, out["response"].ptr,
+            out["desc"].ptr, dlo.ptr, dn.ptr), "lorb_orb_extract_dev")
+        self.sync()  # detection and description run asynchronously: d_n / d_level_off are valid only now
+        n_all, lo_all = dn.numpy(), dlo.numpy()
+        n = int(n_all[0])
+        if n < 0:
+            raise LorbError("lorb_orb_extract_dev: DistributeOctTree exceeded its node capacity (d_n = -1)")
+        raw = {k: v.numpy() for k, v in out.items()}
+        raw["desc"] = raw["desc"].reshape(-1, 32)
+        raw["level_off"], raw["n"] = lo_all, n_all
+        res = {k: raw[k][:n].copy() for k in (*shapes, "desc")}
+        res.update(level_off=lo_all[:len(sf) + 1].copy(), n=n, raw=raw, raw_pyramid=dpyr.numpy(), capacity=cap,
+                   pyramid_bytes=pb)
+        return res
+    finally:
+        st.close()
+
+
+def _orb_extract(self, img, n_desired, scale_factors, pattern, ini_th=20, min_th=7, max_kp=100000,
+                 device_resident=False, max_keypoints=None, pyramid_bytes=None, step=None):
+    """The whole ORBextractor::operator() (src/ORBextractor.cpp:1087-1151) on the device.  img may be a
+    view with a row stride above its width (a padded cv::Mat); `step` overrides the stride passed on.
+    device_resident=True stages image and pattern in device memory, sizes the outputs with
+    lorb_orb_extract_capacity (max_keypoints / pyramid_bytes override what the call is told) and calls
+    lorb_orb_extract_dev; see _orb_extract_dev for the extra keys it returns."""
+    img, addr, rows, cols, stride = A.strided_image(img)
+    step = stride if step is None else step
     nd, sf, pat = A.i32(n_desired), A.f32(scale_factors), A.i32(pattern).reshape(-1)
+    if device_resident:
+        return _orb_extract_dev(self, img, step, nd, sf, pat, ini_th, min_th, max_keypoints, pyramid_bytes)
     x, y, sz, ang, r = (np.zeros(max_kp, np.float32) for _ in range(5))
     o = np.zeros(max_kp, np.int32)
     desc = np.zeros((max_kp, 32), np.uint8)
     lo = np.zeros(len(sf) + 1, np.int32)
     n = C.c_int32(0)
-    self.check(lib().lorb_orb_extract(self._p, A.ptr(img, C.c_uint8), C.c_int32(img.shape[0]), C.c_int32(img.shape[1]),
-                                      C.c_int32(img.shape[1]), C.c_int32(len(sf)), A.ptr(sf, C.c_float),
+    self.check(lib().lorb_orb_extract(self._p, C.cast(addr, A.u8p), C.c_int32(rows), C.c_int32(cols),
+                                      C.c_int32(step), C.c_int32(len(sf)), A.ptr(sf, C.c_float),
                                       A.ptr(nd, C.c_int32), C.c_int32(ini_th), C.c_int32(min_th), A.ptr(pat, C.c_int32),
                                       C.c_int32(max_kp), A.ptr(x, C.c_float), A.ptr(y, C.c_float), A.ptr(o, C.c_int32),
                                       A.ptr(sz, C.c_float), A.ptr(ang, C.c_float), A.ptr(r, C.c_float),
@@ -336,17 +404,37 @@ def _orb_extract(self, img, n_desired, scale_factors, pattern, ini_th=20, min_th
                 response=r[:k].copy(), desc=desc[:k].copy(), level_off=lo)
 
 
-def _orb_pyramid(self, img, scale_factors):
-    """ORBextractor::ComputePyramid on the device -> list of level images."""
-    img = A.u8(img)
+def _orb_pyramid(self, img, scale_factors, device_resident=False, step=None):
+    """ORBextractor::ComputePyramid on the device -> list of level images.  img may be a view with a
+    row stride above its width; `step` overrides the stride passed on.  device_resident=True stages
+    the image in device memory and calls lorb_orb_pyramid_dev on a buffer of exactly the needed bytes
+    (as the call is told) followed by ORB_GUARD bytes of ORB_SENTINEL, which must come back intact."""
+    img, addr, rows, cols, stride = A.strided_image(img)
+    step = stride if step is None else step
     sf = A.f32(scale_factors)
-    total = int(sum(int(np.rint(np.float32(img.shape[0]) * (np.float32(1) / s))) *
-                    int(np.rint(np.float32(img.shape[1]) * (np.float32(1) / s))) for s in sf))
-    out = np.zeros(total + 16, np.uint8)
+    total = int(sum(int(np.rint(np.float32(rows) * (np.float32(1) / s))) *
+                    int(np.rint(np.float32(cols) * (np.float32(1) / s))) for s in sf))
     P = A.ImagePyramid()
-    self.check(lib().lorb_orb_pyramid(self._p, A.ptr(img, C.c_uint8), C.c_int32(img.shape[0]), C.c_int32(img.shape[1]),
-                                      C.c_int32(img.shape[1]), C.c_int32(len(sf)), A.ptr(sf, C.c_float),
-                                      A.ptr(out, C.c_uint8), C.c_int64(len(out)), C.byref(P)), "lorb_orb_pyramid")
+    if device_resident:
+        st = _Staged(self)
+        try:
+            dimg = st.dev(A.image_bytes(img), np.uint8)
+            dout = self.to_device(np.full(total + ORB_GUARD, ORB_SENTINEL, np.uint8))
+            st.arrs.append(dout)
+            self.check(lib().lorb_orb_pyramid_dev(self._p, dimg, C.c_int32(rows), C.c_int32(cols), C.c_int32(step),
+                                                  C.c_int32(len(sf)), A.ptr(sf, C.c_float), dout.ptr, C.c_int64(total),
+                                                  C.byref(P)), "lorb_orb_pyramid_dev")
+            self.sync()
+            out = dout.numpy()
+        finally:
+            st.close()
+        if not (out[total:] == ORB_SENTINEL).all():
+            raise LorbError("lorb_orb_pyramid_dev wrote past the bytes it was given")
+    else:
+        out = np.zeros(total + 16, np.uint8)
+        self.check(lib().lorb_orb_pyramid(self._p, C.cast(addr, A.u8p), C.c_int32(rows), C.c_int32(cols),
+                                          C.c_int32(step), C.c_int32(len(sf)), A.ptr(sf, C.c_float),
+                                          A.ptr(out, C.c_uint8), C.c_int64(len(out)), C.byref(P)), "lorb_orb_pyramid")
     return [out[P.offset[l]:P.offset[l] + P.rows[l] * P.cols[l]].reshape(P.rows[l], P.cols[l]).copy()
             for l in range(len(sf))]
 

@@ -177,3 +177,82 @@ def test_resize_oracle_vs_pyref():
     assert np.abs(out[5] - np.clip(xs, 0, 199)).max() <= 1.0
     pyr = O.orb_pyramid(img, synth.scale_factors())
     assert [p.shape for p in pyr[:3]] == [(97, 131), (81, 109), (67, 91)]
+
+
+SHAPE_GEOMETRIES = [(256, 256, 8), (300, 813, 8), (232, 813, 3), (255, 550, 8), (300, 240, 6)]
+
+
+@pytest.fixture(scope="module", params=SHAPE_GEOMETRIES, ids=lambda g: "%dx%d_L%d" % g)
+def shape_pyramid(request):
+    """The oracle's pyramid of a scene at one of the non-752 x 480 geometries the GPU tests use
+    (tests/test_gpu_orb_shapes.py): 1, 2, 3 and 4 initial quadtree nodes, skipped cells, portrait."""
+    rows, cols, L = request.param
+    img = synth.orb_scene(seed=101, rows=rows, cols=cols, n_shapes=max(20, rows * cols // 3000))
+    return img, O.orb_pyramid(img, synth.scale_factors(n_levels=L))
+
+
+def test_shapes_resize_oracle_vs_pyref(shape_pyramid):
+    """ComputePyramid at the new geometries: level l is pyref's resize of level l - 1."""
+    img, pyr = shape_pyramid
+    assert np.array_equal(pyr[0], img)
+    for l in range(1, len(pyr)):
+        assert np.array_equal(pyr[l], pyref.resize_linear(pyr[l - 1], *pyr[l].shape)), l
+
+
+def test_shapes_cells_oracle_vs_pyref(shape_pyramid):
+    """The cell grid of every level, skipped cells (w = h = 0) included."""
+    _, pyr = shape_pyramid
+    for l, p in enumerate(pyr):
+        c, nc, nr = O.orb_cells(*p.shape)
+        assert len(c) == nc * nr
+        assert [tuple(x) for x in c] == pyref.orb_cells(*p.shape), (l, p.shape)
+    if pyr[0].shape[1] == 813:  # the first width at which the last column starts past maxBorderX - 6
+        c, nc, nr = O.orb_cells(*pyr[0].shape)
+        assert (c[:, 2] == 0).sum() == nr and (c[:, 3] == 0).sum() == nr
+
+
+def test_shapes_distribute_octree_oracle_vs_pyref(shape_pyramid):
+    """DistributeOctTree on every level at N = 0, 1, 37, 5000: 1..4 initial nodes, and N = 0 / 1
+    where the reference divides once before it checks the node count."""
+    _, pyr = shape_pyramid
+    f = O.orb_fast_cells(pyr)
+    n_ini = set()
+    for l, p in enumerate(pyr):
+        b0, b1 = f["cell_off"][f["cell_base"][l] + l], f["cell_off"][f["cell_base"][l + 1] + l]
+        kx, ky, kr = f["x"][b0:b1] - 16, f["y"][b0:b1] - 16, f["response"][b0:b1]
+        n_ini.add(int(np.round(np.float32(p.shape[1] - 32) / np.float32(p.shape[0] - 32))))
+        for N in (0, 1, 37, 5000):
+            a = O.distribute_octree(kx, ky, kr, 16, p.shape[1] - 16, 16, p.shape[0] - 16, N)
+            b = pyref.distribute_octree(kx, ky, kr, 16, p.shape[1] - 16, 16, p.shape[0] - 16, N)
+            assert np.array_equal(a, b), (l, N)
+            assert len(set(a.tolist())) == len(a)
+    assert n_ini <= {1, 2, 3, 4}
+
+
+def test_pack_pyramid_row_pad_and_strided_image():
+    """The padded layouts the GPU stride tests pass on: pack_pyramid(row_pad) keeps every pixel at
+    offset + y * step + x with step = cols + row_pad and fills everything else; strided_image passes
+    a row-padded view on uncopied and copies anything it cannot describe by one row stride."""
+    from lorb_slam_amd import _abi as A
+    rng = np.random.default_rng(0)
+    levels = [rng.integers(1, 200, s, dtype=np.uint8) for s in ((7, 9), (5, 6), (3, 4))]
+    plain, p0 = A.pack_pyramid(levels)
+    assert [p0.step[l] for l in range(3)] == [9, 6, 4] and len(plain) == 63 + 30 + 12
+    buf, p = A.pack_pyramid(levels, row_pad=13, fill=255)
+    used = np.zeros(len(buf), bool)
+    for l, im in enumerate(levels):
+        assert (p.rows[l], p.cols[l], p.step[l]) == (im.shape[0], im.shape[1], im.shape[1] + 13)
+        idx = p.offset[l] + np.arange(im.shape[0])[:, None] * p.step[l] + np.arange(im.shape[1])[None, :]
+        assert np.array_equal(buf[idx], im)
+        assert not used[idx].any()
+        used[idx] = True
+        if l:  # a gap beyond the previous level's last padded row
+            assert p.offset[l] > p.offset[l - 1] + p.rows[l - 1] * p.step[l - 1]
+    assert (buf[~used] == 255).all() and (~used).sum() > used.sum()
+    big = np.full((7, 22), 255, np.uint8)
+    big[:, :9] = levels[0]
+    keep, addr, rows, cols, step = A.strided_image(big[:, :9])
+    assert (rows, cols, step) == (7, 9, 22) and addr == big.ctypes.data
+    assert np.array_equal(A.image_bytes(keep), big.reshape(-1)[:6 * 22 + 9])
+    keep, addr, rows, cols, step = A.strided_image(big[:, :18:2])  # pixels not adjacent: copied
+    assert (rows, cols, step) == (7, 9, 9) and np.array_equal(keep, big[:, :18:2])

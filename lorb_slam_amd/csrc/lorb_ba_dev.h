@@ -1,7 +1,7 @@
 // lorb_ba_dev.h -- device-side types and inline helpers shared by the bundle-adjustment units
-// (lorb_ba.hip, lorb_ba_chol.hip): the structs the kernels take as arguments, the wave / block
-// reductions, the small index helpers, the iteration head that both k_ba_lm_begin and the fused
-// Cholesky run, and the Cholesky unit's host launchers.
+// (lorb_ba.hip, lorb_ba_build.hip, lorb_ba_chol.hip): the structs the kernels take as arguments,
+// the wave / block reductions, the small index helpers, the iteration head that both k_ba_lm_begin
+// and the fused Cholesky run, the Cholesky's LDS sizes and the Cholesky unit's host launchers.
 //
 // Included after the unit's `#pragma clang fp contract(fast)` block (see lorb_ba.hip), so the inline
 // device code here is compiled under the including unit's contraction setting.
@@ -260,6 +260,13 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
 __device__ __forceinline__ double& band(double* A, int bw, int i, int j) {
   return A[(size_t)i * (bw + 1) + (j - i + bw)];
 }
+// slot of block (a, a - dd) of a point group's camera window ("Point-major Schur path", lorb_ba.hip); a window's slots
+__host__ __device__ __forceinline__ int pm_slot(int a, int dd, int bwc) {
+  return a <= bwc ? a * (a + 1) / 2 + dd : (bwc + 1) * (bwc + 2) / 2 + (a - bwc - 1) * (bwc + 1) + dd;
+}
+__host__ __device__ __forceinline__ int pm_nslots(int span, int bwc) {
+  return span <= 0 ? 0 : pm_slot(span - 1, span - 1 < bwc ? span - 1 : bwc, bwc) + 1;
+}
 
 // v_rsq_f64 is accurate to about 2^-22 relative; each Newton step squares the error.  Two steps
 // reach full double precision; LORB_RSQ_STEPS=1 stops at ~1e-14.
@@ -349,6 +356,13 @@ __device__ __forceinline__ WinState lm_head(const BaDev& d, const LMOpt& o, int 
 // (together the 48 x 48 combine), zX (48), two 64 x 17 panel hand-off buffers, a zero word
 __host__ __device__ constexpr int chol2s_words(int n16, int bw) {
   return n16 * (bw + 1) + (n16 + 48) + 2 * 64 * 18 + 48 + 2 * 64 * 17 + 2;
+}
+// LDS words a plan reserves for a band (max_env_w): the largest of the one-sided K6w (band + z + invd +
+// exchange), the two-sided K6t ((n16 + 48) band rows, z, invd, two exchanges, zX) and k_ba_chol_2s
+constexpr int chol_lds_words(int n16, int bw) {
+  const int w1 = n16 * (bw + 1) + 2 * n16 + 64 * 18, w2 = (n16 + 48) * (bw + 2) + 2 * 64 * 18 + 48;
+  const int w3 = chol2s_words(n16, bw);
+  return w1 > w2 ? (w1 > w3 ? w1 : w3) : (w2 > w3 ? w2 : w3);
 }
 
 // ==========================================================================================

@@ -590,3 +590,47 @@ def test_device_built_plan_update_and_result(ctx):
     dp.free()
     for a in arrays.values():
         a.free()
+
+
+def test_device_plan_create_rejects_bad_arguments(ctx):
+    """lorb_ba_plan_create_dev and lorb_ba_plan_create_sharded_dev (over a one-rank communicator)
+    check a lorb_ba_window_dev alike: each bad window is LORB_E_INVALID and leaves *out untouched;
+    the valid window then builds a plan through either entry point."""
+    import ctypes as C
+    from lorb_slam_amd.runtime import Comm, lib, unique_id
+    LORB_E_INVALID = -1  # include/lorb_c.h
+    one = lambda dt, *shape: ctx.to_device(np.zeros(shape, dt))
+    arrays = dict(n_points=ctx.to_device(np.array([1], np.int32)), n_obs=ctx.to_device(np.array([1], np.int32)),
+                  pose_init=one(np.float32, 1, 6), point_init=ctx.to_device(np.array([[0.1, -0.2, 4.0]], np.float32)),
+                  obs_point=one(np.int32, 1), obs_frame=one(np.int32, 1), obs_uv=one(np.float32, 1, 2))
+
+    def window(**bad):  # 1 camera, 0 fixed, max_points = max_obs = 1
+        w = A.BAWindowDev()
+        w.n_poses, w.n_fixed, w.max_points, w.max_obs = 1, 0, 1, 1
+        w.fx, w.fy, w.cx, w.cy = 500.0, 500.0, 320.0, 240.0
+        w.d_n_points, w.d_n_obs = arrays["n_points"].ptr, arrays["n_obs"].ptr
+        for k in ("pose_init", "point_init", "obs_point", "obs_frame", "obs_uv"):
+            setattr(w, "d_" + k, arrays[k].ptr)
+        for k, v in bad.items():
+            setattr(w, k, v)
+        return w
+    bad = [dict(d_n_points=None), dict(d_n_obs=None), dict(n_poses=-1), dict(max_obs=1, d_obs_uv=None),
+           dict(n_poses=1, d_pose_init=None)]
+    comm = Comm.rccl(ctx, 1, 0, unique_id())
+    entries = {"create_dev": lambda w, out: lib().lorb_ba_plan_create_dev(ctx.handle, C.byref(w), C.byref(out)),
+               "create_sharded_dev": lambda w, out: lib().lorb_ba_plan_create_sharded_dev(ctx.handle, comm.handle, C.byref(w),
+                                                                                         C.byref(out))}
+    try:
+        for name, create in entries.items():
+            for b in bad:
+                out = C.c_void_p(0x5a5a)
+                assert create(window(**b), out) == LORB_E_INVALID, (name, b)
+                assert out.value == 0x5a5a, (name, b)
+            out = C.c_void_p()
+            ctx.check(create(window(), out), name)
+            assert out.value
+            ctx.check(lib().lorb_ba_plan_destroy(out), "lorb_ba_plan_destroy")
+    finally:
+        comm.close()
+        for a in arrays.values():
+            a.free()

@@ -571,4 +571,88 @@ size_t TrackLocalMap(lorb_ctx* ctx, FrameT* F, const std::set<PointT*>& localMPs
   return (size_t)nm;
 }
 
+// ---- VisualOdometry::EstimatePoseLocal after UpdateLocalMap(), src/visual_odometry.cpp:149-209
+// The :153-171 loop runs here on the host (a bad held point empties its slot; every other held
+// point gets IncreaseVisible, mnLastFrameSeen = the frame's id and mbTrackInView = false); then
+// the frame, its slots and the local points are gathered once and IsInFrustum, SearchByProjection
+// (F, localMPs, 1), the nMatches <= 20 gate and ProjectPoseOptimization(F) run as ONE call
+// (lorb_track_local): the gate and the residual gathering happen on the device.  Applies what the
+// reference would have written: the tracking fields and IncreaseVisible of every examined point
+// (:186-194), the slots the matcher filled (kept when the gate fails, as the reference keeps them)
+// and, when the gate passes, the optimised pose.  Returns what EstimatePoseLocal returns;
+// *nmatches = nMatches.
+template <class FrameT, class PointT>
+bool EstimatePoseLocal(lorb_ctx* ctx, FrameT* F, const std::set<PointT*>& localMPs, size_t* nmatches = nullptr) {
+  using FT = FrameTraits<FrameT>;
+  using PT = PointTraits<PointT>;
+  const size_t nk = FT::num_keypoints(F);
+  const float none[4] = {0.f, 0.f, 0.f, 0.f};
+  for (size_t j = 0; j < nk; ++j) {  // :153-171
+    PointT* p = FT::map_point(F, j);
+    if (!p) continue;
+    if (PT::is_bad(p)) {
+      FT::set_map_point(F, j, (PointT*)nullptr);
+    } else {
+      PT::increase_visible(p);
+      PT::set_last_frame_seen(p, FT::id(F));
+      PT::set_tracking(p, false, none, 0);
+    }
+  }
+  const lorb_frame_params fp = frame_params(F);
+  float T[16], rt[6];
+  FT::Tcw(F, T);
+  FT::pose_vectors(F, rt, rt + 3);  // mRvec, mTvec (src/bundle_adjust.cpp:163-168)
+  KeypointsSoA k = gather_keypoints(F);
+  std::vector<uint8_t> st = gather_slot_state(F);
+  std::vector<float> slot_pos(3 * nk + 3, 0.f);  // the points the slots hold before the search
+  for (size_t j = 0; j < nk; ++j)
+    if (PointT* p = FT::map_point(F, j)) PT::pos(p, &slot_pos[3 * j]);
+  const size_t n = localMPs.size();
+  std::vector<PointT*> mps;
+  mps.reserve(n);
+  std::vector<float> pos(3 * n + 3), nrm(3 * n + 3), maxd(n + 1), mind(n + 1);
+  std::vector<uint8_t> desc(32 * n + 32), locked(n + 1), bad(n + 1), inframe(n + 1);
+  for (PointT* p : localMPs) {  // std::set iteration order (:176)
+    const size_t i = mps.size();
+    mps.push_back(p);
+    PT::pos(p, &pos[3 * i]);
+    PT::normal(p, &nrm[3 * i]);
+    PT::distances(p, &maxd[i], &mind[i]);
+    PT::descriptor(p, &desc[32 * i]);
+    locked[i] = PT::num_obs(p) > 0 ? 1 : 0;
+    bad[i] = PT::is_bad(p) ? 1 : 0;
+    inframe[i] = PT::last_frame_seen(p) == FT::id(F) ? 1 : 0;
+  }
+  lorb_map_points_dev M;  // host arrays for the host entry point
+  M.n = (int32_t)n; M.pos = pos.data(); M.normal = nrm.data(); M.max_dist = maxd.data(); M.min_dist = mind.data();
+  M.desc = desc.data(); M.locked = locked.data(); M.is_bad = bad.data(); M.in_frame = inframe.data();
+  lorb_keypoints kv = k.view();
+  lorb_track_local_params par;
+  par.viewing_cos_limit = 0.5f; par.th = 1.0f; par.min_matches = 20;
+  par.fy_eff = fp.fx;  // PoseCost quirk: v uses fx, src/bundle_adjust.cpp:51
+  lorb_lm_options opt;
+  lorb_lm_options_default(&opt);
+  std::vector<uint8_t> iv(n + 1);
+  std::vector<float> tr(4 * n + 4);
+  std::vector<int32_t> lev(n + 1), assign(nk + 1);
+  lorb_track_local_result res;
+  check(ctx, lorb_track_local(ctx, &fp, T, rt, &kv, nk ? st.data() : nullptr, nk ? slot_pos.data() : nullptr, &M, &par,
+                              &opt, iv.data(), tr.data(), lev.data(), assign.data(), &res, nullptr),
+        "lorb_track_local");
+  for (size_t i = 0; i < n; ++i) {
+    if (inframe[i] || bad[i]) continue;
+    const float t4[4] = {tr[i], tr[n + i], tr[2 * n + i], tr[3 * n + i]};  // planes x, y, xr, viewcos
+    PT::set_tracking(mps[i], iv[i] != 0, t4, lev[i]);
+    if (iv[i]) PT::increase_visible(mps[i]);
+  }
+  for (size_t j = 0; j < nk; ++j)
+    if (assign[j] >= 0) FT::set_map_point(F, j, mps[assign[j]]);
+  if (nmatches) *nmatches = (size_t)res.nmatches;
+  if (!res.ok) return false;  // :204-205
+  const float R[3] = {(float)res.pose[0], (float)res.pose[1], (float)res.pose[2]};
+  const float Tv[3] = {(float)res.pose[3], (float)res.pose[4], (float)res.pose[5]};
+  FT::set_pose(F, Tv, R);  // Frame::SetPose(T, R), src/bundle_adjust.cpp:198-201
+  return true;
+}
+
 }  // namespace lorb

@@ -520,6 +520,67 @@ int lorb_track_motion(lorb_ctx* ctx, const lorb_frame_params* cur, const float c
                       const lorb_lm_options* opt, int32_t* assign,
                       lorb_track_motion_result* result, float* Tcw_out);
 
+/* ----------------------------------------------------------------------------------------
+ * VisualOdometry::EstimatePoseLocal after UpdateLocalMap (src/visual_odometry.cpp:173-209) as
+ * ONE call: a8 (IsInFrustum + PredictScale, :181-195) for every local map point that is neither
+ * already in the frame nor bad, a5 (SearchByProjection(F, localMPs, th), :196-202) over the
+ * points in view, the nMatches <= 20 gate (:204-207) and, when it passes, a12
+ * (BA::ProjectPoseOptimization, src/bundle_adjust.cpp:158-202) over the slots that hold a map
+ * point afterwards.  The gate and the residual gathering happen on the device: nothing is read
+ * back between the first launch and the last.
+ *
+ * Slots: slot_state / slot_pos describe the slots as stage 1 left them, with the slots whose point
+ * is bad already EMPTY (the :153-171 loop is the caller's).  The frustum test and the search behave
+ * exactly as lorb_track_local_map_dev; with nothing in view nothing matches (:198 skips the search).
+ * assign[j] is LORB_ASSIGN_UNCHANGED or a point index, written whether or not the gate passes (the
+ * reference keeps the matcher's writes when it returns false).
+ *
+ * Residuals, one per slot j holding a map point after the search, in ascending j
+ * (src/bundle_adjust.cpp:173-186), observation (x[j], y[j]):  assign[j] >= 0 -> pts.pos[assign[j]];
+ * assign[j] == UNCHANGED and slot_state[j] != EMPTY -> slot_pos[j].
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_track_local_params {
+  float viewing_cos_limit;  /* 0.5  (src/visual_odometry.cpp:188) */
+  float th;                 /* 1    (:201) */
+  int32_t min_matches;      /* 20: the stage stands when the search finds MORE than this (:204) */
+  float fy_eff;             /* PoseCost's v focal length: fx for the reference's quirk (see a12) */
+} lorb_track_local_params;
+
+typedef struct lorb_track_local_result {
+  int32_t ok;           /* 1: nmatches > min_matches and the pose was optimised; 0: the reference returns false */
+  int32_t nmatches;     /* SearchByProjection's return value (0 when nothing is in view, :198) */
+  int32_t n_in_view;    /* nToMatch (:193): points IsInFrustum accepted */
+  int32_t n_residuals;  /* slots holding a map point after the search (not nmatches plus the kept
+                           slots: two unlocked points can win one slot, the later one stands) */
+  double pose[6];       /* optimised (mRvec | mTvec); ok == 0: pose_init widened to double */
+  lorb_ba_summary summary;  /* ok == 0: zeroed, as a12's empty problem */
+} lorb_track_local_result;
+
+/* Device form.  frame, Tcw (the pose a8 projects with), pose_init (the same pose as mRvec | mTvec,
+ * the a12 start, src/bundle_adjust.cpp:163-168), the structs, par and opt are host values; every
+ * array of d_kps and d_pts, d_slot_state and d_slot_pos are DEVICE pointers.  d_slot_state NULL
+ * means all EMPTY; d_slot_pos (n x 3) may be NULL only then.  Outputs on the device: d_in_view,
+ * d_track (four planes), d_level as lorb_track_local_map_dev; d_assign (n_keypoints codes);
+ * d_result (one record).  Asynchronous on the ctx stream: no host readback and no stream
+ * synchronise while n_points * n_keypoints <= 8M; past that the candidate total is read back once,
+ * as lorb_track_local_map_dev does. */
+int lorb_track_local_dev(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16],
+                         const float pose_init[6], const lorb_keypoints* d_kps,
+                         const uint8_t* d_slot_state, const float* d_slot_pos,
+                         const lorb_map_points_dev* d_pts, const lorb_track_local_params* par,
+                         const lorb_lm_options* opt, uint8_t* d_in_view, float* d_track,
+                         int32_t* d_level, int32_t* d_assign, lorb_track_local_result* d_result);
+/* Host-array form (synchronous): the same with host arrays; one staging of every input, the same
+ * launches, one completion wait for the tracking fields, assign and the record (both forms give
+ * the same bits).  Tcw_out (optional, 16 floats): Frame::SetPose write-back of the rounded pose
+ * (ok == 0: of pose_init). */
+int lorb_track_local(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16],
+                     const float pose_init[6], const lorb_keypoints* kps,
+                     const uint8_t* slot_state, const float* slot_pos,
+                     const lorb_map_points_dev* pts, const lorb_track_local_params* par,
+                     const lorb_lm_options* opt, uint8_t* in_view, float* track, int32_t* level,
+                     int32_t* assign, lorb_track_local_result* result, float* Tcw_out);
+
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.
  * obs_frame[k] >= 0 : optimised pose index (PoseMPCost, src/bundle_adjust.cpp:293-301)

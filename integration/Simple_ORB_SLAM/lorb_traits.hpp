@@ -122,6 +122,8 @@ template <> struct PointTraits<Simple_ORB_SLAM::MapPoint> {
     }
   }
   static void increase_visible(P* p) { p->IncreaseVisible(); }                     // map_point.cpp:167
+  // lorb::EstimatePoseLocal: the held points' mark (src/visual_odometry.cpp:166)
+  static void set_last_frame_seen(P* p, size_t id) { p->mnLastFrameSeen = id; }    // map_point.h:69
   // SURVEY §8f row 4 (lorb::ComputeDescriptors): mDescriptor is private (map_point.h:81), so
   // batching needs `friend struct lorb::PointTraits<MapPoint>;` in map_point.h
   // (-DLORB_REFERENCE_FRIENDS, as above).

@@ -176,6 +176,15 @@ class TrackMotionResult(C.Structure):  # lorb_track_motion_result
                 ("n_residuals", C.c_int32), ("pose", C.c_double * 6), ("summary", BASummary)]
 
 
+class TrackLocalParams(C.Structure):  # lorb_track_local_params
+    _fields_ = [("viewing_cos_limit", C.c_float), ("th", C.c_float), ("min_matches", C.c_int32), ("fy_eff", C.c_float)]
+
+
+class TrackLocalResult(C.Structure):  # lorb_track_local_result
+    _fields_ = [("ok", C.c_int32), ("nmatches", C.c_int32), ("n_in_view", C.c_int32), ("n_residuals", C.c_int32),
+                ("pose", C.c_double * 6), ("summary", BASummary)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

@@ -1297,32 +1297,42 @@ __global__ __launch_bounds__(kPoThreads) void k_ba_pose_only(PoOff aoff, const i
          pose_out + 6 * f, sums + f);
 }
 
-// The tail of the motion-tracking chain (VisualOdometry::EstimatePoseMotion after its matcher
-// calls), one workgroup: which pass counts (pass 1 unless it found <= min_matches, then the retry,
-// which must itself find more), the final assign codes, the slots holding a map point afterwards
-// compacted in ascending slot order by a workgroup scan (src/bundle_adjust.cpp:173-186 walks the
-// slots in order), and the pose-only LM over them.  The first kPoRegRes residuals are listed by slot
-// in LDS and each thread loads its own straight into the registers the LM keeps them in; later ones
-// go through a list in global memory written before the barrier that ends the compaction.
-__global__ __launch_bounds__(kPoThreads) void k_track_tail(lorb::TrackTail a, LMOpt o) {
+// The residual slots of a tracking chain's tail (k_track_tail, k_local_tail): slot j holds a map
+// point after the matching if code[j] >= 0 (the point pt_pos[code[j]]) or, where `keep` is set, if
+// the code is UNCHANGED and slot_state[j] is not EMPTY (the point slot_pos[j]).
+struct TailSlots {
+  int nk;
+  const int* code;
+  bool keep;
+  const uint8_t* slot_state;  // null: all EMPTY
+  const float *slot_pos, *pt_pos, *x, *y;
+  float* list;      // 5 floats per slot: the residuals past the LM's register-resident ones
+  int* copy_to;     // non-null: the codes are also stored here
+  int* assign_out;  // non-null: and here (the mapped result block)
+};
+// The tail body, one kPoThreads workgroup: the slots holding a map point compacted in ascending
+// slot order by a workgroup scan (src/bundle_adjust.cpp:173-186 walks the slots in order), their
+// count stored at *n_res, then the pose-only LM over them (over none unless `solve`: the empty
+// problem, which leaves pose_init widened and a zeroed summary).  The first kPoRegRes residuals are
+// listed by slot in LDS and each thread loads its own straight into the registers the LM keeps them
+// in; later ones go through a list in global memory written before the barrier that ends the
+// compaction.
+__device__ __forceinline__ void tail_run(const TailSlots& s, bool solve, double fx, double fyv, double cx, double cy,
+                                         const float* pose_init, const LMOpt& o, int* __restrict__ n_res,
+                                         double* __restrict__ pose_out, lorb_ba_summary* __restrict__ sum) {
   __shared__ int s_slot[kPoRegRes];
   __shared__ int wsum[kPoW];
   const int t = threadIdx.x;
-  const int nm1 = *a.nm1;
-  const bool retry = nm1 <= a.min_matches;
-  const int nm2 = retry ? *a.nm2 : -1;
-  const int pass = !retry ? 1 : (nm2 > a.min_matches ? 2 : 0);
-  const int* code = retry ? a.assign2 : a.assign;
   int nres = 0;
-  for (int c0 = 0; c0 < a.nk; c0 += kPoThreads) {
+  for (int c0 = 0; c0 < s.nk; c0 += kPoThreads) {
     const int j = c0 + t;
     int cd = LORB_ASSIGN_NULL;
     bool has = false;
-    if (j < a.nk) {
-      cd = code[j];
-      has = cd >= 0 || (!retry && cd == LORB_ASSIGN_UNCHANGED && a.slot_state && a.slot_state[j] != LORB_SLOT_EMPTY);
-      if (retry) a.assign[j] = cd;
-      if (a.assign_out) a.assign_out[j] = cd;
+    if (j < s.nk) {
+      cd = s.code[j];
+      has = cd >= 0 || (s.keep && cd == LORB_ASSIGN_UNCHANGED && s.slot_state && s.slot_state[j] != LORB_SLOT_EMPTY);
+      if (s.copy_to) s.copy_to[j] = cd;
+      if (s.assign_out) s.assign_out[j] = cd;
     }
     int tot;
     const int r = nres + lorb::block_excl_scan<kPoThreads>(has ? 1 : 0, wsum, &tot);
@@ -1330,33 +1340,63 @@ __global__ __launch_bounds__(kPoThreads) void k_track_tail(lorb::TrackTail a, LM
       if (r < kPoRegRes) {
         s_slot[r] = j;
       } else {
-        const float* X = cd >= 0 ? a.last_pos + 3 * (size_t)cd : a.slot_pos + 3 * (size_t)j;
-        float* L = a.list + 5 * (size_t)r;
-        L[0] = X[0]; L[1] = X[1]; L[2] = X[2]; L[3] = a.x[j]; L[4] = a.y[j];
+        const float* X = cd >= 0 ? s.pt_pos + 3 * (size_t)cd : s.slot_pos + 3 * (size_t)j;
+        float* L = s.list + 5 * (size_t)r;
+        L[0] = X[0]; L[1] = X[1]; L[2] = X[2]; L[3] = s.x[j]; L[4] = s.y[j];
       }
     }
     nres += tot;
   }
   __syncthreads();  // s_slot and the list are complete (the scan's barriers order the loop itself)
-  if (t == 0) {
-    a.rec->pass = pass; a.rec->nmatches_first = nm1; a.rec->nmatches_retry = nm2; a.rec->n_residuals = nres;
-  }
-  po_run(pass ? nres : 0, a.fx, a.fy_eff, a.cx, a.cy, a.pose_init, o,
+  if (t == 0) *n_res = nres;
+  po_run(solve ? nres : 0, fx, fyv, cx, cy, pose_init, o,
          [&](int r, double (&X)[3], double (&uv)[2]) {
            if (r < kPoRegRes) {
-             const int j = s_slot[r], cd = code[j];
-             const float* Xp = cd >= 0 ? a.last_pos + 3 * (size_t)cd : a.slot_pos + 3 * (size_t)j;
+             const int j = s_slot[r], cd = s.code[j];
+             const float* Xp = cd >= 0 ? s.pt_pos + 3 * (size_t)cd : s.slot_pos + 3 * (size_t)j;
 #pragma unroll
              for (int k = 0; k < 3; ++k) X[k] = Xp[k];
-             uv[0] = a.x[j]; uv[1] = a.y[j];
+             uv[0] = s.x[j]; uv[1] = s.y[j];
            } else {
-             const float* L = a.list + 5 * (size_t)r;
+             const float* L = s.list + 5 * (size_t)r;
 #pragma unroll
              for (int k = 0; k < 3; ++k) X[k] = L[k];
              uv[0] = L[3]; uv[1] = L[4];
            }
          },
-         a.rec->pose, &a.rec->summary);
+         pose_out, sum);
+}
+
+// The tail of the motion-tracking chain (VisualOdometry::EstimatePoseMotion after its matcher
+// calls), one workgroup: which pass counts (pass 1 unless it found <= min_matches, then the retry,
+// which must itself find more), the final assign codes, and tail_run over the slots holding a map
+// point afterwards (the retry starts from emptied slots: only its own matches count).
+__global__ __launch_bounds__(kPoThreads) void k_track_tail(lorb::TrackTail a, LMOpt o) {
+  const int nm1 = *a.nm1;
+  const bool retry = nm1 <= a.min_matches;
+  const int nm2 = retry ? *a.nm2 : -1;
+  const int pass = !retry ? 1 : (nm2 > a.min_matches ? 2 : 0);
+  if (threadIdx.x == 0) { a.rec->pass = pass; a.rec->nmatches_first = nm1; a.rec->nmatches_retry = nm2; }
+  const TailSlots s = {a.nk, retry ? a.assign2 : a.assign, !retry, a.slot_state, a.slot_pos, a.last_pos, a.x, a.y,
+                       a.list, retry ? a.assign : nullptr, a.assign_out};
+  tail_run(s, pass != 0, a.fx, a.fy_eff, a.cx, a.cy, a.pose_init, o, &a.rec->n_residuals, a.rec->pose, &a.rec->summary);
+}
+
+// The tail of the local-map tracking chain (VisualOdometry::EstimatePoseLocal after its matcher
+// call, src/visual_odometry.cpp:204-209), one workgroup: nToMatch counted from a8's flags (an
+// integer sum), the nMatches <= min_matches gate, and tail_run over the slots holding a map point
+// after a5 (a slot a5 left alone keeps the point stage 1 gave it).
+__global__ __launch_bounds__(kPoThreads) void k_local_tail(lorb::LocalTail a, LMOpt o) {
+  __shared__ int wcnt[kPoW];
+  const int nm = *a.nm;
+  int c = 0;
+  for (int m = threadIdx.x; m < a.np; m += kPoThreads) c += a.in_view[m] != 0;
+  int n_in_view;
+  lorb::block_excl_scan<kPoThreads>(c, wcnt, &n_in_view);
+  const bool ok = nm > a.min_matches;
+  if (threadIdx.x == 0) { a.rec->ok = ok; a.rec->nmatches = nm; a.rec->n_in_view = n_in_view; }
+  const TailSlots s = {a.nk, a.assign, true, a.slot_state, a.slot_pos, a.pt_pos, a.x, a.y, a.list, nullptr, a.assign_out};
+  tail_run(s, ok, a.fx, a.fy_eff, a.cx, a.cy, a.pose_init, o, &a.rec->n_residuals, a.rec->pose, &a.rec->summary);
 }
 
 LMOpt to_dev_opt(const lorb_lm_options* o) {
@@ -1729,6 +1769,11 @@ int group_solve(lorb_ba_group* G, const lorb_lm_options* opt) {
 }  // namespace
 
 namespace lorb {
+int launch_local_tail(lorb_ctx* ctx, const LocalTail& t, const lorb_lm_options* opt) {
+  hipLaunchKernelGGL(k_local_tail, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, to_dev_opt(opt));
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
 int launch_track_tail(lorb_ctx* ctx, const TrackTail& t, const lorb_lm_options* opt) {
   hipLaunchKernelGGL(k_track_tail, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, to_dev_opt(opt));
   LORB_CHECK_LAUNCH(ctx);

@@ -403,6 +403,24 @@ struct TrackTail {
 };
 int launch_track_tail(lorb_ctx* ctx, const TrackTail& t, const lorb_lm_options* opt);
 
+// The tail of the local-map tracking chain (lorb_track_local*, lorb_window.hip): one launch of
+// k_local_tail (lorb_ba.hip) after a8 + a5 -- the in-view count, the nmatches > min_matches gate,
+// residual compaction, pose-only LM, result record.  All pointers are device pointers.
+struct LocalTail {
+  int nk, np;
+  const int* nm;                 // a5's match count
+  const int* assign;             // nk: a5's codes
+  const uint8_t* in_view;        // np: a8's flags
+  const uint8_t* slot_state;     // null: all EMPTY
+  const float *slot_pos, *pt_pos, *x, *y;
+  int min_matches;
+  float fx, fy_eff, cx, cy, pose_init[6];
+  float* list;                   // as TrackTail::list
+  lorb_track_local_result* rec;  // the record (device memory, or the mapped result block)
+  int* assign_out;               // non-null: the codes are also stored here (mapped block)
+};
+int launch_local_tail(lorb_ctx* ctx, const LocalTail& t, const lorb_lm_options* opt);
+
 // Four counters (plain POD: HIP's int4 member proxies are avoided in arithmetic-heavy code).
 struct I4 {
   int v[4];
@@ -452,6 +470,7 @@ enum {
   S_WX = 34,   /* 8 slots: windowed-matcher scratch */
   S_TM = 88,   /* 3 slots: motion-tracking chain (pass 2's codes + both counts, the residual list, the host form's codes) */
   S_TM_ZERO = 91, /* all-EMPTY slot states: zeroed when (re)allocated, never written */
+  S_TLC = 92,  /* 6 slots: local-map tracking chain (match count, residual list; the host form's codes, in-view flags, fields, levels) */
   S_BF_TKEY = 120, /* crossCheck per-train keys: all-ones between calls (the merge resets them) */
   S_IO_IN = 121,   /* InPack device block */
   S_IO_OUT = 122,  /* OutPack device block */

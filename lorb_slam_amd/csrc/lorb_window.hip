@@ -629,7 +629,55 @@ __global__ __launch_bounds__(1024) void k_resolve(int np, int nk, const int* __r
                     nmatches, stride, out);
 }
 
-// (a8) Frame::IsInFrustum + PredictScale, one thread per map point
+// (a8) Frame::IsInFrustum + PredictScale for map point m: false if the point is skipped or out of
+// view, else its tracking fields.  One body for k_frustum (one thread per point) and the local-map
+// chain's candidate kernel (one wavefront per point, every lane the same values): same expression in
+// the same unit, so both store the same bits.
+struct TrackFields {
+  float x, y, xr, cos;
+  int lev;
+};
+__device__ __forceinline__ bool frustum_point(const lorb_frame_params& fp, const float* __restrict__ T,
+                                              const float* __restrict__ Ow, int m, const float* __restrict__ pos,
+                                              const float* __restrict__ nrm, const float* __restrict__ maxd,
+                                              const float* __restrict__ mind, float cos_limit,
+                                              const uint8_t* __restrict__ skip_a, const uint8_t* __restrict__ skip_b,
+                                              TrackFields* f) {
+  // EstimatePoseLocal skips points already matched in the frame and bad points before calling
+  // IsInFrustum (src/visual_odometry.cpp:181-184); they leave tracking with mbTrackInView false
+  if ((skip_a && skip_a[m]) || (skip_b && skip_b[m])) return false;
+  const float P0 = pos[3 * m], P1 = pos[3 * m + 1], P2 = pos[3 * m + 2];
+  float Pc[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double s = (double)T[4 * r] * P0 + (double)T[4 * r + 1] * P1 + (double)T[4 * r + 2] * P2 + (double)T[4 * r + 3] * 1.0f;
+    Pc[r] = (float)s;
+  }
+  if (Pc[2] < 0.0f) return false;
+  const float invz = 1.0f / Pc[2];
+  const float u = fp.fx * Pc[0] * invz + fp.cx;
+  const float v = fp.fy * Pc[1] * invz + fp.cy;
+  if (u < fp.min_x || u > fp.max_x) return false;
+  if (v < fp.min_y || v > fp.max_y) return false;
+  const float maxDistance = 1.2f * maxd[m];
+  const float minDistance = 0.8f * mind[m];
+  const float PO0 = P0 - Ow[0], PO1 = P1 - Ow[1], PO2 = P2 - Ow[2];
+  const float dist = (float)sqrt((double)PO0 * PO0 + (double)PO1 * PO1 + (double)PO2 * PO2);
+  if (dist < minDistance || dist > maxDistance) return false;
+  const float dot = PO0 * nrm[3 * m] + PO1 * nrm[3 * m + 1] + PO2 * nrm[3 * m + 2];
+  const float viewCos = dot / dist;
+  if (viewCos < cos_limit) return false;
+  const float ratio = maxd[m] / dist;
+  int nScale = (int)ceilf((float)log((double)ratio) / fp.log_scale_factor);
+  if (nScale < 0) nScale = 0;
+  else if (nScale >= fp.n_levels) nScale = fp.n_levels - 1;
+  f->x = u;
+  f->xr = u - fp.bf * invz;
+  f->y = v;
+  f->lev = nScale;
+  f->cos = viewCos;
+  return true;
+}
 __global__ __launch_bounds__(256) void k_frustum(lorb_frame_params fp, const float* __restrict__ T,
                                                  const float* __restrict__ Ow, int n,
                                                  const float* __restrict__ pos, const float* __restrict__ nrm,
@@ -642,41 +690,72 @@ __global__ __launch_bounds__(256) void k_frustum(lorb_frame_params fp, const flo
                                                  const uint8_t* __restrict__ skip_b) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= n) return;
-  in_view[m] = 0;
-  // EstimatePoseLocal skips points already matched in the frame and bad points before calling
-  // IsInFrustum (src/visual_odometry.cpp:181-184); they leave tracking with mbTrackInView false
-  if ((skip_a && skip_a[m]) || (skip_b && skip_b[m])) return;
-  const float P0 = pos[3 * m], P1 = pos[3 * m + 1], P2 = pos[3 * m + 2];
-  float Pc[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const double s = (double)T[4 * r] * P0 + (double)T[4 * r + 1] * P1 + (double)T[4 * r + 2] * P2 + (double)T[4 * r + 3] * 1.0f;
-    Pc[r] = (float)s;
+  TrackFields f;
+  const bool iv = frustum_point(fp, T, Ow, m, pos, nrm, maxd, mind, cos_limit, skip_a, skip_b, &f);
+  in_view[m] = iv;
+  if (!iv) return;
+  ox[m] = f.x;
+  oxr[m] = f.xr;
+  oy[m] = f.y;
+  olev[m] = f.lev;
+  ocos[m] = f.cos;
+}
+
+// The local-map chain's candidate kernel (lorb_track_local*): k_cand_local with a8 fused in.  One
+// wavefront per map point evaluates frustum_point for it, lane 0 stores the tracking fields (and a
+// second copy into the host form's mapped result block, `mir`), and the candidates are walked
+// straight from those registers.  WRITE: one strided pass (candidates at m * stride, counts in
+// cand_cnt); !WRITE: the count pass of the count / scan / write sequence, whose write pass is
+// k_cand_local<true> reading the fields stored here.
+struct FrustumIn {  // a8's inputs; the pose and the camera centre travel as kernel arguments
+  float T[16], Ow[3];
+  const float *pos, *nrm, *maxd, *mind;
+  const uint8_t *skip_a, *skip_b;
+  float cos_limit;
+};
+struct FieldsOut {
+  uint8_t* in_view;  // np
+  float* track;      // 4 planes of np: x, y, xr, cos
+  int* level;        // np
+};
+template <bool WRITE, bool GRID = false>
+__global__ __launch_bounds__(64 * kCandWaves) void k_cand_local_fr(KpDev K, WinParams P, int np, FrustumIn F,
+                                                                   FieldsOut o, FieldsOut mir,
+                                                                   const uint4* __restrict__ pdesc,
+                                                                   int* __restrict__ cand_cnt, int2* __restrict__ cand,
+                                                                   int stride) {
+  const int m = blockIdx.x * kCandWaves + (threadIdx.x >> 6);
+  // the query's fields first (GRID: its loads are in flight while the grid is staged)
+  TrackFields f;
+  const bool act = frustum_point(P.fp, F.T, F.Ow, min(m, np - 1), F.pos, F.nrm, F.maxd, F.mind, F.cos_limit, F.skip_a,
+                                 F.skip_b, &f);
+  if constexpr (GRID) {
+    __shared__ KpLds L;
+    K = stage_grid<64 * kCandWaves>(K, P.fp, L);
   }
-  if (Pc[2] < 0.0f) return;
-  const float invz = 1.0f / Pc[2];
-  const float u = fp.fx * Pc[0] * invz + fp.cx;
-  const float v = fp.fy * Pc[1] * invz + fp.cy;
-  if (u < fp.min_x || u > fp.max_x) return;
-  if (v < fp.min_y || v > fp.max_y) return;
-  const float maxDistance = 1.2f * maxd[m];
-  const float minDistance = 0.8f * mind[m];
-  const float PO0 = P0 - Ow[0], PO1 = P1 - Ow[1], PO2 = P2 - Ow[2];
-  const float dist = (float)sqrt((double)PO0 * PO0 + (double)PO1 * PO1 + (double)PO2 * PO2);
-  if (dist < minDistance || dist > maxDistance) return;
-  const float dot = PO0 * nrm[3 * m] + PO1 * nrm[3 * m + 1] + PO2 * nrm[3 * m + 2];
-  const float viewCos = dot / dist;
-  if (viewCos < cos_limit) return;
-  const float ratio = maxd[m] / dist;
-  int nScale = (int)ceilf((float)log((double)ratio) / fp.log_scale_factor);
-  if (nScale < 0) nScale = 0;
-  else if (nScale >= fp.n_levels) nScale = fp.n_levels - 1;
-  in_view[m] = 1;
-  ox[m] = u;
-  oxr[m] = u - fp.bf * invz;
-  oy[m] = v;
-  olev[m] = nScale;
-  ocos[m] = viewCos;
+  if (m >= np) return;
+  const bool lane0 = (threadIdx.x & 63) == 0;
+  if (lane0) {
+    o.in_view[m] = act;
+    if (mir.in_view) mir.in_view[m] = act;
+    if (act) {
+      o.track[m] = f.x; o.track[np + m] = f.y; o.track[2 * np + m] = f.xr; o.track[3 * np + m] = f.cos;
+      o.level[m] = f.lev;
+      if (mir.in_view) {
+        mir.track[m] = f.x; mir.track[np + m] = f.y; mir.track[2 * np + m] = f.xr; mir.track[3 * np + m] = f.cos;
+        mir.level[m] = f.lev;
+      }
+    }
+  }
+  int cnt = 0;
+  if (act && K.n > 0) {  // a frame without keypoints has no grid to walk
+    float r = ((double)f.cos > 0.998) ? 2.5f : 4.0f;  // RadiusByViewingCos
+    if (P.th != 1.0f) r *= P.th;
+    const float rs = r * P.fp.scale_factors[f.lev];
+    cnt = walk_candidates_wave<WRITE>(K, P.fp, f.x, f.y, rs, f.lev - 1, f.lev, f.xr, rs, pdesc + 2 * (size_t)m,
+                                      WRITE ? cand + (size_t)m * stride : nullptr);
+  }
+  if (lane0) cand_cnt[m] = cnt;
 }
 
 // (a20) Frame::UnprojectStereo, one thread per keypoint; Twc = mTcw.inv() given
@@ -736,11 +815,13 @@ struct KpParts {
   int x, y, ang, oc, desc, ur, ss;
   std::vector<uint8_t> zeros;
 };
-void kps_add(lorb::InPack& in, const lorb_keypoints* k, const uint8_t* slot_state, KpParts& p) {
+// pack_empty = false: a null slot_state packs nothing and K->slot_state comes out null (a chain that
+// reads the context's own all-EMPTY buffer)
+void kps_add(lorb::InPack& in, const lorb_keypoints* k, const uint8_t* slot_state, KpParts& p, bool pack_empty = true) {
   const size_t n = (size_t)k->n;
   p.x = in.add_t(k->x, n); p.y = in.add_t(k->y, n); p.ang = in.add_t(k->angle, n);
   p.oc = in.add_t(k->octave, n); p.desc = in.add_t(k->desc, n * 32); p.ur = in.add_t(k->u_right, n);
-  if (!slot_state) { p.zeros.assign(n, 0); slot_state = p.zeros.data(); }
+  if (!slot_state && pack_empty) { p.zeros.assign(n, 0); slot_state = p.zeros.data(); }
   p.ss = in.add_t(slot_state, n);
 }
 // grid = false: the candidate kernel builds the grid in its own LDS (k_cand_*<., true>)
@@ -1289,6 +1370,194 @@ int lorb_track_local_map(lorb_ctx* ctx, const lorb_frame_params* frame, const fl
   if (nk > 0) LORB_HIP(ctx, hipMemcpyAsync(assign, das, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, ctx->stream));
   LORB_HIP(ctx, hipMemcpyAsync(nmatches, dnm, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return LORB_OK;
+}
+
+// VisualOdometry::EstimatePoseLocal after UpdateLocalMap (src/visual_odometry.cpp:173-209) on
+// device-resident data: a8 fused into a5's candidate kernel, the resolver, then the tail kernel
+// (in-view count, gate, residual gathering, pose-only LM).  Launches: candidates + resolver + tail
+// while np * nk <= kCandStrided and nk <= kStageKps; the grid build is added past kStageKps, the
+// count / scan / write sequence replaces the one candidate pass past kCandStrided.  o: the tracking
+// fields on the device; mir (or nulls): the host form's copy in its mapped result block.
+static int track_local_issue(lorb_ctx* ctx, const lorb_frame_params* frame, const float* Tcw, const float* pose_init,
+                             KpDev K, const float* slot_pos, const lorb_map_points_dev* pts,
+                             const lorb_track_local_params* par, const lorb_lm_options* opt, const FieldsOut& o,
+                             const FieldsOut& mir, int* d_assign, lorb_track_local_result* rec, int* assign_out) {
+  const int nk = K.n, np = pts->n;
+  int* nm;
+  float* list;
+  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 0, 1, &nm));
+  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 1, (size_t)std::max(nk, 1) * 5, &list));
+  const uint8_t* given = K.slot_state;
+  FrustumIn F{};
+  float Twc[16];
+  inv4_lu32f(Tcw, Twc);
+  memcpy(F.T, Tcw, sizeof(F.T));
+  F.Ow[0] = Twc[3]; F.Ow[1] = Twc[7]; F.Ow[2] = Twc[11];
+  F.pos = pts->pos; F.nrm = pts->normal; F.maxd = pts->max_dist; F.mind = pts->min_dist;
+  F.skip_a = pts->in_frame; F.skip_b = pts->is_bad;
+  F.cos_limit = par->viewing_cos_limit;
+  WinParams P{};
+  P.fp = *frame;
+  P.th = par->th;
+  const uint4* pdesc = reinterpret_cast<const uint4*>(pts->desc);
+  const unsigned g = lorb::ceil_div(std::max(np, 1), kCandWaves);
+  int *cnt, *off, *res, *claim;
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 0, (size_t)np + 1, &cnt));
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 1, (size_t)np + 1, &off));
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 2, (size_t)np + 1, &res));
+  LORB_TRY(lorb::scratch_t(ctx, S_WX + 3, (size_t)nk + 1, &claim));
+  if (nk == 0) {
+    // no keypoints: the fields are still computed (the count pass walks nothing), nothing matches
+    if (np > 0)
+      hipLaunchKernelGGL(k_cand_local_fr<false>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, F, o, mir, pdesc, cnt,
+                         (int2*)nullptr, 0);
+    LORB_HIP(ctx, hipMemsetAsync(nm, 0, sizeof(int), ctx->stream));
+  } else {
+    if (!given) LORB_TRY(empty_slots(ctx, nk, &K.slot_state));
+    const bool strided = (size_t)np * (size_t)nk <= kCandStrided;  // as lorb_search_by_projection_local
+    const bool lds_grid = strided && nk <= kStageKps;              // the candidate kernel builds the grid itself
+    if (!lds_grid) {
+      int *cell_off, *cell_idx, *kp_cell;
+      LORB_TRY(lorb::scratch_t(ctx, S_KP + 7, kCells + 1, &cell_off));
+      LORB_TRY(lorb::scratch_t(ctx, S_KP + 8, (size_t)nk, &cell_idx));
+      LORB_TRY(lorb::scratch_t(ctx, S_KP + 9, (size_t)nk, &kp_cell));
+      hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(1024), 0, ctx->stream, K.x, K.y, nk, *frame, cell_off, cell_idx,
+                         kp_cell);
+      K.cell_off = cell_off; K.cell_idx = cell_idx;
+    }
+    int2* cand;
+    if (strided) {
+      LORB_TRY(lorb::scratch_t(ctx, S_W9, std::max<size_t>((size_t)np * nk, 1), &cand));
+      if (np > 0) {
+        lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
+        if (lds_grid)
+          hipLaunchKernelGGL((k_cand_local_fr<true, true>), dim3(g), dim3(256), 0, ctx->stream, K, P, np, F, o, mir, pdesc,
+                             cnt, cand, nk);
+        else
+          hipLaunchKernelGGL(k_cand_local_fr<true>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, F, o, mir, pdesc, cnt,
+                             cand, nk);
+      }
+    } else {  // np > 0
+      {
+        lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
+        hipLaunchKernelGGL(k_cand_local_fr<false>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, F, o, mir, pdesc, cnt,
+                           (int2*)nullptr, 0);
+      }
+      hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, np, off);
+      LORB_TRY(alloc_candidates(ctx, off + np, (size_t)np * (size_t)nk, &cand));
+      const float* tx = o.track;
+      hipLaunchKernelGGL(k_cand_local<true>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, o.in_view, pts->is_bad, tx,
+                         tx + np, tx + 2 * np, o.level, tx + 3 * np, pdesc, cnt, off, cand, 0);
+    }
+    size_t rlds = 0;
+    const int rmode = resolve_lds_mode(np, nk, &rlds);
+    hipLaunchKernelGGL(k_resolve<0>, dim3(1), dim3(1024), rlds, ctx->stream, np, nk,
+                       strided ? (const int*)cnt : (const int*)off, cand, pts->locked, (const float*)nullptr,
+                       (const float*)nullptr, res, claim, d_assign, (int*)nullptr, (int*)nullptr, nm, rmode,
+                       strided ? nk : 0);
+  }
+  LORB_CHECK_LAUNCH(ctx);
+  lorb::LocalTail t{};
+  t.nk = nk; t.np = np; t.nm = nm; t.assign = d_assign; t.in_view = o.in_view;
+  t.slot_state = given; t.slot_pos = slot_pos; t.pt_pos = pts->pos; t.x = K.x; t.y = K.y;
+  t.min_matches = par->min_matches;
+  t.fx = frame->fx; t.fy_eff = par->fy_eff; t.cx = frame->cx; t.cy = frame->cy;
+  memcpy(t.pose_init, pose_init, sizeof(t.pose_init));
+  t.list = list; t.rec = rec; t.assign_out = assign_out;
+  return lorb::launch_local_tail(ctx, t, opt);
+}
+
+// argument checks shared by both forms of the local-map chain
+static int track_local_check(lorb_ctx* ctx, const lorb_frame_params* frame, const lorb_keypoints* k,
+                             const uint8_t* slot_state, const float* slot_pos, const lorb_map_points_dev* p,
+                             const lorb_track_local_params* par, const uint8_t* in_view, const float* track,
+                             const int32_t* level, const int32_t* assign) {
+  const int nk = k->n, np = p->n;
+  if (nk < 0 || np < 0) return lorb::set_error(ctx, LORB_E_INVALID, "negative sizes");
+  if (frame->n_levels < 1 || frame->n_levels > LORB_MAX_LEVELS)
+    return lorb::set_error(ctx, LORB_E_INVALID, "n_levels %d out of range", frame->n_levels);
+  if (par->min_matches < 0) return lorb::set_error(ctx, LORB_E_INVALID, "min_matches %d is negative", par->min_matches);
+  if ((np > 0 && (!in_view || !track || !level || !p->pos || !p->normal || !p->max_dist || !p->min_dist || !p->desc ||
+                  !p->locked)) ||
+      (nk > 0 && (!assign || !k->x || !k->y || !k->octave || !k->angle || !k->desc)) || (slot_state && !slot_pos))
+    return lorb::set_error(ctx, LORB_E_INVALID, "null array");
+  return LORB_OK;
+}
+
+int lorb_track_local_dev(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16], const float pose_init[6],
+                         const lorb_keypoints* d_kps, const uint8_t* d_slot_state, const float* d_slot_pos,
+                         const lorb_map_points_dev* d_pts, const lorb_track_local_params* par,
+                         const lorb_lm_options* opt, uint8_t* d_in_view, float* d_track, int32_t* d_level,
+                         int32_t* d_assign, lorb_track_local_result* d_result) {
+  if (!ctx || !frame || !Tcw || !pose_init || !d_kps || !d_pts || !par || !opt || !d_result) return LORB_E_INVALID;
+  LORB_TRY(track_local_check(ctx, frame, d_kps, d_slot_state, d_slot_pos, d_pts, par, d_in_view, d_track, d_level,
+                             d_assign));
+  const FieldsOut o = {d_in_view, d_track, d_level}, none = {nullptr, nullptr, nullptr};
+  return track_local_issue(ctx, frame, Tcw, pose_init, kp_dev(d_kps, d_slot_state), d_slot_pos, d_pts, par, opt, o, none,
+                           d_assign, d_result, nullptr);
+}
+
+int lorb_track_local(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16], const float pose_init[6],
+                     const lorb_keypoints* kps, const uint8_t* slot_state, const float* slot_pos,
+                     const lorb_map_points_dev* pts, const lorb_track_local_params* par, const lorb_lm_options* opt,
+                     uint8_t* in_view, float* track, int32_t* level, int32_t* assign, lorb_track_local_result* result,
+                     float* Tcw_out) {
+  if (!ctx || !frame || !Tcw || !pose_init || !kps || !pts || !par || !opt || !result) return LORB_E_INVALID;
+  LORB_TRY(track_local_check(ctx, frame, kps, slot_state, slot_pos, pts, par, in_view, track, level, assign));
+  const int nk = kps->n, np = pts->n;
+  // every input in one pull; the candidate kernel stores the tracking fields, the tail kernel assign
+  // and the record, into the mapped block
+  lorb::InPack in(ctx);
+  KpParts kp;
+  kps_add(in, kps, slot_state, kp, false);  // all EMPTY: nothing packed, the chain reads its own zeroed buffer
+  const int i_sp = in.add_t(slot_state ? slot_pos : nullptr, (size_t)nk * 3);
+  const int i_pos = in.add_t(pts->pos, (size_t)np * 3), i_nrm = in.add_t(pts->normal, (size_t)np * 3),
+            i_mx = in.add_t(pts->max_dist, np), i_mn = in.add_t(pts->min_dist, np),
+            i_pd = in.add_t(pts->desc, (size_t)np * 32), i_lk = in.add_t(pts->locked, np),
+            i_bad = in.add_t(pts->is_bad, np), i_inf = in.add_t(pts->in_frame, np);
+  LORB_TRY(in.commit());
+  KpDev K;
+  LORB_TRY(kps_finish(ctx, in, kp, nk, S_KP, &K, frame, false));  // track_local_issue builds the grid where it needs one
+  lorb_map_points_dev M{};
+  M.n = np;
+  M.pos = in.dev<float>(i_pos); M.normal = in.dev<float>(i_nrm); M.max_dist = in.dev<float>(i_mx);
+  M.min_dist = in.dev<float>(i_mn); M.desc = in.dev<uint8_t>(i_pd); M.locked = in.dev<uint8_t>(i_lk);
+  M.is_bad = in.dev<uint8_t>(i_bad); M.in_frame = in.dev<uint8_t>(i_inf);
+  int* dassign;
+  FieldsOut o;
+  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 2, (size_t)nk + 1, &dassign));
+  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 3, (size_t)std::max(np, 1), &o.in_view));
+  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 4, (size_t)std::max(np, 1) * 4, &o.track));
+  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 5, (size_t)std::max(np, 1), &o.level));
+  lorb::OutPack out(ctx);
+  const int o_rec = out.add(sizeof(lorb_track_local_result)), o_as = out.add(sizeof(int) * ((size_t)nk + 1)),
+            o_iv = out.add((size_t)np + 1), o_tr = out.add(sizeof(float) * 4 * ((size_t)np + 1)),
+            o_lv = out.add(sizeof(int) * ((size_t)np + 1));
+  LORB_TRY(out.alloc(true));
+  const FieldsOut mir = {out.dev<uint8_t>(o_iv), out.dev<float>(o_tr), out.dev<int>(o_lv)};
+  LORB_TRY(track_local_issue(ctx, frame, Tcw, pose_init, K, in.dev<float>(i_sp), &M, par, opt, o, mir, dassign,
+                             out.dev<lorb_track_local_result>(o_rec), out.dev<int>(o_as)));
+  LORB_TRY(out.fetch());
+  if (np > 0) {
+    // as the device form, only the fields of points in view are defined: the others are left as given
+    const uint8_t* iv = out.host<uint8_t>(o_iv);
+    const float* tr = out.host<float>(o_tr);
+    const int* lv = out.host<int>(o_lv);
+    memcpy(in_view, iv, (size_t)np);
+    for (int m = 0; m < np; ++m)
+      if (iv[m]) {
+        for (int q = 0; q < 4; ++q) track[(size_t)q * np + m] = tr[(size_t)q * np + m];
+        level[m] = lv[m];
+      }
+  }
+  if (nk > 0) memcpy(assign, out.host<int>(o_as), sizeof(int) * nk);
+  *result = *out.host<lorb_track_local_result>(o_rec);
+  if (Tcw_out) {
+    const float R[3] = {(float)result->pose[0], (float)result->pose[1], (float)result->pose[2]};
+    const float T[3] = {(float)result->pose[3], (float)result->pose[4], (float)result->pose[5]};
+    lorb_pose_to_Tcw(R, T, Tcw_out);
+  }
   return LORB_OK;
 }
 

@@ -213,6 +213,74 @@ def _track_motion(self, fp, cur_Tcw, pose_init, cur_kps, slot_state, slot_pos, l
                 Tcw=Tout)
 
 
+def _track_local(self, fp, Tcw, pose_init, kps, slot_state, slot_pos, pts, cos_limit=0.5, th=1.0, min_matches=20,
+                 fy_eff=None, device_resident=True, opt=None):
+    """VisualOdometry::EstimatePoseLocal after UpdateLocalMap as one call (lorb_track_local /
+    lorb_track_local_dev).  device_resident=True stages the inputs in device memory first and calls
+    the _dev form.  Returns assign, in_view, proj_x, proj_y, proj_xr, view_cos, pred_level, ok,
+    nmatches, n_in_view, n_residuals, pose, summary and Tcw."""
+    fps = A.make_frame_params(fp)
+    par = A.TrackLocalParams(cos_limit, th, min_matches, fps.fx if fy_eff is None else fy_eff)
+    opt = opt or A.LMOptions.default()
+    T = A.f32(Tcw).reshape(16)
+    pi = A.f32(pose_init).reshape(6)
+    nk, npt = len(kps["x"]), len(pts["max_dist"])
+    rec = A.TrackLocalResult()
+    Tout = np.zeros((4, 4), np.float32)
+    if slot_state is None:
+        slot_pos = None
+    if device_resident:
+        st = _Staged(self)
+        try:
+            k = st.keypoints(kps)
+            m = A.MapPointsDev(npt, st.dev(pts["pos"], np.float32), st.dev(pts["normal"], np.float32),
+                               st.dev(pts["max_dist"], np.float32), st.dev(pts["min_dist"], np.float32),
+                               st.dev(pts["desc"], np.uint8), st.dev(pts["locked"], np.uint8),
+                               st.dev(pts.get("is_bad"), np.uint8), st.dev(pts.get("in_frame"), np.uint8))
+            ss, sp = st.dev(slot_state, np.uint8), st.dev(slot_pos, np.float32)
+            iv, tr, lv = (st.empty(max(npt, 1), np.uint8), st.empty((4, max(npt, 1)), np.float32),
+                          st.empty(max(npt, 1), np.int32))
+            asg, drec = st.empty(max(nk, 1), np.int32), st.empty(C.sizeof(rec), np.uint8)
+            self.check(lib().lorb_track_local_dev(self._p, C.byref(fps), A.ptr(T, C.c_float), A.ptr(pi, C.c_float),
+                                                  C.byref(k), ss, sp, C.byref(m), C.byref(par), C.byref(opt), iv.ptr,
+                                                  tr.ptr, lv.ptr, asg.ptr, drec.ptr), "lorb_track_local_dev")
+            assign = asg.numpy()[:nk]
+            rec = A.TrackLocalResult.from_buffer_copy(drec.numpy().tobytes())
+            in_view, level = iv.numpy()[:npt], lv.numpy()[:npt]
+            trk = tr.numpy().reshape(4, -1)[:, :npt] if npt else np.zeros((4, 0), np.float32)
+        finally:
+            st.close()
+        rv, tv = A.f32(rec.pose[:3]), A.f32(rec.pose[3:])  # Frame::SetPose from the rounded pose
+        lib().lorb_pose_to_Tcw(A.ptr(rv, C.c_float), A.ptr(tv, C.c_float), A.ptr(Tout, C.c_float))
+    else:
+        keep = A.KeepAlive()
+
+        def host(a, dtype):
+            return None if a is None else keep.keep(np.ascontiguousarray(a, dtype)).ctypes.data
+
+        k = A.make_keypoints(kps, keep)
+        m = A.MapPointsDev(npt, host(pts["pos"], np.float32), host(pts["normal"], np.float32),
+                           host(pts["max_dist"], np.float32), host(pts["min_dist"], np.float32),
+                           host(pts["desc"], np.uint8), host(pts["locked"], np.uint8),
+                           host(pts.get("is_bad"), np.uint8), host(pts.get("in_frame"), np.uint8))
+        ss = keep.keep(A.u8(slot_state)) if slot_state is not None else None
+        sp = keep.keep(A.f32(slot_pos)) if slot_pos is not None else None
+        in_view, trk, level = (np.zeros(max(npt, 1), np.uint8), np.zeros((4, max(npt, 1)), np.float32),
+                               np.zeros(max(npt, 1), np.int32))
+        assign = np.empty(max(nk, 1), np.int32)
+        self.check(lib().lorb_track_local(self._p, C.byref(fps), A.ptr(T, C.c_float), A.ptr(pi, C.c_float), C.byref(k),
+                                          A.ptr(ss, C.c_uint8), A.ptr(sp, C.c_float), C.byref(m), C.byref(par),
+                                          C.byref(opt), A.ptr(in_view, C.c_uint8), A.ptr(trk, C.c_float),
+                                          A.ptr(level, C.c_int32), A.ptr(assign, C.c_int32), C.byref(rec),
+                                          A.ptr(Tout, C.c_float)), "lorb_track_local")
+        assign, in_view, level = assign[:nk].copy(), in_view[:npt], level[:npt]
+        trk = trk[:, :npt] if npt else np.zeros((4, 0), np.float32)
+    return dict(assign=assign, in_view=in_view, proj_x=trk[0], proj_y=trk[1], proj_xr=trk[2], view_cos=trk[3],
+                pred_level=level, ok=rec.ok, nmatches=rec.nmatches, n_in_view=rec.n_in_view,
+                n_residuals=rec.n_residuals, pose=np.array(rec.pose[:], np.float64), summary=rec.summary.as_dict(),
+                Tcw=Tout)
+
+
 def _compute_stereo_matches(self, fp, left, right, pyr_l, pyr_r, device_resident=False, row_pad=0, fill=255):
     """Frame::ComputeStereoMatches -> (u_right, depth).  device_resident=True stages every input in
     device memory first and calls lorb_compute_stereo_matches_dev (the async form).  row_pad > 0
@@ -449,6 +517,7 @@ Context.track_local_map = _track_local_map
 Context.search_by_projection_frame_dev = _search_by_projection_frame_dev
 Context.ba_pose_only_dev = _ba_pose_only_dev
 Context.track_motion = _track_motion
+Context.track_local = _track_local
 Context.search_by_projection_frame = _search_by_projection_frame
 Context.search_by_projection_local = _search_by_projection_local
 Context.is_in_frustum = _is_in_frustum

@@ -487,6 +487,69 @@ void ComputeStereoMatches(lorb_ctx* ctx, FrameT* F) {
   FT::set_stereo(F, uR.data(), depth.data(), nl);
 }
 
+// ---- Frame::Frame(imgLeft, imgRight, camera), src/frame.cpp:17-63 -------------------------
+// RAII over a lorb_frame_builder: everything that depends only on the geometry (image size,
+// levels, features per level, thresholds, pattern) is built once; keep one per camera.
+class FrameBuilder {
+ public:
+  FrameBuilder(lorb_ctx* ctx, const lorb_frame_config& cfg) : ctx_(ctx), n_levels_(cfg.frame.n_levels) {
+    check(ctx, lorb_frame_builder_create(ctx, &cfg, &b_), "lorb_frame_builder_create");
+    check(ctx, lorb_frame_builder_capacity(b_, &capacity_, &pyramid_bytes_), "lorb_frame_builder_capacity");
+  }
+  ~FrameBuilder() { if (b_) lorb_frame_builder_destroy(b_); }
+  FrameBuilder(const FrameBuilder&) = delete;
+  FrameBuilder& operator=(const FrameBuilder&) = delete;
+  lorb_frame_builder* handle() const { return b_; }
+  lorb_ctx* ctx() const { return ctx_; }
+  int32_t capacity() const { return capacity_; }       // keypoints per image
+  int64_t pyramid_bytes() const { return pyramid_bytes_; }
+  int n_levels() const { return n_levels_; }
+
+ private:
+  lorb_ctx* ctx_;
+  lorb_frame_builder* b_ = nullptr;
+  int32_t capacity_ = 0;
+  int64_t pyramid_bytes_ = 0;
+  int n_levels_;
+};
+
+// The extraction and stereo part of the constructor (:42-51) for a frame-like object: fills mvKeys /
+// mvKeysRight (pt, octave, size, angle, response), mvKeysUn (= mvKeys, :361), mDescriptors /
+// mDescriptorsRight, mvuRight, mvDepth and mnMapPoints (with empty map-point slots, :46, :53-54)
+// through FrameTraits.  Frame::AssignFeaturesToGrid (:57) stays host code, done by the caller.
+template <class FrameT>
+void BuildFrame(FrameBuilder& B, FrameT* F, const uint8_t* left, int left_step, const uint8_t* right,
+                int right_step) {
+  using FT = FrameTraits<FrameT>;
+  struct Side {
+    std::vector<float> x, y, size, angle, response;
+    std::vector<int32_t> octave, level_off;
+    std::vector<uint8_t> desc;
+    explicit Side(size_t n)
+        : x(n), y(n), size(n), angle(n), response(n), octave(n), level_off(LORB_MAX_LEVELS + 1), desc(32 * n) {}
+    lorb_frame_side view() {
+      return lorb_frame_side{x.data(), y.data(), octave.data(), size.data(), angle.data(), response.data(),
+                             desc.data(), level_off.data(), nullptr};
+    }
+  };
+  const size_t cap = (size_t)B.capacity() + 1;
+  Side L(cap), R(cap);
+  std::vector<float> uR(cap, -1.0f), depth(cap, -1.0f);
+  int32_t counts[2] = {0, 0};
+  const lorb_frame_out out{L.view(), R.view(), uR.data(), depth.data(), counts};
+  check(B.ctx(), lorb_frame_build(B.handle(), left, left_step, right, right_step, B.capacity(), &out),
+        "lorb_frame_build");
+  const size_t nl = (size_t)counts[0], nr = (size_t)counts[1];
+  FT::set_keypoints(F, 0, nl, L.x.data(), L.y.data(), L.octave.data(), L.size.data(), L.angle.data(),
+                    L.response.data());                                     // mvKeys and mvKeysUn
+  FT::set_keypoints(F, 1, nr, R.x.data(), R.y.data(), R.octave.data(), R.size.data(), R.angle.data(),
+                    R.response.data());                                     // mvKeysRight
+  FT::set_descriptors(F, 0, nl, L.desc.data());                             // mDescriptors
+  FT::set_descriptors(F, 1, nr, R.desc.data());                             // mDescriptorsRight
+  FT::set_stereo(F, uR.data(), depth.data(), nl);                           // mvuRight / mvDepth
+  FT::set_num_map_points(F, nl);                                            // mnMapPoints, empty slots
+}
+
 // ---- MapPoint::ComputeDescriptor, src/map_point.cpp:69-129, batched (§8f row 4) -----------
 // Candidates: the observations in std::map<Frame*, size_t> order, bad frames skipped (:74-81).
 // A point with no candidate keeps its descriptor (the reference indexes an empty vector there).

@@ -384,6 +384,74 @@ int lorb_orb_extract_capacity(int32_t rows, int32_t cols, int32_t n_levels, cons
                               const int32_t* n_desired, int32_t* max_keypoints, int64_t* pyramid_bytes);
 
 /* ----------------------------------------------------------------------------------------
+ * The stereo Frame constructor, Frame::Frame(imgLeft, imgRight, camera) (src/frame.cpp:17-63), as
+ * one call: ORBextractor::operator() on both images (:42-45; the reference runs them in two
+ * threads), UndistortKeyPoints (:358-362, a copy: mvKeysUn = mvKeys, :361) and
+ * ComputeStereoMatches (:125-333).  The result is the frame that lorb_track_motion_dev,
+ * lorb_unproject_stereo_dev and lorb_track_local_dev read: the left side's x, y, octave, angle,
+ * u_right and desc ARE the lorb_keypoints view (of mvKeysUn, which is mvKeys) as they stand.
+ *
+ * A builder holds everything that depends only on the geometry, built once by _create: the
+ * pyramid layout, the resize tap tables of every level, the FAST cell table, the quadtree plan,
+ * the blur tiles, the pattern, and all scratch for two images and the stereo stage (row table, row
+ * lists, SAD array).  The memory is the builder's own (not the ctx's scratch), so a builder does
+ * not disturb interleaved calls of the other entry points nor a second builder on the same ctx.
+ *
+ * Count protocol: counts[2] = {n_left, n_right} stays in device memory.  Every kernel after the
+ * quadtree is launched over the capacity (lorb_frame_builder_capacity) and reads its count there,
+ * bounded by the capacity; nothing is written past n_left / n_right entries of any array.  A side
+ * whose quadtree overflowed its node capacity has count -1; the stereo stage then treats both
+ * counts as 0 and writes nothing.  u_right / depth hold -1 where a left keypoint has no depth.
+ *
+ * Left to the host: Frame::AssignFeaturesToGrid (:87-103) is NOT an output -- every consumer
+ * (the grid of lorb_search_by_projection_*, lorb_track_*) builds its grid from x, y -- and the
+ * map-point slots (mvpMapPoints, mnMapPoints = 0).
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_frame_config {
+  int32_t rows, cols;                    /* both images */
+  lorb_frame_params frame;               /* n_levels, scale_factors, bf, b are read */
+  int32_t n_desired[LORB_MAX_LEVELS];    /* ORBextractor::mnFeaturesPerLevel */
+  int32_t ini_th, min_th;                /* iniThFAST, minThFAST */
+  const int32_t* pattern;                /* host, 1024 ints: bit_pattern_31_ (copied by _create) */
+} lorb_frame_config;
+/* one camera's outputs: the content and order of lorb_orb_extract_dev's */
+typedef struct lorb_frame_side {
+  float* x;                /* kp.pt.x (level 0 coordinates) */
+  float* y;
+  int32_t* octave;
+  float* size;
+  float* angle;            /* degrees */
+  float* response;
+  uint8_t* desc;           /* capacity x 32 */
+  int32_t* level_off;      /* n_levels + 1 */
+  uint8_t* pyramid;        /* pyramid_bytes (ORBextractor::mvImagePyramid); ignored by lorb_frame_build */
+} lorb_frame_side;
+typedef struct lorb_frame_out {   /* a host struct of device (_dev) or host pointers */
+  lorb_frame_side left, right;    /* mvKeys + mDescriptors, mvKeysRight + mDescriptorsRight */
+  float* u_right;                 /* mvuRight, left only */
+  float* depth;                   /* mvDepth, left only */
+  int32_t* counts;                /* {n_left, n_right} */
+} lorb_frame_out;
+typedef struct lorb_frame_builder lorb_frame_builder;
+/* Fails as lorb_orb_extract does for the geometries it rejects (LORB_E_UNSUPPORTED: 0 or 5 initial
+ * quadtree nodes; LORB_E_INVALID: a level with no 30-pixel cell, a cell beyond the LDS tile) and
+ * with LORB_E_INVALID for rows > 4096 (the stereo row table) or a null pattern. */
+int lorb_frame_builder_create(lorb_ctx* ctx, const lorb_frame_config* cfg, lorb_frame_builder** out);
+/* per image: the bounds of lorb_orb_extract_capacity */
+int lorb_frame_builder_capacity(const lorb_frame_builder* builder, int32_t* max_keypoints, int64_t* pyramid_bytes);
+/* Both images and every array of d_out are device memory (keypoint arrays: max_keypoints entries;
+ * pyramids: pyramid_bytes; counts: 2 ints).  Asynchronous on the ctx stream: 16 kernel launches
+ * (n_levels = 8), no stream synchronise, no device-to-host read and no host-to-device copy. */
+int lorb_frame_build_dev(lorb_frame_builder* builder, const uint8_t* d_left, int32_t left_step,
+                         const uint8_t* d_right, int32_t right_step, const lorb_frame_out* d_out);
+/* Host arrays (each keypoint array holds max_keypoints entries): one staging copy of the two images,
+ * the same launches, one fetch and one wait.  LORB_E_UNSUPPORTED when a quadtree overflowed
+ * (counts still show which), LORB_E_INVALID when a count exceeds max_keypoints. */
+int lorb_frame_build(lorb_frame_builder* builder, const uint8_t* left, int32_t left_step, const uint8_t* right,
+                     int32_t right_step, int32_t max_keypoints, const lorb_frame_out* out);
+int lorb_frame_builder_destroy(lorb_frame_builder* builder);
+
+/* ----------------------------------------------------------------------------------------
  * Bundle adjustment: Ceres-default Levenberg-Marquardt + DENSE_SCHUR restated
  * (src/bundle_adjust.cpp:158-202 and :207-330; solver defaults in SURVEY Appendix B).
  * -------------------------------------------------------------------------------------- */

@@ -51,7 +51,31 @@ template <> struct FrameTraits<Simple_ORB_SLAM::Frame> {
     const cv::Mat& m = (side ? f->mpORBextractorRight : f->mpORBextractorLeft)->mvImagePyramid[l];  // ORBextractor.h:85
     *d = m.ptr<uint8_t>(); *rows = m.rows; *cols = m.cols; *step = (int)m.step;
   }
+  // lorb::BuildFrame (the extraction + stereo part of Frame::Frame, frame.cpp:42-51): the
+  // descriptor matrices are private (frame.h:132), hence inside this block as well.
+  static void set_descriptors(F* f, int side, size_t n, const uint8_t* d) {       // mDescriptors / mDescriptorsRight
+    cv::Mat m((int)n, 32, CV_8U);
+    for (size_t i = 0; i < n; ++i) std::memcpy(m.ptr<uint8_t>((int)i), d + 32 * i, 32);
+    (side ? f->mDescriptorsRight : f->mDescriptors) = m;
+  }
 #endif  // LORB_REFERENCE_FRIENDS
+  // lorb::BuildFrame: mvKeys and mvKeysUn (UndistortKeyPoints is a copy, frame.cpp:361), or mvKeysRight
+  static void set_keypoints(F* f, int side, size_t n, const float* x, const float* y, const int* octave,
+                            const float* size, const float* angle, const float* response) {
+    std::vector<cv::KeyPoint> k(n);
+    for (size_t i = 0; i < n; ++i) {
+      k[i].pt.x = x[i]; k[i].pt.y = y[i]; k[i].octave = octave[i]; k[i].size = size[i]; k[i].angle = angle[i];
+      k[i].response = response[i];
+    }
+    if (side) { f->mvKeysRight = k; return; }
+    f->mvKeys = k;
+    f->mvKeysUn = k;
+  }
+  static void set_num_map_points(F* f, size_t n) {                                 // frame.cpp:46, 53-54
+    f->mnMapPoints = n;
+    f->mvpMapPoints.assign(n, static_cast<point_type*>(nullptr));
+    f->mvbOutlier.assign(n, false);
+  }
   static void set_stereo(F* f, const float* uR, const float* depth, size_t n) {   // mvuRight / mvDepth (frame.h:90-91)
     f->mvuRight.assign(uR, uR + n);
     f->mvDepth.assign(depth, depth + n);

@@ -185,6 +185,23 @@ class TrackLocalResult(C.Structure):  # lorb_track_local_result
                 ("pose", C.c_double * 6), ("summary", BASummary)]
 
 
+class FrameConfig(C.Structure):  # lorb_frame_config
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("frame", FrameParams),
+                ("n_desired", C.c_int32 * LORB_MAX_LEVELS), ("ini_th", C.c_int32), ("min_th", C.c_int32),
+                ("pattern", i32p)]
+
+
+class FrameSide(C.Structure):  # lorb_frame_side (device or host addresses)
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("octave", C.c_void_p), ("size", C.c_void_p),
+                ("angle", C.c_void_p), ("response", C.c_void_p), ("desc", C.c_void_p), ("level_off", C.c_void_p),
+                ("pyramid", C.c_void_p)]
+
+
+class FrameOut(C.Structure):  # lorb_frame_out
+    _fields_ = [("left", FrameSide), ("right", FrameSide), ("u_right", C.c_void_p), ("depth", C.c_void_p),
+                ("counts", C.c_void_p)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

@@ -421,6 +421,65 @@ struct LocalTail {
 };
 int launch_local_tail(lorb_ctx* ctx, const LocalTail& t, const lorb_lm_options* opt);
 
+// Device memory owned by one object (not a ctx scratch slot): add() every array, commit() allocates
+// one block and sets the pointers (256-byte aligned, 16 spare bytes each as scratch_t gives).
+struct Arena {
+  struct Item { void** p; size_t off; };
+  std::vector<Item> items;
+  size_t total = 0;
+  void* base = nullptr;
+  template <typename T>
+  void add(T** p, size_t count) {
+    items.push_back({reinterpret_cast<void**>(p), total});
+    total += (count * sizeof(T) + 16 + 255) & ~size_t(255);
+  }
+  hipError_t commit() {
+    const hipError_t e = hipMalloc(&base, total ? total : 256);
+    if (e != hipSuccess) { base = nullptr; return e; }
+    for (const Item& it : items) *it.p = static_cast<unsigned char*>(base) + it.off;
+    return hipSuccess;
+  }
+  void release() {
+    if (base) (void)hipFree(base);
+    base = nullptr;
+  }
+};
+
+// The extractor over a stereo pair (lorb_orb.hip; used by lorb_frame.hip's builder): the plan and
+// scratch of one geometry, and its 13 launches per frame on the ctx stream -- no host copy, no wait.
+// Per image the outputs of lorb_orb_extract_dev; d_counts[2] receives {n_left, n_right} (-1: that
+// image's quadtree overflowed its node capacity).
+struct OrbPair;
+struct OrbPairSide {
+  uint8_t* pyramid;
+  float *x, *y;
+  int* octave;
+  float *size, *angle, *response;
+  uint8_t* desc;
+  int* level_off;
+};
+int orb_pair_create(lorb_ctx* ctx, int rows, int cols, int n_levels, const float* sf, const int32_t* n_desired,
+                    int ini_th, int min_th, const int32_t* pattern, OrbPair** out);
+void orb_pair_destroy(OrbPair* B);
+void orb_pair_info(const OrbPair* B, int* capacity, int64_t* pyr_bytes, lorb_image_pyramid* layout);
+int orb_pair_enqueue(lorb_ctx* ctx, OrbPair* B, const uint8_t* d_img0, int step0, const uint8_t* d_img1, int step1,
+                     const OrbPairSide& o0, const OrbPairSide& o1, int* d_counts);
+
+// Frame::ComputeStereoMatches with the keypoint counts in device memory (lorb_stereo.hip): d_counts =
+// {n_left, n_right}, each bounded by its side's capacity; a negative count makes both 0.  The three
+// scratch arrays are the caller's: row_off (rows + 1), row_list (stereo_row_list_len), sad (left cap).
+struct StereoSideDev {
+  const float *x, *y;
+  const int* octave;
+  const uint8_t* desc;
+  const uint8_t* pyramid;
+  int capacity;
+};
+size_t stereo_row_list_len(const lorb_frame_params* fp, int right_capacity);
+int enqueue_stereo_counts(lorb_ctx* ctx, const lorb_frame_params* fp, const lorb_image_pyramid* layout,
+                          const StereoSideDev& L, const StereoSideDev& R, const int* d_counts, int* row_off,
+                          int* row_list, int* sad, float* d_ur, float* d_dp);
+
 // Four counters (plain POD: HIP's int4 member proxies are avoided in arithmetic-heavy code).
 struct I4 {
   int v[4];

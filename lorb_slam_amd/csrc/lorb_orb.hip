@@ -42,16 +42,17 @@ __device__ __forceinline__ int reflect101(int p, int n) {
   return p;
 }
 
-__global__ __launch_bounds__(256) void k_orb_blur(OrbPyr P) {
-  __shared__ int in[kTileH + 6][kTileW + 6 + 1];
-  __shared__ int rowp[kTileH + 6][kTileW + 1];
-  const int b = blockIdx.x, t = threadIdx.x;
+// one 64 x 16 output tile (tile b of the pyramid's tile table) of raw -> blurred
+__device__ __forceinline__ void blur_tile(const OrbPyr& P, const uint8_t* __restrict__ data, uint8_t* __restrict__ blur,
+                                          int b, int (&in)[kTileH + 6][kTileW + 6 + 1],
+                                          int (&rowp)[kTileH + 6][kTileW + 1]) {
+  const int t = threadIdx.x;
   int l = 0;
   while (l + 1 < P.n_levels && b >= P.tile_off[l + 1]) ++l;
   const int tb = b - P.tile_off[l];
   const int x0 = (tb % P.tiles_x[l]) * kTileW, y0 = (tb / P.tiles_x[l]) * kTileH;
   const int rows = P.rows[l], cols = P.cols[l], step = P.step[l];
-  const uint8_t* src = P.data + P.offset[l];
+  const uint8_t* src = data + P.offset[l];
   for (int e = t; e < (kTileH + 6) * (kTileW + 6); e += 256) {
     const int r = e / (kTileW + 6), c = e - r * (kTileW + 6);
     const int yy = reflect101(y0 + r - 3, rows), xx = reflect101(x0 + c - 3, cols);
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void k_orb_blur(OrbPyr P) {
     rowp[r][c] = s;
   }
   __syncthreads();
-  uint8_t* dst = P.blur + P.offset[l];
+  uint8_t* dst = blur + P.offset[l];
   for (int e = t; e < kTileH * kTileW; e += 256) {  // column pass
     const int r = e / kTileW, c = e - r * kTileW;
     const int y = y0 + r, x = x0 + c;
@@ -77,6 +78,26 @@ __global__ __launch_bounds__(256) void k_orb_blur(OrbPyr P) {
     const int v = (s + (1 << 15)) >> 16;
     dst[(int64_t)y * step + x] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
   }
+}
+
+__global__ __launch_bounds__(256) void k_orb_blur(OrbPyr P) {
+  __shared__ int in[kTileH + 6][kTileW + 6 + 1];
+  __shared__ int rowp[kTileH + 6][kTileW + 1];
+  blur_tile(P, P.data, P.blur, blockIdx.x, in, rowp);
+}
+
+// The second image of a stereo pair (same geometry, its own raw / blurred pyramids): the kernels
+// suffixed 2 run both images in one launch, image = blockIdx.y (blockIdx.z for the resize).
+struct OrbSide2 {
+  const uint8_t* data;
+  uint8_t* blur;
+};
+
+__global__ __launch_bounds__(256) void k_orb_blur2(OrbPyr P, OrbSide2 right) {
+  __shared__ int in[kTileH + 6][kTileW + 6 + 1];
+  __shared__ int rowp[kTileH + 6][kTileW + 1];
+  const bool r = blockIdx.y != 0;
+  blur_tile(P, r ? right.data : P.data, r ? right.blur : P.blur, blockIdx.x, in, rowp);
 }
 
 // cv::fastAtan2 (OpenCV 3.1), degrees
@@ -109,16 +130,12 @@ __device__ __forceinline__ int wave_isum(int v) {
 
 constexpr int kDescWaves = 4;
 
-__global__ __launch_bounds__(64 * kDescWaves) void k_orb_desc(OrbPyr P, int n, const int* __restrict__ d_n,
-                                                              const float* __restrict__ kx,
-                                                              const float* __restrict__ ky,
-                                                              const int* __restrict__ klev,
-                                                              const int* __restrict__ pattern,
-                                                              float* __restrict__ angle_out,
-                                                              uint8_t* __restrict__ desc_out) {
-  __shared__ int s_pat[1024];
-  for (int e = threadIdx.x; e < 1024; e += 64 * kDescWaves) s_pat[e] = pattern[e];
-  __syncthreads();
+// one wavefront: keypoint i of (raw, blurred); s_pat holds the staged pattern
+__device__ __forceinline__ void desc_key(const OrbPyr& P, const uint8_t* __restrict__ raw,
+                                         const uint8_t* __restrict__ blurred, int n, const int* __restrict__ d_n,
+                                         const float* __restrict__ kx, const float* __restrict__ ky,
+                                         const int* __restrict__ klev, const int* s_pat,
+                                         float* __restrict__ angle_out, uint8_t* __restrict__ desc_out) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * kDescWaves + (threadIdx.x >> 6);
   if (d_n) n = min(n, *d_n);  // device-side count (extraction pipeline); < 0 = failed upstream
@@ -130,7 +147,7 @@ __global__ __launch_bounds__(64 * kDescWaves) void k_orb_desc(OrbPyr P, int n, c
   // IC_Angle: lane u + 15 (u in [-15, 15]) sums column u over the disc, rows split in two halves
   int m10 = 0, m01 = 0;
   {
-    const uint8_t* center = P.data + P.offset[l] + (int64_t)cy * step + cx;
+    const uint8_t* center = raw + P.offset[l] + (int64_t)cy * step + cx;
     const int u = (lane & 31) - kHalfPatch;
     const bool half = lane >= 32;  // rows v > 0 for the upper half-wave, v <= 0 for the lower
     if ((lane & 31) < 2 * kHalfPatch + 1) {
@@ -153,7 +170,7 @@ __global__ __launch_bounds__(64 * kDescWaves) void k_orb_desc(OrbPyr P, int n, c
   const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
   const float angle = ang * factorPI;
   const float a = lorb_cosf(angle), b = lorb_sinf(angle);  // std::cos(float) = libm cosf (:115)
-  const uint8_t* center = P.blur + P.offset[l] + (int64_t)cy * step + cx;
+  const uint8_t* center = blurred + P.offset[l] + (int64_t)cy * step + cx;
   int nib = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -165,6 +182,40 @@ __global__ __launch_bounds__(64 * kDescWaves) void k_orb_desc(OrbPyr P, int n, c
   const int hi = __shfl_down(nib, 1, 64);
   if ((lane & 1) == 0) desc_out[32 * (size_t)i + (lane >> 1)] = (uint8_t)(nib | (hi << 4));
   if (lane == 0) angle_out[i] = ang;
+}
+
+__global__ __launch_bounds__(64 * kDescWaves) void k_orb_desc(OrbPyr P, int n, const int* __restrict__ d_n,
+                                                              const float* __restrict__ kx,
+                                                              const float* __restrict__ ky,
+                                                              const int* __restrict__ klev,
+                                                              const int* __restrict__ pattern,
+                                                              float* __restrict__ angle_out,
+                                                              uint8_t* __restrict__ desc_out) {
+  __shared__ int s_pat[1024];
+  for (int e = threadIdx.x; e < 1024; e += 64 * kDescWaves) s_pat[e] = pattern[e];
+  __syncthreads();
+  desc_key(P, P.data, P.blur, n, d_n, kx, ky, klev, s_pat, angle_out, desc_out);
+}
+
+// per-image keypoint arrays of k_orb_desc2 (d_n: that image's device count, never null)
+struct DescSide {
+  const uint8_t* data;
+  const uint8_t* blur;
+  const int* d_n;
+  const float *kx, *ky;
+  const int* klev;
+  float* angle;
+  uint8_t* desc;
+};
+
+// launched over the capacity `cap` per image; a wave at or past its image's count exits in desc_key
+__global__ __launch_bounds__(64 * kDescWaves) void k_orb_desc2(OrbPyr P, int cap, DescSide s0, DescSide s1,
+                                                               const int* __restrict__ pattern) {
+  __shared__ int s_pat[1024];
+  for (int e = threadIdx.x; e < 1024; e += 64 * kDescWaves) s_pat[e] = pattern[e];
+  __syncthreads();
+  const DescSide& s = blockIdx.y ? s1 : s0;
+  desc_key(P, s.data, s.blur, cap, s.d_n, s.kx, s.ky, s.klev, s_pat, s.angle, s.desc);
 }
 
 // cv::getGaussianKernel(7, 2, CV_32F) * 256, rounded (convertTo CV_32S, float arithmetic)
@@ -246,11 +297,11 @@ int enqueue_orb(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const uint8_t* d_d
 // columns < xs and the scalar FixedPtCast for the rest (oracle/orb.c states the formulas).
 __device__ __forceinline__ int sat16d(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 
-__global__ __launch_bounds__(256) void k_orb_resize(const uint8_t* __restrict__ src, int sh, int sw, int sstep,
-                                                    uint8_t* __restrict__ dst, int dh, int dw, int dstep,
-                                                    const int* __restrict__ xofs, const short2* __restrict__ ia,
-                                                    const int* __restrict__ yofs, const short2* __restrict__ ib,
-                                                    int xmax, int xs) {
+__device__ __forceinline__ void resize_px(const uint8_t* __restrict__ src, int sh, int sw, int sstep,
+                                          uint8_t* __restrict__ dst, int dh, int dw, int dstep,
+                                          const int* __restrict__ xofs, const short2* __restrict__ ia,
+                                          const int* __restrict__ yofs, const short2* __restrict__ ib, int xmax,
+                                          int xs) {
   const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
   const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (dx >= dw || dy >= dh) return;
@@ -275,6 +326,36 @@ __global__ __launch_bounds__(256) void k_orb_resize(const uint8_t* __restrict__ 
     v = (r[0] * b.x + r[1] * b.y + (1 << 21)) >> 22;
   }
   dst[(int64_t)dy * dstep + dx] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+__global__ __launch_bounds__(256) void k_orb_resize(const uint8_t* __restrict__ src, int sh, int sw, int sstep,
+                                                    uint8_t* __restrict__ dst, int dh, int dw, int dstep,
+                                                    const int* __restrict__ xofs, const short2* __restrict__ ia,
+                                                    const int* __restrict__ yofs, const short2* __restrict__ ib,
+                                                    int xmax, int xs) {
+  resize_px(src, sh, sw, sstep, dst, dh, dw, dstep, xofs, ia, yofs, ib, xmax, xs);
+}
+
+// level l-1 -> level l of both pyramids (blockIdx.z = image; offsets inside the pyramid buffers)
+__global__ __launch_bounds__(256) void k_orb_resize2(uint8_t* __restrict__ pyr0, uint8_t* __restrict__ pyr1,
+                                                     int64_t soff, int sh, int sw, int sstep, int64_t doff, int dh,
+                                                     int dw, int dstep, const int* __restrict__ xofs,
+                                                     const short2* __restrict__ ia, const int* __restrict__ yofs,
+                                                     const short2* __restrict__ ib, int xmax, int xs) {
+  uint8_t* pyr = blockIdx.z ? pyr1 : pyr0;
+  resize_px(pyr + soff, sh, sw, sstep, pyr + doff, dh, dw, dstep, xofs, ia, yofs, ib, xmax, xs);
+}
+
+// level 0 of both pyramids: the two images (row strides step0 / step1) packed to `cols` bytes per
+// row; blockIdx.y = image, one thread per pixel
+__global__ __launch_bounds__(256) void k_orb_copy2(const uint8_t* __restrict__ img0, int step0,
+                                                   const uint8_t* __restrict__ img1, int step1, int rows, int cols,
+                                                   uint8_t* __restrict__ pyr0, uint8_t* __restrict__ pyr1) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (int64_t)rows * cols) return;
+  const int r = (int)(p / cols), c = (int)(p - (int64_t)r * cols);
+  if (blockIdx.y) pyr1[p] = img1[(int64_t)r * step1 + c];
+  else pyr0[p] = img0[(int64_t)r * step0 + c];
 }
 
 short sat16h(int v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
@@ -404,13 +485,19 @@ __device__ __forceinline__ int fast_score(int v, const int (&ring)[16], int thre
 // One 256-thread workgroup per cell: the cell image in LDS, FAST_t<16> detection + score of every
 // inner pixel, 3x3 non-maximum suppression, the minThFAST re-run when no corner survives, and the
 // survivors written in FAST's row-major order (block scan) relative to the level border.
-__global__ __launch_bounds__(kFastThreads) void k_orb_fast(const uint8_t* __restrict__ data, OrbPyr P,
-                                                           const FastCell* __restrict__ cells, int ini_th, int min_th,
-                                                           float* __restrict__ ox, float* __restrict__ oy,
-                                                           float* __restrict__ oresp, int* __restrict__ ocount) {
-  __shared__ uint8_t img[kCellMax * kCellMax], score[kCellMax * kCellMax], corner[kCellMax * kCellMax];
-  __shared__ int s_count, wsum[kFastThreads / 64];
-  const FastCell c = cells[blockIdx.x];
+struct FastSh {
+  uint8_t img[kCellMax * kCellMax], score[kCellMax * kCellMax], corner[kCellMax * kCellMax];
+  int s_count, wsum[kFastThreads / 64];
+};
+
+__device__ __forceinline__ void fast_cell(const uint8_t* __restrict__ data, const OrbPyr& P, const FastCell c,
+                                          int ini_th, int min_th, float* __restrict__ ox, float* __restrict__ oy,
+                                          float* __restrict__ oresp, int* __restrict__ ocount, FastSh& sh) {
+  uint8_t* img = sh.img;
+  uint8_t* score = sh.score;
+  uint8_t* corner = sh.corner;
+  int& s_count = sh.s_count;
+  int* wsum = sh.wsum;
   const int w = c.w, h = c.h, n = w * h, t = threadIdx.x;
   const uint8_t* src = data + P.offset[c.level] + (int64_t)c.ini_y * P.step[c.level] + c.ini_x;
   const int step = P.step[c.level];
@@ -489,7 +576,30 @@ __global__ __launch_bounds__(kFastThreads) void k_orb_fast(const uint8_t* __rest
     }
     run += tot;
   }
-  if (t == 0) ocount[blockIdx.x] = run;
+  if (t == 0) *ocount = run;
+}
+
+__global__ __launch_bounds__(kFastThreads) void k_orb_fast(const uint8_t* __restrict__ data, OrbPyr P,
+                                                           const FastCell* __restrict__ cells, int ini_th, int min_th,
+                                                           float* __restrict__ ox, float* __restrict__ oy,
+                                                           float* __restrict__ oresp, int* __restrict__ ocount) {
+  __shared__ FastSh sh;
+  fast_cell(data, P, cells[blockIdx.x], ini_th, min_th, ox, oy, oresp, ocount + blockIdx.x, sh);
+}
+
+// both images over one cell table: image blockIdx.y writes its corners fast_cap floats and its cell
+// counts n_cells ints after image 0's
+__global__ __launch_bounds__(kFastThreads) void k_orb_fast2(const uint8_t* __restrict__ data0,
+                                                            const uint8_t* __restrict__ data1, OrbPyr P,
+                                                            const FastCell* __restrict__ cells, int n_cells,
+                                                            int fast_cap, int ini_th, int min_th,
+                                                            float* __restrict__ ox, float* __restrict__ oy,
+                                                            float* __restrict__ oresp, int* __restrict__ ocount) {
+  __shared__ FastSh sh;
+  const int im = blockIdx.y;
+  const size_t fo = (size_t)im * fast_cap;
+  fast_cell(im ? data1 : data0, P, cells[blockIdx.x], ini_th, min_th, ox + fo, oy + fo, oresp + fo,
+            ocount + (size_t)im * n_cells + blockIdx.x, sh);
 }
 
 // the cell grid of one level, src/ORBextractor.cpp:803-847 (see oracle/fast.c)
@@ -1421,16 +1531,34 @@ __global__ __launch_bounds__(kOctThreads) void k_orb_octree(OctArgs A) {
     oct_global(A, sh, s_key);
 }
 
+// Both images' quadtrees in one launch: 2 * n_levels workgroups, level = blockIdx.x and image =
+// blockIdx.y (each image has its own OctArgs: the same plan over its own scratch).  The LDS of a
+// workgroup is k_orb_octree's.
+struct OctArgs2 {
+  OctArgs a[2];
+};
+
+__global__ __launch_bounds__(kOctThreads) void k_orb_octree2(OctArgs2 AA) {
+  __shared__ OctSh sh;
+  __shared__ long long s_key[kOctKeyChunk];
+  __shared__ OctLds S;
+  __shared__ OctWaves ww;
+  const OctArgs& A = AA.a[blockIdx.y];
+  const OctLevel& V = A.lv[blockIdx.x];
+  if (V.node_cap <= kOctNC && V.cell_end - V.cell_begin <= kOctCells)
+    oct_lds(A, sh, S, ww, s_key);
+  else
+    oct_global(A, sh, s_key);
+}
+
 // Gathers the per-level results in level order: level coordinates, octave, size, response and the
 // level-0 (scaled) coordinates (:881-891, :1141-1147); level_off[n_levels + 1] and *n_total (-1
 // when a level failed).
-__global__ __launch_bounds__(256) void k_orb_gather(OctArgs A, int cap, float* __restrict__ lx, float* __restrict__ ly,
-                                                    float* __restrict__ sx, float* __restrict__ sy,
-                                                    int* __restrict__ oct, float* __restrict__ size,
-                                                    float* __restrict__ resp, int* __restrict__ level_off,
-                                                    int* __restrict__ n_total) {
-  __shared__ int off[LORB_MAX_LEVELS + 1];
-  __shared__ int bad;
+__device__ __forceinline__ void gather_keys(const OctArgs& A, int cap, float* __restrict__ lx, float* __restrict__ ly,
+                                            float* __restrict__ sx, float* __restrict__ sy, int* __restrict__ oct,
+                                            float* __restrict__ size, float* __restrict__ resp,
+                                            int* __restrict__ level_off, int* __restrict__ n_total, int* off,
+                                            int& bad) {
   if (threadIdx.x == 0) {
     int s = 0, b = 0;
     for (int l = 0; l < A.n_levels; l++) {
@@ -1458,6 +1586,31 @@ __global__ __launch_bounds__(256) void k_orb_gather(OctArgs A, int cap, float* _
   sx[i] = l != 0 ? x * V.scale : x;
   sy[i] = l != 0 ? y * V.scale : y;
   oct[i] = l; size[i] = V.size; resp[i] = A.kr[V.key_base + k];
+}
+
+__global__ __launch_bounds__(256) void k_orb_gather(OctArgs A, int cap, float* __restrict__ lx, float* __restrict__ ly,
+                                                    float* __restrict__ sx, float* __restrict__ sy,
+                                                    int* __restrict__ oct, float* __restrict__ size,
+                                                    float* __restrict__ resp, int* __restrict__ level_off,
+                                                    int* __restrict__ n_total) {
+  __shared__ int off[LORB_MAX_LEVELS + 1];
+  __shared__ int bad;
+  gather_keys(A, cap, lx, ly, sx, sy, oct, size, resp, level_off, n_total, off, bad);
+}
+
+struct GatherOut {
+  float *lx, *ly, *sx, *sy;
+  int* oct;
+  float *size, *resp;
+  int *level_off, *n_total;
+};
+
+// both images (blockIdx.y), each into its own outputs; n_total is that image's entry of counts[2]
+__global__ __launch_bounds__(256) void k_orb_gather2(OctArgs2 AA, int cap, GatherOut o0, GatherOut o1) {
+  __shared__ int off[LORB_MAX_LEVELS + 1];
+  __shared__ int bad;
+  const GatherOut& o = blockIdx.y ? o1 : o0;
+  gather_keys(AA.a[blockIdx.y], cap, o.lx, o.ly, o.sx, o.sy, o.oct, o.size, o.resp, o.level_off, o.n_total, off, bad);
 }
 
 // Host plan of the keypoint stage: cells, capacities and the octree arguments (device pointers are
@@ -1910,3 +2063,156 @@ int lorb_orb_extract(lorb_ctx* ctx, const uint8_t* image, int32_t rows, int32_t 
 }
 
 }  // extern "C"
+
+// ---- the extractor over a stereo pair (lorb_frame.hip's builder) ---------------------------
+// Everything that depends only on the geometry is built once: the pyramid layout, the resize tap
+// tables of every level, the FAST cell table, the quadtree plan, the blur tiles, the pattern, and
+// the scratch of both images.  A frame is then 13 launches with the image as a grid dimension and
+// no host work beyond them: copy, n_levels - 1 resizes, FAST, quadtree, gather, blur, describe.
+namespace lorb {
+
+struct OrbPair {
+  int rows = 0, cols = 0, n_levels = 0, ini_th = 0, min_th = 0;
+  lorb_image_pyramid layout{};
+  int64_t pyr_bytes = 0;
+  OrbPlan plan;
+  OctArgs2 AA{};
+  OrbPyr P{};  // offsets, tiles, taps, umax (data / blur are set per call)
+  int tiles = 0, n_cells = 0;
+  struct Level {
+    int *xofs, *yofs;
+    short2 *ia, *ib;
+    int xmax, xs;
+  } lvl[LORB_MAX_LEVELS] = {};
+  FastCell* d_cells = nullptr;
+  int* d_cnt = nullptr;
+  float *fx = nullptr, *fy = nullptr, *fr = nullptr;
+  uint8_t* blur[2] = {};
+  float *lx[2] = {}, *ly[2] = {};
+  int* d_pat = nullptr;
+  Arena arena;
+};
+
+void orb_pair_destroy(OrbPair* B) {
+  if (!B) return;
+  B->arena.release();
+  delete B;
+}
+
+int orb_pair_create(lorb_ctx* ctx, int rows, int cols, int n_levels, const float* sf, const int32_t* n_desired,
+                    int ini_th, int min_th, const int32_t* pattern, OrbPair** out) {
+  if (!sf || !n_desired || !pattern || !out || rows < 1 || cols < 1 || n_levels < 1 || n_levels > LORB_MAX_LEVELS)
+    return set_error(ctx, LORB_E_INVALID, "bad image / level / pattern arguments");
+  OrbPair* B = new (std::nothrow) OrbPair;
+  if (!B) return set_error(ctx, LORB_E_NOMEM, "out of host memory");
+  struct Guard {
+    OrbPair* b;
+    ~Guard() { orb_pair_destroy(b); }
+  } guard{B};
+  B->rows = rows; B->cols = cols; B->n_levels = n_levels; B->ini_th = ini_th; B->min_th = min_th;
+  B->pyr_bytes = pyramid_layout(rows, cols, n_levels, sf, &B->layout);
+  LORB_TRY(orb_plan(ctx, &B->layout, n_desired, sf, &B->plan));
+  const lorb_image_pyramid& L = B->layout;
+  OrbPyr& P = B->P;
+  P.n_levels = n_levels;
+  for (int l = 0; l < n_levels; l++) {
+    P.offset[l] = L.offset[l]; P.rows[l] = L.rows[l]; P.cols[l] = L.cols[l]; P.step[l] = L.step[l];
+    P.tile_off[l] = B->tiles;
+    P.tiles_x[l] = (L.cols[l] + kTileW - 1) / kTileW;
+    B->tiles += P.tiles_x[l] * ((L.rows[l] + kTileH - 1) / kTileH);
+  }
+  P.tile_off[n_levels] = B->tiles;
+  gauss_taps(P.k);
+  orb_umax(P.umax);
+  // device memory: one block
+  Arena& M = B->arena;
+  OrbPlan& Q = B->plan;
+  B->n_cells = (int)Q.cells.size();
+  const size_t K = (size_t)std::max(Q.key_total, 1), NN = (size_t)std::max(Q.node_total, 1);
+  const size_t F = (size_t)std::max(Q.fast_cap, 1), NC = (size_t)std::max(B->n_cells, 1);
+  for (int l = 1; l < n_levels; l++) {
+    M.add(&B->lvl[l].xofs, (size_t)L.cols[l]); M.add(&B->lvl[l].ia, (size_t)L.cols[l]);
+    M.add(&B->lvl[l].yofs, (size_t)L.rows[l]); M.add(&B->lvl[l].ib, (size_t)L.rows[l]);
+  }
+  M.add(&B->d_cells, NC); M.add(&B->d_cnt, 2 * NC);
+  M.add(&B->fx, 2 * F); M.add(&B->fy, 2 * F); M.add(&B->fr, 2 * F);
+  M.add(&B->d_pat, (size_t)1024);
+  for (int im = 0; im < 2; im++) {
+    OctArgs& A = B->AA.a[im];
+    A = Q.A;
+    M.add(&A.kx, K); M.add(&A.ky, K); M.add(&A.kr, K);
+    M.add(&A.perm, K); M.add(&A.perm2, K); M.add(&A.cls, K); M.add(&A.own, K); M.add(&A.hd, K);
+    M.add(&A.ex, K + LORB_MAX_LEVELS);
+    M.add(&A.na, NN); M.add(&A.nb, NN); M.add(&A.act, NN); M.add(&A.rank, NN); M.add(&A.ech, NN);
+    M.add(&A.tmp, NN); M.add(&A.surv, NN); M.add(&A.cnt, NN); M.add(&A.out_key, NN);
+    M.add(&A.out_cnt, (size_t)LORB_MAX_LEVELS);
+    M.add(&B->blur[im], (size_t)B->pyr_bytes);
+    M.add(&B->lx[im], NN); M.add(&B->ly[im], NN);
+  }
+  LORB_HIP(ctx, M.commit());
+  for (int im = 0; im < 2; im++) {
+    OctArgs& A = B->AA.a[im];
+    A.cells = B->d_cells; A.cell_cnt = B->d_cnt + im * NC;
+    A.fx = B->fx + im * F; A.fy = B->fy + im * F; A.fr = B->fr + im * F;
+    A.trace = nullptr;
+  }
+  // the tables (blocking copies: create is not on the per-frame path)
+  for (int l = 1; l < n_levels; l++) {
+    std::vector<int> xofs, yofs;
+    std::vector<short2> ia, ib;
+    resize_tabs(L.cols[l - 1], L.cols[l], xofs, ia, &B->lvl[l].xmax, true);
+    resize_tabs(L.rows[l - 1], L.rows[l], yofs, ib, nullptr, false);
+    B->lvl[l].xs = simd_cols(L.cols[l]);
+    LORB_HIP(ctx, hipMemcpy(B->lvl[l].xofs, xofs.data(), sizeof(int) * xofs.size(), hipMemcpyHostToDevice));
+    LORB_HIP(ctx, hipMemcpy(B->lvl[l].ia, ia.data(), sizeof(short2) * ia.size(), hipMemcpyHostToDevice));
+    LORB_HIP(ctx, hipMemcpy(B->lvl[l].yofs, yofs.data(), sizeof(int) * yofs.size(), hipMemcpyHostToDevice));
+    LORB_HIP(ctx, hipMemcpy(B->lvl[l].ib, ib.data(), sizeof(short2) * ib.size(), hipMemcpyHostToDevice));
+  }
+  if (B->n_cells)
+    LORB_HIP(ctx, hipMemcpy(B->d_cells, Q.cells.data(), sizeof(FastCell) * Q.cells.size(), hipMemcpyHostToDevice));
+  LORB_HIP(ctx, hipMemcpy(B->d_pat, pattern, sizeof(int) * 1024, hipMemcpyHostToDevice));
+  guard.b = nullptr;
+  *out = B;
+  return LORB_OK;
+}
+
+void orb_pair_info(const OrbPair* B, int* capacity, int64_t* pyr_bytes, lorb_image_pyramid* layout) {
+  if (capacity) *capacity = B->plan.out_cap;
+  if (pyr_bytes) *pyr_bytes = B->pyr_bytes;
+  if (layout) *layout = B->layout;
+}
+
+int orb_pair_enqueue(lorb_ctx* ctx, OrbPair* B, const uint8_t* d_img0, int step0, const uint8_t* d_img1, int step1,
+                     const OrbPairSide& o0, const OrbPairSide& o1, int* d_counts) {
+  const lorb_image_pyramid& L = B->layout;
+  const int cap = B->plan.out_cap;
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(k_orb_copy2, dim3(ceil_div((size_t)B->rows * B->cols, 256), 2), dim3(256), 0, st, d_img0, step0,
+                     d_img1, step1, B->rows, B->cols, o0.pyramid, o1.pyramid);
+  for (int l = 1; l < B->n_levels; l++) {
+    const OrbPair::Level& T = B->lvl[l];
+    hipLaunchKernelGGL(k_orb_resize2, dim3(ceil_div(L.cols[l], 64), ceil_div(L.rows[l], 4), 2), dim3(256), 0, st,
+                       o0.pyramid, o1.pyramid, L.offset[l - 1], L.rows[l - 1], L.cols[l - 1], L.step[l - 1], L.offset[l],
+                       L.rows[l], L.cols[l], L.step[l], T.xofs, T.ia, T.yofs, T.ib, T.xmax, T.xs);
+  }
+  OrbPyr P = B->P;
+  P.data = o0.pyramid;
+  P.blur = B->blur[0];
+  if (B->n_cells)
+    hipLaunchKernelGGL(k_orb_fast2, dim3((unsigned)B->n_cells, 2), dim3(kFastThreads), 0, st, o0.pyramid, o1.pyramid, P,
+                       B->d_cells, B->n_cells, std::max(B->plan.fast_cap, 1), B->ini_th, B->min_th, B->fx, B->fy, B->fr,
+                       B->d_cnt);
+  hipLaunchKernelGGL(k_orb_octree2, dim3(B->n_levels, 2), dim3(kOctThreads), 0, st, B->AA);
+  const GatherOut g0{B->lx[0], B->ly[0], o0.x, o0.y, o0.octave, o0.size, o0.response, o0.level_off, d_counts};
+  const GatherOut g1{B->lx[1], B->ly[1], o1.x, o1.y, o1.octave, o1.size, o1.response, o1.level_off, d_counts + 1};
+  hipLaunchKernelGGL(k_orb_gather2, dim3(ceil_div(cap, 256), 2), dim3(256), 0, st, B->AA, cap, g0, g1);
+  hipLaunchKernelGGL(k_orb_blur2, dim3(B->tiles, 2), dim3(256), 0, st, P, OrbSide2{o1.pyramid, B->blur[1]});
+  const DescSide s0{o0.pyramid, B->blur[0], d_counts, B->lx[0], B->ly[0], o0.octave, o0.angle, o0.desc};
+  const DescSide s1{o1.pyramid, B->blur[1], d_counts + 1, B->lx[1], B->ly[1], o1.octave, o1.angle, o1.desc};
+  hipLaunchKernelGGL(k_orb_desc2, dim3(ceil_div(cap, kDescWaves), 2), dim3(64 * kDescWaves), 0, st, P, cap, s0, s1,
+                     B->d_pat);
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
+
+}  // namespace lorb

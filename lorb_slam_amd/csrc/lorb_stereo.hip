@@ -56,8 +56,19 @@ __device__ __forceinline__ int band_packed(int o, float kpY, const float* s_sf, 
   return lo | (hi << 16);
 }
 
-__global__ __launch_bounds__(1024) void k_st_rows(Keys R, Scales S, int n_levels, int nRows, int* __restrict__ row_off,
-                                                  int* __restrict__ row_list) {
+// The device-count variants (kDevCount; lorb_frame_build*): the Keys' n is that side's capacity and
+// counts = {n_left, n_right} lives in device memory.  A count is used only once it is bounded by its
+// capacity; a negative count (an extraction that failed) makes both sides empty.
+__device__ __forceinline__ int dev_count(const int* __restrict__ counts, int side, int cap) {
+  const int l = counts[0], r = counts[1];
+  if (l < 0 || r < 0) return 0;
+  return min(side ? r : l, cap);
+}
+
+template <bool kDevCount>
+__global__ __launch_bounds__(1024) void k_st_rows(Keys R, const int* __restrict__ counts, Scales S, int n_levels,
+                                                  int nRows, int* __restrict__ row_off, int* __restrict__ row_list) {
+  if (kDevCount) R.n = dev_count(counts, 1, R.n);
   __shared__ int cnt[kStMaxRows + 1];
   __shared__ int s_band[kStBandKeys];
   __shared__ float s_sf[LORB_MAX_LEVELS];
@@ -107,13 +118,19 @@ __device__ __forceinline__ int px(const Pyr& P, int lv, int r, int c) {
   return P.data[P.offset[lv] + (int64_t)r * P.step[lv] + c];
 }
 
-__global__ __launch_bounds__(64 * kStWaves) void k_st_match(Keys L, Keys R, Pyr PL, Pyr PR, Scales S, float bf, float b,
+template <bool kDevCount>
+__global__ __launch_bounds__(64 * kStWaves) void k_st_match(Keys L, Keys R, const int* __restrict__ counts, Pyr PL,
+                                                            Pyr PR, Scales S, float bf, float b,
                                                             const int* __restrict__ row_off,
                                                             const int* __restrict__ row_list, float* __restrict__ u_right,
                                                             float* __restrict__ depth, int* __restrict__ sad_out) {
   __shared__ int rs[kStWaves][128];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int iL = blockIdx.x * kStWaves + wv;
+  if (kDevCount) {  // launched over the capacity: a wave at or past n_left exits before any other load
+    L.n = dev_count(counts, 0, L.n);
+    R.n = dev_count(counts, 1, R.n);
+  }
   if (iL >= L.n) return;
   float ur_o = -1.0f, dp_o = -1.0f;
   int sad_o = -1;
@@ -131,6 +148,7 @@ __global__ __launch_bounds__(64 * kStWaves) void k_st_match(Keys L, Keys R, Pyr 
     const uint4* dL = L.desc + 2 * (size_t)iL;
     for (int c = c0 + lane; c < c1; c += 64) {
       const int iR = row_list[c];
+      if (kDevCount && (unsigned)iR >= (unsigned)R.n) continue;  // k_st_rows wrote only indices below n_right
       const int o = R.octave[iR];
       if (o < levelL - 1 || o > levelL + 1) continue;
       const float uR = R.x[iR];
@@ -239,8 +257,10 @@ __device__ __forceinline__ void select_bucket(const int* hist, int k, int& b, in
   r = __shfl(kk, src, 64);
 }
 
-__global__ __launch_bounds__(1024) void k_st_reject(int n, const int* __restrict__ sad, float* __restrict__ u_right,
-                                                    float* __restrict__ depth) {
+template <bool kDevCount>
+__global__ __launch_bounds__(1024) void k_st_reject(int n, const int* __restrict__ counts, const int* __restrict__ sad,
+                                                    float* __restrict__ u_right, float* __restrict__ depth) {
+  if (kDevCount) n = dev_count(counts, 0, n);
   __shared__ int hist[256];
   __shared__ int s_n, s_hi, s_rank, s_med;
   const int t = threadIdx.x;
@@ -332,13 +352,15 @@ int enqueue_stereo(lorb_ctx* ctx, const lorb_frame_params* fp, const Keys& L, co
   LORB_TRY(lorb::scratch_t(ctx, S_ST + 0, (size_t)nRows + 1, &row_off));
   LORB_TRY(lorb::scratch_t(ctx, S_ST + 1, std::max<size_t>((size_t)R.n * per, 1), &row_list));
   LORB_TRY(lorb::scratch_t(ctx, S_ST + 2, std::max<size_t>((size_t)L.n, 1), &sad));
-  hipLaunchKernelGGL(k_st_rows, dim3(1), dim3(1024), 0, ctx->stream, R, S, fp->n_levels, nRows, row_off, row_list);
+  const int* no_counts = nullptr;
+  hipLaunchKernelGGL((k_st_rows<false>), dim3(1), dim3(1024), 0, ctx->stream, R, no_counts, S, fp->n_levels, nRows,
+                     row_off, row_list);
   {
     lorb::KernelTimer kt(ctx, LORB_K_STEREO);
-    hipLaunchKernelGGL(k_st_match, dim3(lorb::ceil_div(L.n, kStWaves)), dim3(64 * kStWaves), 0, ctx->stream, L, R, PL,
-                       PR, S, fp->bf, fp->b, row_off, row_list, d_ur, d_dp, sad);
+    hipLaunchKernelGGL((k_st_match<false>), dim3(lorb::ceil_div(L.n, kStWaves)), dim3(64 * kStWaves), 0, ctx->stream, L,
+                       R, no_counts, PL, PR, S, fp->bf, fp->b, row_off, row_list, d_ur, d_dp, sad);
   }
-  hipLaunchKernelGGL(k_st_reject, dim3(1), dim3(1024), 0, ctx->stream, L.n, sad, d_ur, d_dp);
+  hipLaunchKernelGGL((k_st_reject<false>), dim3(1), dim3(1024), 0, ctx->stream, L.n, no_counts, sad, d_ur, d_dp);
   LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
 }
@@ -406,3 +428,43 @@ int lorb_compute_stereo_matches(lorb_ctx* ctx, const lorb_frame_params* frame, c
 }
 
 }  // extern "C"
+
+namespace lorb {
+
+namespace {
+// each right keypoint covers at most ceil(y + r) - floor(y - r) + 1 rows (as enqueue_stereo)
+size_t rows_per_key(const lorb_frame_params* fp) {
+  float rmax = 0;
+  for (int l = 0; l < fp->n_levels; l++) rmax = std::max(rmax, 2.0f * fp->scale_factors[l]);
+  return (size_t)(2.0f * rmax) + 3;
+}
+}  // namespace
+
+size_t stereo_row_list_len(const lorb_frame_params* fp, int right_capacity) {
+  return std::max<size_t>((size_t)std::max(right_capacity, 0) * rows_per_key(fp), 1);
+}
+
+int enqueue_stereo_counts(lorb_ctx* ctx, const lorb_frame_params* fp, const lorb_image_pyramid* layout,
+                          const StereoSideDev& l, const StereoSideDev& r, const int* d_counts, int* row_off,
+                          int* row_list, int* sad, float* d_ur, float* d_dp) {
+  const int nRows = layout->rows[0];
+  if (nRows > kStMaxRows) return set_error(ctx, LORB_E_INVALID, "image rows %d > %d", nRows, kStMaxRows);
+  if (l.capacity < 1 || r.capacity < 0) return set_error(ctx, LORB_E_INVALID, "bad stereo capacity");
+  Scales S{};
+  for (int k = 0; k < LORB_MAX_LEVELS; k++) S.sf[k] = fp->scale_factors[k];
+  const Keys L{l.x, l.y, l.octave, reinterpret_cast<const uint4*>(l.desc), l.capacity};
+  const Keys R{r.x, r.y, r.octave, reinterpret_cast<const uint4*>(r.desc), r.capacity};
+  const Pyr PL = pyr_of(layout, l.pyramid), PR = pyr_of(layout, r.pyramid);
+  hipLaunchKernelGGL((k_st_rows<true>), dim3(1), dim3(1024), 0, ctx->stream, R, d_counts, S, fp->n_levels, nRows,
+                     row_off, row_list);
+  {
+    KernelTimer kt(ctx, LORB_K_STEREO);
+    hipLaunchKernelGGL((k_st_match<true>), dim3(ceil_div(L.n, kStWaves)), dim3(64 * kStWaves), 0, ctx->stream, L, R,
+                       d_counts, PL, PR, S, fp->bf, fp->b, row_off, row_list, d_ur, d_dp, sad);
+  }
+  hipLaunchKernelGGL((k_st_reject<true>), dim3(1), dim3(1024), 0, ctx->stream, L.n, d_counts, sad, d_ur, d_dp);
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
+
+}  // namespace lorb

@@ -473,6 +473,37 @@ def orb_scene(seed=91, rows=H, cols=W, n_shapes=120, noise=3):
     return np.clip(np.rint(img), 0, 255).astype(np.uint8)
 
 
+STEREO_SHIFTS = (6, 14, 27)  # disparity of the three row bands of stereo_pair
+
+
+def stereo_pair(seed, rows, cols, kind="scene", noise=2, shift=0, noise_seed=None):
+    """A rectified stereo pair for the whole Frame constructor (extractor x 2 + ComputeStereoMatches):
+    one wide image (orb_scene without pixel noise, or uniform noise for kind="noise"), the left image
+    its first `cols` columns, the right image the same rows shifted left by 6 / 14 / 27 (+ shift)
+    pixels in three row bands -- three depths -- then integer pixel noise in [-noise, noise] from
+    default_rng(noise_seed, default seed + 1), drawn for the left image first.  shift > 0 moves every
+    band further (the wide image's last column is repeated).  -> (left, right), uint8 rows x cols."""
+    wcols = cols + STEREO_SHIFTS[-1]
+    if kind == "scene":
+        wide = orb_scene(seed, rows, wcols, n_shapes=max(20, rows * cols // 3000), noise=0)
+    else:
+        wide = np.random.default_rng(seed).integers(0, 256, (rows, wcols), dtype=np.uint8)
+    if shift:
+        wide = np.pad(wide, ((0, 0), (0, shift)), mode="edge")
+    left = wide[:, :cols].copy()
+    right = np.empty_like(left)
+    edges = np.linspace(0, rows, 4).astype(int)
+    for b, d in enumerate(STEREO_SHIFTS):
+        right[edges[b]:edges[b + 1]] = wide[edges[b]:edges[b + 1], d + shift:d + shift + cols]
+    if noise:
+        rng = np.random.default_rng(seed + 1 if noise_seed is None else noise_seed)
+        out = []
+        for img in (left, right):
+            out.append(np.clip(img.astype(np.int64) + rng.integers(-noise, noise + 1, img.shape), 0, 255).astype(np.uint8))
+        left, right = out
+    return left, right
+
+
 def mapping_sequence(seed=4, n_kf=50, n_fixed=5, n_new=189, obs_lens=(7, 8), steps=8, n_kps=2000,
                      max_flips=20, noise_px=0.5, pert=(2e-3, 2e-2, 5e-2), fx=FX, fy=FY, cx=CX, cy=CY):
     """A stationary keyframe stream for the LocalMapping full step (VERDICT r01

@@ -520,18 +520,55 @@ __device__ __forceinline__ I4 block_excl_scan4(const I4& v, I4* wsum, I4* total)
 
 }  // namespace lorb
 
-// scratch slot plan (per API family; calls on one ctx are serialized)
+// Scratch slot plan: every family of ctx->scratch slots, declared once.  Calls on one ctx are
+// serialized, so per-call families may share slots (the aliases below); a persistent slot keeps its
+// contents from one API call to the next and is shared with nothing.
+struct SlotFamily {
+  int base, n;
+  bool persistent;
+};
+// slots named one by one
 enum {
   S_BF_Q = 0, S_BF_T, S_BF_TL, S_BF_TILES, S_BF_K1, S_BF_K2, S_BF_QKEY, S_BF_OUT0, S_BF_OUT1,
-  S_BF_OUT2, S_BF_OUT3, S_BF_OUT4, S_BF_OUT5, S_BF_OFF,
-  S_W0 = 14, S_W1, S_W2, S_W3, S_W4, S_W5, S_W6, S_W7, S_W8, S_W9,
-  S_KP = 24,   /* 10 slots: keypoint upload + grid */
-  S_WX = 34,   /* 8 slots: windowed-matcher scratch */
-  S_TM = 88,   /* 3 slots: motion-tracking chain (pass 2's codes + both counts, the residual list, the host form's codes) */
-  S_TM_ZERO = 91, /* all-EMPTY slot states: zeroed when (re)allocated, never written */
-  S_TLC = 92,  /* 6 slots: local-map tracking chain (match count, residual list; the host form's codes, in-view flags, fields, levels) */
+  S_BF_OUT2, S_BF_OUT3, S_BF_OUT4, S_BF_OUT5, S_BF_OFF,  // brute-force matcher
+  S_W0 = 14, S_W1, S_W2, S_W3, S_W4, S_W5, S_W6, S_W7, S_W8, S_W9,  // frame-side calls; S_W9: candidate lists
+  // persistent
   S_BF_TKEY = 120, /* crossCheck per-train keys: all-ones between calls (the merge resets them) */
   S_IO_IN = 121,   /* InPack device block */
   S_IO_OUT = 122,  /* OutPack device block */
-  S_BF_DONE = 123  /* k_bf_cc1's workgroup counter: zero between calls (the last workgroup resets it) */
+  S_BF_DONE = 123, /* k_bf_cc1's workgroup counter: zero between calls (the last workgroup resets it) */
+  S_TM_ZERO = 124  /* all-EMPTY slot states: zeroed when (re)allocated, never written (empty_slots) */
 };
+// families addressed by offset: slot<S_WX, 3>()
+inline constexpr SlotFamily
+    S_KP = {24, 10, false},   // keypoint grid of a search (7 .. 9; 0 .. 6 are free: the keypoints travel in the InPack)
+    S_WX = {34, 8, false},    // windowed-matcher working buffers
+    S_ST = {48, 15, false},   // stereo matcher
+    S_ORB = {48, 51, false},  // ORB extractor.  Alias: over S_ST, S_TL, S_TM and S_TLC -- no call runs two of them
+    S_TL = {64, 20, false},   // lorb_track_local_map's staging.  Alias: inside S_ORB's range, as above
+    S_TM = {88, 3, false},    // motion chain: pass 2's codes + both counts, the residual list, the host form's codes
+    S_TLC = {92, 6, false};   // local-map chain: match count, residual list; the host form's codes, in-view flags, fields, levels
+inline constexpr SlotFamily kSlotPlan[] = {
+    {S_BF_Q, 14, false}, {S_W0, 10, false}, S_KP, S_WX, S_ST, S_ORB, S_TL, S_TM, S_TLC,
+    {S_BF_TKEY, 1, true}, {S_IO_IN, 1, true}, {S_IO_OUT, 1, true}, {S_BF_DONE, 1, true}, {S_TM_ZERO, 1, true}};
+
+// slot K of family F; an offset past the family's end does not compile
+template <const SlotFamily& F, int K>
+constexpr int slot() {
+  static_assert(K >= 0 && K < F.n, "scratch slot offset outside its family");
+  return F.base + K;
+}
+constexpr bool slot_plan_fits() {
+  for (const SlotFamily& f : kSlotPlan)
+    if (f.base < 0 || f.n < 1 || f.base + f.n > lorb_ctx::kScratch) return false;
+  return true;
+}
+constexpr bool slot_plan_keeps_persistent() {  // no family's range contains a persistent slot of another
+  for (const SlotFamily& p : kSlotPlan)
+    for (const SlotFamily& f : kSlotPlan)
+      if (p.persistent && &f != &p && f.base < p.base + p.n && p.base < f.base + f.n) return false;
+  return true;
+}
+static_assert(S_BF_OFF == S_BF_Q + 13 && S_W9 == S_W0 + 9, "the named slots fill their families");
+static_assert(slot_plan_fits(), "the scratch slot plan exceeds lorb_ctx::kScratch");
+static_assert(slot_plan_keeps_persistent(), "a scratch family's range contains a persistent slot");

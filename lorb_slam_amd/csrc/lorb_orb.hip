@@ -264,8 +264,6 @@ int check_orb(lorb_ctx* ctx, const lorb_image_pyramid* p, int n) {
   return LORB_OK;
 }
 
-enum { S_ORB = 48 };  // shares the stereo family's slots (calls on one ctx are serialized)
-
 int enqueue_orb(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const uint8_t* d_data, int n, const int* d_n, const float* d_x,
                 const float* d_y, const int* d_lev, const int* d_pat, float* d_ang, uint8_t* d_desc) {
   OrbPyr P{};
@@ -281,7 +279,7 @@ int enqueue_orb(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const uint8_t* d_d
   P.tile_off[pyr->n_levels] = tiles;
   gauss_taps(P.k);
   orb_umax(P.umax);
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 0, (size_t)pyr_extent(pyr), &P.blur));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 0>(), (size_t)pyr_extent(pyr), &P.blur));
   hipLaunchKernelGGL(k_orb_blur, dim3(tiles), dim3(256), 0, ctx->stream, P);
   if (n > 0)
     hipLaunchKernelGGL(k_orb_desc, dim3(lorb::ceil_div(n, kDescWaves)), dim3(64 * kDescWaves), 0, ctx->stream, P, n, d_n,
@@ -421,10 +419,14 @@ int enqueue_pyramid(lorb_ctx* ctx, const uint8_t* d_img, int rows, int cols, int
     resize_tabs(P.rows[l - 1], P.rows[l], yofs, ib, nullptr, false);
     int *dxo, *dyo;
     short2 *dia, *dib;
-    LORB_TRY(lorb::upload_t(ctx, S_ORB + 8 + 4 * (l & 1), xofs.data(), xofs.size(), &dxo));
-    LORB_TRY(lorb::upload_t(ctx, S_ORB + 9 + 4 * (l & 1), ia.data(), ia.size(), &dia));
-    LORB_TRY(lorb::upload_t(ctx, S_ORB + 10 + 4 * (l & 1), yofs.data(), yofs.size(), &dyo));
-    LORB_TRY(lorb::upload_t(ctx, S_ORB + 11 + 4 * (l & 1), ib.data(), ib.size(), &dib));
+    static constexpr int kTabs[2][4] = {  // two sets: consecutive levels alternate
+        {slot<S_ORB, 8>(), slot<S_ORB, 9>(), slot<S_ORB, 10>(), slot<S_ORB, 11>()},
+        {slot<S_ORB, 12>(), slot<S_ORB, 13>(), slot<S_ORB, 14>(), slot<S_ORB, 15>()}};
+    const int* tabs = kTabs[l & 1];
+    LORB_TRY(lorb::upload_t(ctx, tabs[0], xofs.data(), xofs.size(), &dxo));
+    LORB_TRY(lorb::upload_t(ctx, tabs[1], ia.data(), ia.size(), &dia));
+    LORB_TRY(lorb::upload_t(ctx, tabs[2], yofs.data(), yofs.size(), &dyo));
+    LORB_TRY(lorb::upload_t(ctx, tabs[3], ib.data(), ib.size(), &dib));
     const dim3 grid(lorb::ceil_div(P.cols[l], 64), lorb::ceil_div(P.rows[l], 4));
     hipLaunchKernelGGL(k_orb_resize, grid, dim3(256), 0, ctx->stream, d_out + P.offset[l - 1], P.rows[l - 1],
                        P.cols[l - 1], P.step[l - 1], d_out + P.offset[l], P.rows[l], P.cols[l], P.step[l], dxo, dia, dyo,
@@ -1666,36 +1668,36 @@ int orb_plan(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const int32_t* n_desi
   return LORB_OK;
 }
 
-// allocates the scratch of a plan (slots S_ORB + 20 ..) and fills the device pointers of P->A
+// allocates the scratch of a plan (S_ORB slots 20 ..) and fills the device pointers of P->A
 int orb_alloc(lorb_ctx* ctx, OrbPlan* P, FastCell** d_cells, int** d_cnt) {
   OctArgs& A = P->A;
   const size_t K = (size_t)std::max(P->key_total, 1), NN = (size_t)std::max(P->node_total, 1);
   const size_t F = (size_t)std::max(P->fast_cap, 1);
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 20, P->cells.data(), P->cells.size(), d_cells));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 21, std::max<size_t>(P->cells.size(), 1), d_cnt));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 20>(), P->cells.data(), P->cells.size(), d_cells));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 21>(), std::max<size_t>(P->cells.size(), 1), d_cnt));
   float *fx, *fy, *fr, *kx, *ky, *kr;
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 22, F, &fx));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 23, F, &fy));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 24, F, &fr));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 25, K, &kx));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 26, K, &ky));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 27, K, &kr));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 28, K, &A.perm));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 29, K, &A.perm2));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 30, K, &A.cls));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 31, K, &A.own));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 32, K, &A.hd));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 33, K + LORB_MAX_LEVELS, &A.ex));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 34, NN, &A.na));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 35, NN, &A.nb));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 36, NN, &A.act));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 37, NN, &A.rank));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 38, NN, &A.ech));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 39, NN, &A.tmp));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 40, NN, &A.surv));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 41, NN, &A.cnt));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 42, NN, &A.out_key));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 43, (size_t)LORB_MAX_LEVELS, &A.out_cnt));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 22>(), F, &fx));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 23>(), F, &fy));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 24>(), F, &fr));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 25>(), K, &kx));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 26>(), K, &ky));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 27>(), K, &kr));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 28>(), K, &A.perm));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 29>(), K, &A.perm2));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 30>(), K, &A.cls));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 31>(), K, &A.own));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 32>(), K, &A.hd));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 33>(), K + LORB_MAX_LEVELS, &A.ex));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 34>(), NN, &A.na));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 35>(), NN, &A.nb));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 36>(), NN, &A.act));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 37>(), NN, &A.rank));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 38>(), NN, &A.ech));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 39>(), NN, &A.tmp));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 40>(), NN, &A.surv));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 41>(), NN, &A.cnt));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 42>(), NN, &A.out_key));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 43>(), (size_t)LORB_MAX_LEVELS, &A.out_cnt));
   A.cells = *d_cells; A.cell_cnt = *d_cnt;
   A.fx = fx; A.fy = fy; A.fr = fr; A.kx = kx; A.ky = ky; A.kr = kr;
   return LORB_OK;
@@ -1753,13 +1755,13 @@ int lorb_orb_describe(lorb_ctx* ctx, const lorb_image_pyramid* pyr, int32_t n, c
   float *dx, *dy, *dang;
   int *dl, *dp;
   uint8_t* ddesc;
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 1, pyr->data, (size_t)pyr_extent(pyr), &dd));
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 2, x, (size_t)n, &dx));
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 3, y, (size_t)n, &dy));
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 4, level, (size_t)n, &dl));
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 5, pattern, (size_t)1024, &dp));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 6, (size_t)std::max(n, 1), &dang));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 7, (size_t)std::max(n, 1) * 32, &ddesc));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 1>(), pyr->data, (size_t)pyr_extent(pyr), &dd));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 2>(), x, (size_t)n, &dx));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 3>(), y, (size_t)n, &dy));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 4>(), level, (size_t)n, &dl));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 5>(), pattern, (size_t)1024, &dp));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 6>(), (size_t)std::max(n, 1), &dang));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 7>(), (size_t)std::max(n, 1) * 32, &ddesc));
   LORB_TRY(enqueue_orb(ctx, pyr, dd, n, nullptr, dx, dy, dl, dp, dang, ddesc));
   if (n > 0) {
     LORB_HIP(ctx, hipMemcpyAsync(angle, dang, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1783,8 +1785,8 @@ int lorb_orb_pyramid(lorb_ctx* ctx, const uint8_t* image, int32_t rows, int32_t 
   if (out_bytes < need) return lorb::set_error(ctx, LORB_E_INVALID, "out holds %lld bytes, %lld needed",
                                                (long long)out_bytes, (long long)need);
   uint8_t *dimg, *dout;
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 16, image, (size_t)(rows - 1) * step + cols, &dimg));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 17, (size_t)need, &dout));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 16>(), image, (size_t)(rows - 1) * step + cols, &dimg));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 17>(), (size_t)need, &dout));
   LORB_TRY(enqueue_pyramid(ctx, dimg, rows, cols, step, *layout, dout));
   LORB_HIP(ctx, hipMemcpyAsync(out, dout, (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
   LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1838,7 +1840,7 @@ int lorb_orb_fast_cells(lorb_ctx* ctx, const lorb_image_pyramid* pyr, int32_t in
   int* dcnt;
   uint8_t* dd;
   LORB_TRY(orb_alloc(ctx, &P, &dcells, &dcnt));
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 1, pyr->data, (size_t)pyr_extent(pyr), &dd));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 1>(), pyr->data, (size_t)pyr_extent(pyr), &dd));
   OrbPyr Q{};
   for (int l = 0; l < pyr->n_levels; l++) { Q.offset[l] = pyr->offset[l]; Q.step[l] = pyr->step[l]; }
   if (!P.cells.empty())
@@ -1898,20 +1900,20 @@ int lorb_orb_detect(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const int32_t*
   OrbPlan P;
   LORB_TRY(orb_plan(ctx, pyr, n_desired, scale_factors, &P));
   uint8_t* dd;
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 1, pyr->data, (size_t)pyr_extent(pyr), &dd));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 1>(), pyr->data, (size_t)pyr_extent(pyr), &dd));
   LORB_TRY(enqueue_keypoints(ctx, pyr, dd, &P, ini_th, min_th));
   const size_t cap = (size_t)std::max(P.out_cap, 1);
   float *lx, *ly, *sx, *sy, *sz, *rs;
   int *oc, *lo, *nt;
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 44, cap, &lx));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 45, cap, &ly));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 46, cap, &sx));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 47, cap, &sy));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 6, cap, &sz));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 7, cap, &rs));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 3, cap, &oc));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 4, (size_t)LORB_MAX_LEVELS + 1, &lo));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 5, (size_t)1, &nt));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 44>(), cap, &lx));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 45>(), cap, &ly));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 46>(), cap, &sx));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 47>(), cap, &sy));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 6>(), cap, &sz));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 7>(), cap, &rs));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 3>(), cap, &oc));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 4>(), (size_t)LORB_MAX_LEVELS + 1, &lo));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 5>(), (size_t)1, &nt));
   hipLaunchKernelGGL(k_orb_gather, dim3(lorb::ceil_div(cap, 256)), dim3(256), 0, ctx->stream, P.A, (int)cap, lx, ly, sx,
                      sy, oc, sz, rs, lo, nt);
   LORB_CHECK_LAUNCH(ctx);
@@ -1945,8 +1947,8 @@ int lorb_orb_debug_octree(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const in
   LORB_TRY(orb_plan(ctx, pyr, n_desired, scale_factors, &P));
   uint8_t* dd;
   int* dtr;
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 1, pyr->data, (size_t)pyr_extent(pyr), &dd));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 50, (size_t)pyr->n_levels * (64 * 72 + 16384), &dtr));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 1>(), pyr->data, (size_t)pyr_extent(pyr), &dd));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 50>(), (size_t)pyr->n_levels * (64 * 72 + 16384), &dtr));
   LORB_HIP(ctx, hipMemsetAsync(dtr, 0, sizeof(int) * pyr->n_levels * (64 * 72 + 16384), ctx->stream));
   P.A.trace = dtr;
   LORB_TRY(enqueue_keypoints(ctx, pyr, dd, &P, ini_th, min_th));
@@ -2005,8 +2007,8 @@ int lorb_orb_extract_dev(lorb_ctx* ctx, const uint8_t* d_image, int32_t rows, in
   hipLaunchKernelGGL(k_orb_octree, dim3(n_levels), dim3(kOctThreads), 0, ctx->stream, P.A);
   const size_t cap = (size_t)P.out_cap;
   float *lx, *ly;
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 44, cap, &lx));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 45, cap, &ly));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 44>(), cap, &lx));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 45>(), cap, &ly));
   hipLaunchKernelGGL(k_orb_gather, dim3(lorb::ceil_div(cap, 256)), dim3(256), 0, ctx->stream, P.A, (int)cap, lx, ly, d_x,
                      d_y, d_octave, d_size, d_response, d_level_off, d_n);
   LORB_CHECK_LAUNCH(ctx);
@@ -2027,18 +2029,18 @@ int lorb_orb_extract(lorb_ctx* ctx, const uint8_t* image, int32_t rows, int32_t 
   uint8_t *dimg, *dpyr, *ddesc;
   int32_t *dpat, *doct, *dlo, *dn;
   float *dx, *dy, *dsz, *dang, *drs;
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 16, image, (size_t)(rows - 1) * step + cols, &dimg));
-  LORB_TRY(lorb::upload_t(ctx, S_ORB + 19, pattern, (size_t)1024, &dpat));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 17, (size_t)pb, &dpyr));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 48, (size_t)cap, &dx));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 49, (size_t)cap, &dy));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 2, (size_t)cap, &doct));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 6, (size_t)cap, &dsz));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 7, (size_t)cap, &dang));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 3, (size_t)cap, &drs));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 18, (size_t)cap * 32, &ddesc));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 4, (size_t)LORB_MAX_LEVELS + 1, &dlo));
-  LORB_TRY(lorb::scratch_t(ctx, S_ORB + 5, (size_t)1, &dn));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 16>(), image, (size_t)(rows - 1) * step + cols, &dimg));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 19>(), pattern, (size_t)1024, &dpat));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 17>(), (size_t)pb, &dpyr));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 48>(), (size_t)cap, &dx));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 49>(), (size_t)cap, &dy));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 2>(), (size_t)cap, &doct));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 6>(), (size_t)cap, &dsz));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 7>(), (size_t)cap, &dang));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 3>(), (size_t)cap, &drs));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 18>(), (size_t)cap * 32, &ddesc));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 4>(), (size_t)LORB_MAX_LEVELS + 1, &dlo));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 5>(), (size_t)1, &dn));
   LORB_TRY(lorb_orb_extract_dev(ctx, dimg, rows, cols, step, n_levels, scale_factors, n_desired, ini_th, min_th, dpat, cap,
                                 dpyr, pb, dx, dy, doct, dsz, dang, drs, ddesc, dlo, dn));
   int n = 0;

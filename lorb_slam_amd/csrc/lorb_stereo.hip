@@ -335,8 +335,6 @@ int64_t pyr_bytes(const lorb_image_pyramid* p) {
   return e;
 }
 
-enum { S_ST = 48 };  // scratch slots S_ST .. S_ST+15
-
 int enqueue_stereo(lorb_ctx* ctx, const lorb_frame_params* fp, const Keys& L, const Keys& R, const Pyr& PL,
                    const Pyr& PR, float* d_ur, float* d_dp) {
   const int nRows = PL.rows[0];
@@ -349,9 +347,9 @@ int enqueue_stereo(lorb_ctx* ctx, const lorb_frame_params* fp, const Keys& L, co
   float rmax = 0;
   for (int l = 0; l < fp->n_levels; l++) rmax = std::max(rmax, 2.0f * fp->scale_factors[l]);
   const size_t per = (size_t)(2.0f * rmax) + 3;
-  LORB_TRY(lorb::scratch_t(ctx, S_ST + 0, (size_t)nRows + 1, &row_off));
-  LORB_TRY(lorb::scratch_t(ctx, S_ST + 1, std::max<size_t>((size_t)R.n * per, 1), &row_list));
-  LORB_TRY(lorb::scratch_t(ctx, S_ST + 2, std::max<size_t>((size_t)L.n, 1), &sad));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ST, 0>(), (size_t)nRows + 1, &row_off));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ST, 1>(), std::max<size_t>((size_t)R.n * per, 1), &row_list));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ST, 2>(), std::max<size_t>((size_t)L.n, 1), &sad));
   const int* no_counts = nullptr;
   hipLaunchKernelGGL((k_st_rows<false>), dim3(1), dim3(1024), 0, ctx->stream, R, no_counts, S, fp->n_levels, nRows,
                      row_off, row_list);
@@ -404,22 +402,22 @@ int lorb_compute_stereo_matches(lorb_ctx* ctx, const lorb_frame_params* frame, c
   Keys L{}, R{};
   L.n = nL; R.n = nR;
   uint8_t *dl, *dr;
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 3, left->x, nL, const_cast<float**>(&L.x)));
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 4, left->y, nL, const_cast<float**>(&L.y)));
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 5, left->octave, nL, const_cast<int**>(&L.octave)));
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 6, left->desc, (size_t)nL * 32, &dl));
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 7, right->x, nR, const_cast<float**>(&R.x)));
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 8, right->y, nR, const_cast<float**>(&R.y)));
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 9, right->octave, nR, const_cast<int**>(&R.octave)));
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 10, right->desc, (size_t)nR * 32, &dr));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 3>(), left->x, nL, const_cast<float**>(&L.x)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 4>(), left->y, nL, const_cast<float**>(&L.y)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 5>(), left->octave, nL, const_cast<int**>(&L.octave)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 6>(), left->desc, (size_t)nL * 32, &dl));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 7>(), right->x, nR, const_cast<float**>(&R.x)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 8>(), right->y, nR, const_cast<float**>(&R.y)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 9>(), right->octave, nR, const_cast<int**>(&R.octave)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 10>(), right->desc, (size_t)nR * 32, &dr));
   L.desc = reinterpret_cast<const uint4*>(dl);
   R.desc = reinterpret_cast<const uint4*>(dr);
   uint8_t *pl, *pr;
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 11, left_pyr->data, (size_t)pyr_bytes(left_pyr), &pl));
-  LORB_TRY(lorb::upload_t(ctx, S_ST + 12, right_pyr->data, (size_t)pyr_bytes(right_pyr), &pr));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 11>(), left_pyr->data, (size_t)pyr_bytes(left_pyr), &pl));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ST, 12>(), right_pyr->data, (size_t)pyr_bytes(right_pyr), &pr));
   float *dur, *ddp;
-  LORB_TRY(lorb::scratch_t(ctx, S_ST + 13, (size_t)nL, &dur));
-  LORB_TRY(lorb::scratch_t(ctx, S_ST + 14, (size_t)nL, &ddp));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ST, 13>(), (size_t)nL, &dur));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ST, 14>(), (size_t)nL, &ddp));
   LORB_TRY(enqueue_stereo(ctx, frame, L, R, pyr_of(left_pyr, pl), pyr_of(right_pyr, pr), dur, ddp));
   LORB_HIP(ctx, hipMemcpyAsync(u_right, dur, sizeof(float) * nL, hipMemcpyDeviceToHost, ctx->stream));
   LORB_HIP(ctx, hipMemcpyAsync(depth, ddp, sizeof(float) * nL, hipMemcpyDeviceToHost, ctx->stream));

@@ -824,20 +824,24 @@ void kps_add(lorb::InPack& in, const lorb_keypoints* k, const uint8_t* slot_stat
   if (!slot_state && pack_empty) { p.zeros.assign(n, 0); slot_state = p.zeros.data(); }
   p.ss = in.add_t(slot_state, n);
 }
-// grid = false: the candidate kernel builds the grid in its own LDS (k_cand_*<., true>)
-int kps_finish(lorb_ctx* ctx, const lorb::InPack& in, const KpParts& p, int n, int slot0, KpDev* K,
-               const lorb_frame_params* fp, bool grid = true) {
-  const float* x = in.dev<float>(p.x);
-  const float* y = in.dev<float>(p.y);
-  K->x = x; K->y = y; K->angle = in.dev<float>(p.ang); K->uR = in.dev<float>(p.ur); K->octave = in.dev<int>(p.oc);
-  K->desc = in.dev<const uint4>(p.desc); K->slot_state = in.dev<uint8_t>(p.ss);
-  K->cell_off = nullptr; K->cell_idx = nullptr; K->n = n;
-  if (!grid) return LORB_OK;
+// the committed pack's keypoints, without a grid: the search builds one where it needs it (search_issue)
+KpDev kps_finish(const lorb::InPack& in, const KpParts& p, int n) {
+  KpDev K;
+  K.x = in.dev<float>(p.x); K.y = in.dev<float>(p.y); K.angle = in.dev<float>(p.ang); K.uR = in.dev<float>(p.ur);
+  K.octave = in.dev<int>(p.oc); K.desc = in.dev<const uint4>(p.desc); K.slot_state = in.dev<uint8_t>(p.ss);
+  K.cell_off = nullptr; K.cell_idx = nullptr; K.n = n;
+  return K;
+}
+// The keypoint grid of a frame (src/frame.cpp:87-115) for a *K that has none yet: the one place that
+// launches k_grid_build.  A second search over the same *K reuses the grid.
+int ensure_grid(lorb_ctx* ctx, KpDev* K, const lorb_frame_params& fp) {
+  if (K->cell_off) return LORB_OK;
+  const size_t n = (size_t)std::max(K->n, 1);
   int *cell_off, *cell_idx, *kp_cell;
-  LORB_TRY(lorb::scratch_t(ctx, slot0 + 7, kCells + 1, &cell_off));
-  LORB_TRY(lorb::scratch_t(ctx, slot0 + 8, (size_t)std::max(n, 1), &cell_idx));
-  LORB_TRY(lorb::scratch_t(ctx, slot0 + 9, (size_t)std::max(n, 1), &kp_cell));
-  hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(1024), 0, ctx->stream, x, y, n, *fp, cell_off, cell_idx, kp_cell);
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_KP, 7>(), kCells + 1, &cell_off));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_KP, 8>(), n, &cell_idx));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_KP, 9>(), n, &kp_cell));
+  hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(1024), 0, ctx->stream, K->x, K->y, K->n, fp, cell_off, cell_idx, kp_cell);
   LORB_CHECK_LAUNCH(ctx);
   K->cell_off = cell_off; K->cell_idx = cell_idx;
   return LORB_OK;
@@ -911,69 +915,102 @@ int empty_slots(lorb_ctx* ctx, int n, const uint8_t** out) {
   return LORB_OK;
 }
 
-// The launches of one a4 pass on device-resident inputs, shared by the host-array call, the
-// device-pointer call and the motion chain: the keypoint grid where the candidate kernel does not
-// build its own (once per *K: a second pass over the same keypoints reuses it), the candidate lists
-// (one strided pass up to kCandStrided entries, else count / scan / write), the resolver.  dassign
-// (nk ints) and dnm get the codes and the count; out (or null) is the mapped result block of a
-// host-array call.  skip_unless: a predicated pass, whose kernels return at once unless
-// *skip_unless <= skip_max.  The working buffers (S_WX, S_W9) are the same for every pass.
-int a4_issue(lorb_ctx* ctx, KpDev* K, const WinParams& P, const LastDev& L, int* dassign, int* dnm, int* out,
-             const int* skip_unless = nullptr, int skip_max = 0) {
-  const int nk = K->n, nl = L.n;
+// The launches of one projection search (MODE 1: a4, MODE 0: a5) on device-resident inputs, shared
+// by every caller: the keypoint grid where the candidate kernel does not build its own (once per *K),
+// the candidate lists of the nq queries (one strided pass up to kCandStrided entries, else count /
+// scan / write), the resolver.  What differs per search is `launch`: called as launch(CandPass<WRITE,
+// GRID>, workgroups, cnt, off, cand, stride), it launches that instantiation of its candidate kernel.
+// The working buffers (S_WX, S_W9) are the same for every search.
+template <bool WRITE, bool GRID>
+struct CandPass {
+  static constexpr bool write = WRITE, grid = GRID;
+};
+struct SearchOut {
+  int *assign, *nmatches;  // the nk codes and the count
+  int* out;                // or null: the mapped result block of a host-array call (nk + 1 ints)
+  const int* skip_unless;  // or null: a predicated search, whose kernels return at once unless
+  int skip_max;            // *skip_unless <= skip_max
+};
+template <int MODE, typename Launch>
+int search_issue(lorb_ctx* ctx, KpDev* K, const lorb_frame_params& fp, int nq, const uint8_t* locked,
+                 const float* last_angle, const SearchOut& o, Launch&& launch) {
+  const int nk = K->n;
   // a query has at most nk candidates: up to kCandStrided entries one pass writes them at i * nk
   // (no count pass, no scan); past it the count / scan / write passes size the list exactly
-  const bool strided = (size_t)nl * (size_t)nk <= kCandStrided;
+  const bool strided = (size_t)nq * (size_t)nk <= kCandStrided;
   const bool lds_grid = strided && nk <= kStageKps;  // the candidate kernel builds the grid itself
-  if (!lds_grid && !K->cell_off) {
-    int *cell_off, *cell_idx, *kp_cell;
-    LORB_TRY(lorb::scratch_t(ctx, S_KP + 7, kCells + 1, &cell_off));
-    LORB_TRY(lorb::scratch_t(ctx, S_KP + 8, (size_t)std::max(nk, 1), &cell_idx));
-    LORB_TRY(lorb::scratch_t(ctx, S_KP + 9, (size_t)std::max(nk, 1), &kp_cell));
-    hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(1024), 0, ctx->stream, K->x, K->y, nk, P.fp, cell_off, cell_idx, kp_cell);
-    LORB_CHECK_LAUNCH(ctx);
-    K->cell_off = cell_off; K->cell_idx = cell_idx;
+  if (!lds_grid) LORB_TRY(ensure_grid(ctx, K, fp));
+  int *cnt, *off, *res, *claim, *bins = nullptr, *nulls = nullptr;
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 0>(), (size_t)nq + 1, &cnt));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 1>(), (size_t)nq + 1, &off));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 2>(), (size_t)nq + 1, &res));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 3>(), (size_t)nk + 1, &claim));
+  if constexpr (MODE == 1) {  // the rotation histogram
+    LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 5>(), (size_t)nq + 1, &bins));
+    LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 6>(), (size_t)nk + 1, &nulls));
   }
-  int *cnt, *off, *res, *claim, *bins, *nulls;
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 0, (size_t)nl + 1, &cnt));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 1, (size_t)nl + 1, &off));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 2, (size_t)nl + 1, &res));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 3, (size_t)nk + 1, &claim));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 5, (size_t)nl + 1, &bins));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 6, (size_t)nk + 1, &nulls));
-  const unsigned g = lorb::ceil_div(std::max(nl, 1), kCandWaves);
+  const unsigned g = lorb::ceil_div(std::max(nq, 1), kCandWaves);
   int2* cand;
   if (strided) {
-    LORB_TRY(lorb::scratch_t(ctx, S_W9, std::max<size_t>((size_t)nl * nk, 1), &cand));
-    if (nl > 0) {
+    LORB_TRY(lorb::scratch_t(ctx, S_W9, std::max<size_t>((size_t)nq * nk, 1), &cand));
+    if (nq > 0) {
       lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
-      if (lds_grid)
-        hipLaunchKernelGGL((k_cand_frame<true, true>), dim3(g), dim3(256), 0, ctx->stream, *K, P, nl, L.hm, L.ol, L.pos,
-                           L.lo, L.ld, cnt, (const int*)nullptr, cand, nk, skip_unless, skip_max);
-      else
-        hipLaunchKernelGGL(k_cand_frame<true>, dim3(g), dim3(256), 0, ctx->stream, *K, P, nl, L.hm, L.ol, L.pos, L.lo,
-                           L.ld, cnt, (const int*)nullptr, cand, nk, skip_unless, skip_max);
+      if (lds_grid) launch(CandPass<true, true>{}, g, cnt, (const int*)nullptr, cand, nk);
+      else launch(CandPass<true, false>{}, g, cnt, (const int*)nullptr, cand, nk);
     }
   } else {
-    if (nl > 0) {
+    if (nq > 0) {
       lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
-      hipLaunchKernelGGL(k_cand_frame<false>, dim3(g), dim3(256), 0, ctx->stream, *K, P, nl, L.hm, L.ol, L.pos, L.lo,
-                         L.ld, cnt, (const int*)nullptr, (int2*)nullptr, 0, skip_unless, skip_max);
+      launch(CandPass<false, false>{}, g, cnt, (const int*)nullptr, (int2*)nullptr, 0);
     }
     // a skipped pass leaves cnt as the pass before wrote it: the scan then sizes a list nobody fills
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, nl, off);
-    LORB_TRY(alloc_candidates(ctx, off + nl, (size_t)nl * (size_t)nk, &cand));
-    if (nl > 0)
-      hipLaunchKernelGGL(k_cand_frame<true>, dim3(g), dim3(256), 0, ctx->stream, *K, P, nl, L.hm, L.ol, L.pos, L.lo,
-                         L.ld, cnt, off, cand, 0, skip_unless, skip_max);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, nq, off);
+    LORB_TRY(alloc_candidates(ctx, off + nq, (size_t)nq * (size_t)nk, &cand));
+    if (nq > 0) launch(CandPass<true, false>{}, g, cnt, (const int*)off, cand, 0);
   }
   size_t rlds = 0;
-  const int rmode = resolve_lds_mode(nl, nk, &rlds);
-  hipLaunchKernelGGL(k_resolve<1>, dim3(1), dim3(1024), rlds, ctx->stream, nl, nk,
-                     strided ? (const int*)cnt : (const int*)off, cand, L.lk, L.la, K->angle, res, claim, dassign, bins,
-                     nulls, dnm, rmode, strided ? nk : 0, out, skip_unless, skip_max);
+  const int rmode = resolve_lds_mode(nq, nk, &rlds);
+  hipLaunchKernelGGL(k_resolve<MODE>, dim3(1), dim3(1024), rlds, ctx->stream, nq, nk,
+                     strided ? (const int*)cnt : (const int*)off, cand, locked, last_angle,
+                     MODE == 1 ? K->angle : (const float*)nullptr, res, claim, o.assign, bins, nulls, o.nmatches, rmode,
+                     strided ? nk : 0, o.out, o.skip_unless, o.skip_max);
   LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
+}
+
+// a4 on device-resident inputs, for the host-array call, the device-pointer call and the motion
+// chain (whose second pass over the same *K is predicated on the first's count)
+int a4_issue(lorb_ctx* ctx, KpDev* K, const WinParams& P, const LastDev& L, int* dassign, int* dnm, int* out,
+             const int* skip_unless = nullptr, int skip_max = 0) {
+  return search_issue<1>(ctx, K, P.fp, L.n, L.lk, L.la, {dassign, dnm, out, skip_unless, skip_max},
+                         [&](auto pass, unsigned g, int* cnt, const int* off, int2* cand, int stride) {
+                           using Pass = decltype(pass);
+                           hipLaunchKernelGGL((k_cand_frame<Pass::write, Pass::grid>), dim3(g), dim3(256), 0, ctx->stream,
+                                              *K, P, L.n, L.hm, L.ol, L.pos, L.lo, L.ld, cnt, off, cand, stride,
+                                              skip_unless, skip_max);
+                         });
+}
+
+struct LocalDev {  // a5's queries on the device: lorb_local_points' arrays, or a8's output
+  int n;
+  const uint8_t *iv, *bad, *lk;
+  const float *px, *py, *pxr, *vc;
+  const int* pl;
+  const uint4* pd;
+};
+template <bool WRITE, bool GRID>
+void launch_cand_local(lorb_ctx* ctx, unsigned g, const KpDev& K, const WinParams& P, const LocalDev& Q, int* cnt,
+                       const int* off, int2* cand, int stride) {
+  hipLaunchKernelGGL((k_cand_local<WRITE, GRID>), dim3(g), dim3(256), 0, ctx->stream, K, P, Q.n, Q.iv, Q.bad, Q.px, Q.py,
+                     Q.pxr, Q.pl, Q.vc, Q.pd, cnt, off, cand, stride);
+}
+// a5 on device-resident inputs, for the host-array call and lorb_track_local_map_dev
+int a5_issue(lorb_ctx* ctx, KpDev* K, const WinParams& P, const LocalDev& Q, int* dassign, int* dnm, int* out) {
+  return search_issue<0>(ctx, K, P.fp, Q.n, Q.lk, nullptr, {dassign, dnm, out, nullptr, 0},
+                         [&](auto pass, unsigned g, int* cnt, const int* off, int2* cand, int stride) {
+                           using Pass = decltype(pass);
+                           launch_cand_local<Pass::write, Pass::grid>(ctx, g, *K, P, Q, cnt, off, cand, stride);
+                         });
 }
 
 }  // namespace
@@ -1000,59 +1037,19 @@ int lorb_search_by_projection_local(lorb_ctx* ctx, const lorb_frame_params* fram
             i_pl = in.add_t(pts->pred_level, np), i_vc = in.add_t(pts->view_cos, np),
             i_pd = in.add_t(pts->desc, (size_t)np * 32);
   LORB_TRY(in.commit());
-  const bool strided = (size_t)np * (size_t)nk <= kCandStrided;  // as lorb_search_by_projection_frame
-  const bool lds_grid = strided && nk <= kStageKps;  // the candidate kernel builds the grid itself
-  KpDev K;
-  LORB_TRY(kps_finish(ctx, in, kp, nk, S_KP, &K, frame, !lds_grid));
-  const uint8_t *iv = in.dev<uint8_t>(i_iv), *bad = in.dev<uint8_t>(i_bad), *lk = in.dev<uint8_t>(i_lk);
-  const float *px = in.dev<float>(i_px), *py = in.dev<float>(i_py), *pxr = in.dev<float>(i_pxr), *vc = in.dev<float>(i_vc);
-  const int* pl = in.dev<int>(i_pl);
-  const uint8_t* pd = in.dev<uint8_t>(i_pd);
+  KpDev K = kps_finish(in, kp, nk);
+  const LocalDev Q = {np, in.dev<uint8_t>(i_iv), in.dev<uint8_t>(i_bad), in.dev<uint8_t>(i_lk), in.dev<float>(i_px),
+                      in.dev<float>(i_py), in.dev<float>(i_pxr), in.dev<float>(i_vc), in.dev<int>(i_pl),
+                      in.dev<const uint4>(i_pd)};
   WinParams P{};
   P.fp = *frame;
   P.th = th;
-  int *cnt, *off, *res, *claim, *dassign, *dnm;
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 0, (size_t)np + 1, &cnt));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 1, (size_t)np + 1, &off));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 2, (size_t)np + 1, &res));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 3, (size_t)nk + 1, &claim));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 4, (size_t)nk + 1, &dassign));
-  dnm = dassign + nk;
+  int* dassign;
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 4>(), (size_t)nk + 1, &dassign));
   lorb::OutPack out(ctx);
   const int o_as = out.add(sizeof(int) * ((size_t)nk + 1));
   LORB_TRY(out.alloc(true));  // k_resolve writes assign + count into the mapped block
-  const unsigned g = lorb::ceil_div(std::max(np, 1), kCandWaves);
-  int2* cand;
-  if (strided) {
-    LORB_TRY(lorb::scratch_t(ctx, S_W9, std::max<size_t>((size_t)np * nk, 1), &cand));
-    if (np > 0) {
-      lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
-      if (lds_grid)
-        hipLaunchKernelGGL((k_cand_local<true, true>), dim3(g), dim3(256), 0, ctx->stream, K, P, np, iv, bad, px, py, pxr,
-                           pl, vc, reinterpret_cast<const uint4*>(pd), cnt, (const int*)nullptr, cand, nk);
-      else
-        hipLaunchKernelGGL(k_cand_local<true>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, iv, bad, px, py, pxr, pl,
-                           vc, reinterpret_cast<const uint4*>(pd), cnt, (const int*)nullptr, cand, nk);
-    }
-  } else {
-    if (np > 0) {
-      lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
-      hipLaunchKernelGGL(k_cand_local<false>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, iv, bad, px, py, pxr, pl, vc,
-                         reinterpret_cast<const uint4*>(pd), cnt, (const int*)nullptr, (int2*)nullptr, 0);
-    }
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, np, off);
-    LORB_TRY(alloc_candidates(ctx, off + np, (size_t)np * (size_t)nk, &cand));
-    if (np > 0)
-      hipLaunchKernelGGL(k_cand_local<true>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, iv, bad, px, py, pxr, pl, vc,
-                         reinterpret_cast<const uint4*>(pd), cnt, off, cand, 0);
-  }
-  size_t rlds = 0;
-  const int rmode = resolve_lds_mode(np, nk, &rlds);
-  hipLaunchKernelGGL(k_resolve<0>, dim3(1), dim3(1024), rlds, ctx->stream, np, nk,
-                     strided ? (const int*)cnt : (const int*)off, cand, lk,
-                     (const float*)nullptr, (const float*)nullptr, res, claim, dassign, (int*)nullptr, (int*)nullptr, dnm,
-                     rmode, strided ? nk : 0, out.dev<int>(o_as));
-  LORB_CHECK_LAUNCH(ctx);
+  LORB_TRY(a5_issue(ctx, &K, P, Q, dassign, dassign + nk, out.dev<int>(o_as)));
   LORB_TRY(out.fetch());
   memcpy(assign, out.host<int>(o_as), sizeof(int) * nk);
   *nmatches = out.host<int>(o_as)[nk];
@@ -1078,12 +1075,11 @@ int lorb_search_by_projection_frame(lorb_ctx* ctx, const lorb_frame_params* cur,
             i_pos = in.add_t(last->mp_pos, (size_t)nl * 3), i_ld = in.add_t(last->mp_desc, (size_t)nl * 32),
             i_lo = in.add_t(last->octave, nl), i_la = in.add_t(last->angle, nl);
   LORB_TRY(in.commit());
-  KpDev K;
-  LORB_TRY(kps_finish(ctx, in, kp, nk, S_KP, &K, cur, false));  // a4_issue builds the grid where it needs one
+  KpDev K = kps_finish(in, kp, nk);
   const LastDev L = {nl, in.dev<uint8_t>(i_hm), in.dev<uint8_t>(i_ol), in.dev<uint8_t>(i_lk), in.dev<float>(i_pos),
                      in.dev<float>(i_la), in.dev<int>(i_lo), in.dev<const uint4>(i_ld)};
   int* dassign;
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 4, (size_t)nk + 1, &dassign));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 4>(), (size_t)nk + 1, &dassign));
   lorb::OutPack out(ctx);
   const int o_as = out.add(sizeof(int) * ((size_t)nk + 1));
   LORB_TRY(out.alloc(true));  // k_resolve writes assign + count into the mapped block
@@ -1126,8 +1122,8 @@ static int track_motion_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const
   const int nk = K.n;
   int* tm;  // pass 2's codes (nk) | its count | pass 1's count
   float* list;
-  LORB_TRY(lorb::scratch_t(ctx, S_TM + 0, (size_t)nk + 2, &tm));
-  LORB_TRY(lorb::scratch_t(ctx, S_TM + 1, (size_t)std::max(nk, 1) * 5, &list));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TM, 0>(), (size_t)nk + 2, &tm));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TM, 1>(), (size_t)std::max(nk, 1) * 5, &list));
   int *nm2 = tm + nk, *nm1 = tm + nk + 1;
   const uint8_t* given = K.slot_state;
   if (nk == 0) {
@@ -1187,13 +1183,12 @@ int lorb_track_motion(lorb_ctx* ctx, const lorb_frame_params* cur, const float c
             i_pos = in.add_t(last->mp_pos, (size_t)nl * 3), i_ld = in.add_t(last->mp_desc, (size_t)nl * 32),
             i_lo = in.add_t(last->octave, nl), i_la = in.add_t(last->angle, nl);
   LORB_TRY(in.commit());
-  KpDev K;
-  LORB_TRY(kps_finish(ctx, in, kp, nk, S_KP, &K, cur, false));  // a4_issue builds the grid where it needs one
+  KpDev K = kps_finish(in, kp, nk);
   if (!slot_state) K.slot_state = nullptr;  // all EMPTY: the chain reads its own zeroed buffer
   const LastDev L = {nl, in.dev<uint8_t>(i_hm), in.dev<uint8_t>(i_ol), in.dev<uint8_t>(i_lk), in.dev<float>(i_pos),
                      in.dev<float>(i_la), in.dev<int>(i_lo), in.dev<const uint4>(i_ld)};
   int* dassign;
-  LORB_TRY(lorb::scratch_t(ctx, S_TM + 2, (size_t)nk + 1, &dassign));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TM, 2>(), (size_t)nk + 1, &dassign));
   lorb::OutPack out(ctx);
   const int o_rec = out.add(sizeof(lorb_track_motion_result)), o_as = out.add(sizeof(int) * ((size_t)nk + 1));
   LORB_TRY(out.alloc(true));
@@ -1264,7 +1259,7 @@ int lorb_track_local_map_dev(lorb_ctx* ctx, const lorb_frame_params* frame, cons
   const float TO[19] = {Tcw[0], Tcw[1], Tcw[2], Tcw[3], Tcw[4], Tcw[5], Tcw[6], Tcw[7], Tcw[8], Tcw[9],
                         Tcw[10], Tcw[11], Tcw[12], Tcw[13], Tcw[14], Tcw[15], Twc[3], Twc[7], Twc[11]};
   float* dTO;
-  LORB_TRY(lorb::upload_t(ctx, S_WX + 7, TO, 19, &dTO));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_WX, 7>(), TO, 19, &dTO));
   if (np > 0)
     hipLaunchKernelGGL(k_frustum, dim3(lorb::ceil_div(np, 256)), dim3(256), 0, ctx->stream, *frame, dTO, dTO + 16, np,
                        pts->pos, pts->normal, pts->max_dist, pts->min_dist, viewing_cos_limit, d_in_view, d_track,
@@ -1274,52 +1269,15 @@ int lorb_track_local_map_dev(lorb_ctx* ctx, const lorb_frame_params* frame, cons
     LORB_CHECK_LAUNCH(ctx);
     return LORB_OK;
   }
-  // keypoint grid of the frame, from the device keypoints (src/frame.cpp:87-115)
-  KpDev K;
-  int *cell_off, *cell_idx, *kp_cell;
-  LORB_TRY(lorb::scratch_t(ctx, S_KP + 7, kCells + 1, &cell_off));
-  LORB_TRY(lorb::scratch_t(ctx, S_KP + 8, (size_t)nk, &cell_idx));
-  LORB_TRY(lorb::scratch_t(ctx, S_KP + 9, (size_t)nk, &kp_cell));
-  hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(1024), 0, ctx->stream, d_kps->x, d_kps->y, nk, *frame, cell_off, cell_idx,
-                     kp_cell);
-  uint8_t* ss = const_cast<uint8_t*>(d_slot_state);
-  if (!ss) {
-    LORB_TRY(lorb::scratch_t(ctx, S_KP + 6, (size_t)nk, &ss));
-    LORB_HIP(ctx, hipMemsetAsync(ss, 0, nk, ctx->stream));
-  }
-  K.x = d_kps->x; K.y = d_kps->y; K.angle = d_kps->angle; K.uR = d_kps->u_right; K.octave = d_kps->octave;
-  K.desc = reinterpret_cast<const uint4*>(d_kps->desc); K.slot_state = ss;
-  K.cell_off = cell_off; K.cell_idx = cell_idx; K.n = nk;
+  const uint8_t* ss = d_slot_state;
+  if (!ss) LORB_TRY(empty_slots(ctx, nk, &ss));
+  KpDev K = kp_dev(d_kps, ss);
   WinParams P{};
   P.fp = *frame;
   P.th = th;
-  int *cnt, *off, *res, *claim;
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 0, (size_t)np + 1, &cnt));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 1, (size_t)np + 1, &off));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 2, (size_t)np + 1, &res));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 3, (size_t)nk + 1, &claim));
-  const unsigned g = lorb::ceil_div(std::max(np, 1), kCandWaves);
-  const float* tx = d_track;
-  if (np > 0) {
-    lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
-    hipLaunchKernelGGL(k_cand_local<false>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, d_in_view, pts->is_bad, tx,
-                       tx + np, tx + 2 * np, d_level, tx + 3 * np, reinterpret_cast<const uint4*>(pts->desc), cnt,
-                       (const int*)nullptr, (int2*)nullptr);
-  }
-  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, np, off);
-  int2* cand;
-  LORB_TRY(alloc_candidates(ctx, off + np, (size_t)np * (size_t)nk, &cand));
-  if (np > 0)
-    hipLaunchKernelGGL(k_cand_local<true>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, d_in_view, pts->is_bad, tx,
-                       tx + np, tx + 2 * np, d_level, tx + 3 * np, reinterpret_cast<const uint4*>(pts->desc), cnt, off,
-                       cand);
-  size_t rlds = 0;
-  const int rmode = resolve_lds_mode(np, nk, &rlds);
-  hipLaunchKernelGGL(k_resolve<0>, dim3(1), dim3(1024), rlds, ctx->stream, np, nk, off, cand,
-                     pts->locked, (const float*)nullptr, (const float*)nullptr, res, claim, d_assign, (int*)nullptr,
-                     (int*)nullptr, d_nmatches, rmode);
-  LORB_CHECK_LAUNCH(ctx);
-  return LORB_OK;
+  const LocalDev Q = {np, d_in_view, pts->is_bad, pts->locked, d_track, d_track + np, d_track + 2 * np, d_track + 3 * np,
+                      d_level, reinterpret_cast<const uint4*>(pts->desc)};
+  return a5_issue(ctx, &K, P, Q, d_assign, d_nmatches, nullptr);
 }
 
 int lorb_track_local_map(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16], const lorb_keypoints* kps,
@@ -1332,35 +1290,34 @@ int lorb_track_local_map(lorb_ctx* ctx, const lorb_frame_params* frame, const fl
                   !pts->desc || !pts->locked)) ||
       (nk > 0 && (!assign || !kps->x || !kps->y || !kps->octave || !kps->angle || !kps->desc)))
     return lorb::set_error(ctx, LORB_E_INVALID, "null array");
-  enum { S_TL = 64 };  // 64 .. 87: staging of this call
   lorb_keypoints K{};
   lorb_map_points_dev M{};
   K.n = nk; M.n = np;
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 0, kps->x, (size_t)nk, const_cast<float**>(&K.x)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 1, kps->y, (size_t)nk, const_cast<float**>(&K.y)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 2, kps->octave, (size_t)nk, const_cast<int32_t**>(&K.octave)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 3, kps->angle, (size_t)nk, const_cast<float**>(&K.angle)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 4, kps->u_right, kps->u_right ? (size_t)nk : 0, const_cast<float**>(&K.u_right)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 5, kps->desc, (size_t)nk * 32, const_cast<uint8_t**>(&K.desc)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 0>(), kps->x, (size_t)nk, const_cast<float**>(&K.x)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 1>(), kps->y, (size_t)nk, const_cast<float**>(&K.y)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 2>(), kps->octave, (size_t)nk, const_cast<int32_t**>(&K.octave)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 3>(), kps->angle, (size_t)nk, const_cast<float**>(&K.angle)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 4>(), kps->u_right, kps->u_right ? (size_t)nk : 0, const_cast<float**>(&K.u_right)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 5>(), kps->desc, (size_t)nk * 32, const_cast<uint8_t**>(&K.desc)));
   uint8_t* dss;
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 6, slot_state, slot_state ? (size_t)nk : 0, &dss));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 7, pts->pos, (size_t)np * 3, const_cast<float**>(&M.pos)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 8, pts->normal, (size_t)np * 3, const_cast<float**>(&M.normal)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 9, pts->max_dist, (size_t)np, const_cast<float**>(&M.max_dist)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 10, pts->min_dist, (size_t)np, const_cast<float**>(&M.min_dist)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 11, pts->desc, (size_t)np * 32, const_cast<uint8_t**>(&M.desc)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 12, pts->locked, (size_t)np, const_cast<uint8_t**>(&M.locked)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 13, pts->is_bad, pts->is_bad ? (size_t)np : 0, const_cast<uint8_t**>(&M.is_bad)));
-  LORB_TRY(lorb::upload_t(ctx, S_TL + 14, pts->in_frame, pts->in_frame ? (size_t)np : 0,
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 6>(), slot_state, slot_state ? (size_t)nk : 0, &dss));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 7>(), pts->pos, (size_t)np * 3, const_cast<float**>(&M.pos)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 8>(), pts->normal, (size_t)np * 3, const_cast<float**>(&M.normal)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 9>(), pts->max_dist, (size_t)np, const_cast<float**>(&M.max_dist)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 10>(), pts->min_dist, (size_t)np, const_cast<float**>(&M.min_dist)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 11>(), pts->desc, (size_t)np * 32, const_cast<uint8_t**>(&M.desc)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 12>(), pts->locked, (size_t)np, const_cast<uint8_t**>(&M.locked)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 13>(), pts->is_bad, pts->is_bad ? (size_t)np : 0, const_cast<uint8_t**>(&M.is_bad)));
+  LORB_TRY(lorb::upload_t(ctx, slot<S_TL, 14>(), pts->in_frame, pts->in_frame ? (size_t)np : 0,
                           const_cast<uint8_t**>(&M.in_frame)));
   uint8_t* div;
   float* dtr;
   int32_t *dlv, *das, *dnm;
-  LORB_TRY(lorb::scratch_t(ctx, S_TL + 15, (size_t)std::max(np, 1), &div));
-  LORB_TRY(lorb::scratch_t(ctx, S_TL + 16, (size_t)std::max(np, 1) * 4, &dtr));
-  LORB_TRY(lorb::scratch_t(ctx, S_TL + 17, (size_t)std::max(np, 1), &dlv));
-  LORB_TRY(lorb::scratch_t(ctx, S_TL + 18, (size_t)std::max(nk, 1), &das));
-  LORB_TRY(lorb::scratch_t(ctx, S_TL + 19, 1, &dnm));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TL, 15>(), (size_t)std::max(np, 1), &div));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TL, 16>(), (size_t)std::max(np, 1) * 4, &dtr));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TL, 17>(), (size_t)std::max(np, 1), &dlv));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TL, 18>(), (size_t)std::max(nk, 1), &das));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TL, 19>(), 1, &dnm));
   LORB_TRY(lorb_track_local_map_dev(ctx, frame, Tcw, &K, dss, &M, viewing_cos_limit, th, div, dtr, dlv, das, dnm));
   if (np > 0) {
     LORB_HIP(ctx, hipMemcpyAsync(in_view, div, (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
@@ -1386,8 +1343,8 @@ static int track_local_issue(lorb_ctx* ctx, const lorb_frame_params* frame, cons
   const int nk = K.n, np = pts->n;
   int* nm;
   float* list;
-  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 0, 1, &nm));
-  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 1, (size_t)std::max(nk, 1) * 5, &list));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLC, 0>(), 1, &nm));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLC, 1>(), (size_t)std::max(nk, 1) * 5, &list));
   const uint8_t* given = K.slot_state;
   FrustumIn F{};
   float Twc[16];
@@ -1401,63 +1358,32 @@ static int track_local_issue(lorb_ctx* ctx, const lorb_frame_params* frame, cons
   P.fp = *frame;
   P.th = par->th;
   const uint4* pdesc = reinterpret_cast<const uint4*>(pts->desc);
-  const unsigned g = lorb::ceil_div(std::max(np, 1), kCandWaves);
-  int *cnt, *off, *res, *claim;
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 0, (size_t)np + 1, &cnt));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 1, (size_t)np + 1, &off));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 2, (size_t)np + 1, &res));
-  LORB_TRY(lorb::scratch_t(ctx, S_WX + 3, (size_t)nk + 1, &claim));
   if (nk == 0) {
     // no keypoints: the fields are still computed (the count pass walks nothing), nothing matches
-    if (np > 0)
-      hipLaunchKernelGGL(k_cand_local_fr<false>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, F, o, mir, pdesc, cnt,
-                         (int2*)nullptr, 0);
+    if (np > 0) {
+      int* cnt;
+      LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 0>(), (size_t)np + 1, &cnt));
+      hipLaunchKernelGGL(k_cand_local_fr<false>, dim3(lorb::ceil_div(np, kCandWaves)), dim3(256), 0, ctx->stream, K, P, np,
+                         F, o, mir, pdesc, cnt, (int2*)nullptr, 0);
+    }
     LORB_HIP(ctx, hipMemsetAsync(nm, 0, sizeof(int), ctx->stream));
+    LORB_CHECK_LAUNCH(ctx);
   } else {
     if (!given) LORB_TRY(empty_slots(ctx, nk, &K.slot_state));
-    const bool strided = (size_t)np * (size_t)nk <= kCandStrided;  // as lorb_search_by_projection_local
-    const bool lds_grid = strided && nk <= kStageKps;              // the candidate kernel builds the grid itself
-    if (!lds_grid) {
-      int *cell_off, *cell_idx, *kp_cell;
-      LORB_TRY(lorb::scratch_t(ctx, S_KP + 7, kCells + 1, &cell_off));
-      LORB_TRY(lorb::scratch_t(ctx, S_KP + 8, (size_t)nk, &cell_idx));
-      LORB_TRY(lorb::scratch_t(ctx, S_KP + 9, (size_t)nk, &kp_cell));
-      hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(1024), 0, ctx->stream, K.x, K.y, nk, *frame, cell_off, cell_idx,
-                         kp_cell);
-      K.cell_off = cell_off; K.cell_idx = cell_idx;
-    }
-    int2* cand;
-    if (strided) {
-      LORB_TRY(lorb::scratch_t(ctx, S_W9, std::max<size_t>((size_t)np * nk, 1), &cand));
-      if (np > 0) {
-        lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
-        if (lds_grid)
-          hipLaunchKernelGGL((k_cand_local_fr<true, true>), dim3(g), dim3(256), 0, ctx->stream, K, P, np, F, o, mir, pdesc,
-                             cnt, cand, nk);
-        else
-          hipLaunchKernelGGL(k_cand_local_fr<true>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, F, o, mir, pdesc, cnt,
-                             cand, nk);
-      }
-    } else {  // np > 0
-      {
-        lorb::KernelTimer kt(ctx, LORB_K_WINDOW_CAND);
-        hipLaunchKernelGGL(k_cand_local_fr<false>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, F, o, mir, pdesc, cnt,
-                           (int2*)nullptr, 0);
-      }
-      hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, np, off);
-      LORB_TRY(alloc_candidates(ctx, off + np, (size_t)np * (size_t)nk, &cand));
-      const float* tx = o.track;
-      hipLaunchKernelGGL(k_cand_local<true>, dim3(g), dim3(256), 0, ctx->stream, K, P, np, o.in_view, pts->is_bad, tx,
-                         tx + np, tx + 2 * np, o.level, tx + 3 * np, pdesc, cnt, off, cand, 0);
-    }
-    size_t rlds = 0;
-    const int rmode = resolve_lds_mode(np, nk, &rlds);
-    hipLaunchKernelGGL(k_resolve<0>, dim3(1), dim3(1024), rlds, ctx->stream, np, nk,
-                       strided ? (const int*)cnt : (const int*)off, cand, pts->locked, (const float*)nullptr,
-                       (const float*)nullptr, res, claim, d_assign, (int*)nullptr, (int*)nullptr, nm, rmode,
-                       strided ? nk : 0);
+    // the fused kernel is the first candidate pass; the write pass of the count / scan / write
+    // sequence (off given) is k_cand_local reading the fields the count pass stored
+    const LocalDev Q = {np, o.in_view, pts->is_bad, pts->locked, o.track, o.track + np, o.track + 2 * np,
+                        o.track + 3 * np, o.level, pdesc};
+    LORB_TRY(search_issue<0>(ctx, &K, P.fp, np, pts->locked, nullptr, {d_assign, nm, nullptr, nullptr, 0},
+                             [&](auto pass, unsigned g, int* cnt, const int* off, int2* cand, int stride) {
+                               using Pass = decltype(pass);
+                               if (off)
+                                 launch_cand_local<true, false>(ctx, g, K, P, Q, cnt, off, cand, stride);
+                               else
+                                 hipLaunchKernelGGL((k_cand_local_fr<Pass::write, Pass::grid>), dim3(g), dim3(256), 0,
+                                                    ctx->stream, K, P, np, F, o, mir, pdesc, cnt, cand, stride);
+                             }));
   }
-  LORB_CHECK_LAUNCH(ctx);
   lorb::LocalTail t{};
   t.nk = nk; t.np = np; t.nm = nm; t.assign = d_assign; t.in_view = o.in_view;
   t.slot_state = given; t.slot_pos = slot_pos; t.pt_pos = pts->pos; t.x = K.x; t.y = K.y;
@@ -1517,8 +1443,7 @@ int lorb_track_local(lorb_ctx* ctx, const lorb_frame_params* frame, const float 
             i_pd = in.add_t(pts->desc, (size_t)np * 32), i_lk = in.add_t(pts->locked, np),
             i_bad = in.add_t(pts->is_bad, np), i_inf = in.add_t(pts->in_frame, np);
   LORB_TRY(in.commit());
-  KpDev K;
-  LORB_TRY(kps_finish(ctx, in, kp, nk, S_KP, &K, frame, false));  // track_local_issue builds the grid where it needs one
+  const KpDev K = kps_finish(in, kp, nk);
   lorb_map_points_dev M{};
   M.n = np;
   M.pos = in.dev<float>(i_pos); M.normal = in.dev<float>(i_nrm); M.max_dist = in.dev<float>(i_mx);
@@ -1526,10 +1451,10 @@ int lorb_track_local(lorb_ctx* ctx, const lorb_frame_params* frame, const float 
   M.is_bad = in.dev<uint8_t>(i_bad); M.in_frame = in.dev<uint8_t>(i_inf);
   int* dassign;
   FieldsOut o;
-  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 2, (size_t)nk + 1, &dassign));
-  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 3, (size_t)std::max(np, 1), &o.in_view));
-  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 4, (size_t)std::max(np, 1) * 4, &o.track));
-  LORB_TRY(lorb::scratch_t(ctx, S_TLC + 5, (size_t)std::max(np, 1), &o.level));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLC, 2>(), (size_t)nk + 1, &dassign));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLC, 3>(), (size_t)std::max(np, 1), &o.in_view));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLC, 4>(), (size_t)std::max(np, 1) * 4, &o.track));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLC, 5>(), (size_t)std::max(np, 1), &o.level));
   lorb::OutPack out(ctx);
   const int o_rec = out.add(sizeof(lorb_track_local_result)), o_as = out.add(sizeof(int) * ((size_t)nk + 1)),
             o_iv = out.add((size_t)np + 1), o_tr = out.add(sizeof(float) * 4 * ((size_t)np + 1)),

@@ -251,3 +251,41 @@ def test_track_motion_host_form_identical(ctx, n_kps, n_shared, seed, dx):
         assert d[k] == h[k], k
     assert np.array_equal(d["pose"], h["pose"]) and np.array_equal(d["Tcw"], h["Tcw"])
     check(h, expected(s, dx, None, None))
+
+
+# 8 -- the context's all-EMPTY slot states survive an extractor call --------------------------------
+def orb_count_with_locked_byte(c):
+    """An orb_detect call whose level-0 keypoint count (512 .. 767) has LORB_SLOT_LOCKED as its second
+    byte.  Returns the keypoint indices such a byte would land on if the extractor's per-level counts
+    (int l at bytes 4 l ..) were written over slot states."""
+    nd = np.array(O.orb_features_per_level(1000))
+    nd[0] = 600
+    g = c.orb_detect(synth.orb_problem(seed=61, n_kps=1)["pyr"], nd, synth.scale_factors())
+    counts = np.diff(g["level_off"])
+    hit = [4 * l + b for l, n in enumerate(counts) for b in (0, 1) if (int(n) >> (8 * b)) & 255 == A.LORB_SLOT_LOCKED]
+    assert hit, counts
+    return hit
+
+
+@pytest.mark.parametrize("chain", ["motion", "local"])
+def test_empty_slot_states_survive_orb(chain):
+    """slot_state=None reads a zeroed buffer the context keeps from call to call: an extractor call in
+    between must not write it.  A context of its own: nothing an earlier test left can hide a fault."""
+    import test_gpu_track_local as TL
+    from lorb_slam_amd.runtime import Context
+    if chain == "motion":
+        s = frames(500, 200, 2)
+        e = expected(s, 0.0, None, None)
+        go = lambda c: check(run(c, s, 0.0, None, None), e)
+    else:
+        s = dict(TL.problem(40, 500, 2000, 300), slot_state=None, slot_pos=None)
+        e = TL.expected(s)
+        go = lambda c: TL.check(TL.run(c, s), e)
+    c = Context(0)
+    try:
+        go(c)
+        hit = orb_count_with_locked_byte(c)
+        assert any(e["assign"][j] >= 0 for j in hit), (hit, e["assign"][:32])  # a match a LOCKED byte there would remove
+        go(c)
+    finally:
+        c.close()

@@ -88,20 +88,35 @@ def test_unproject_stereo(ctx):
     assert np.array_equal(ctx.unproject_stereo(fp, T, x, y, d), O.unproject_stereo(fp, T, x, y, d))
 
 
+def _track_local_map_vs_oracle(ctx, pr, slot_state, cos_limit, th, min_view, min_nm):
+    g = ctx.track_local_map(pr["fp"], pr["Tcw"], pr["kps"], slot_state, pr["pts"], cos_limit, th)
+    fr, assign, nm = O.track_local_map(pr["fp"], pr["Tcw"], pr["kps"], slot_state, pr["pts"], cos_limit, th)
+    assert np.array_equal(g["in_view"], fr["in_view"])
+    m = fr["in_view"].astype(bool)
+    assert m.sum() > min_view
+    for k in ("proj_x", "proj_y", "proj_xr", "view_cos", "pred_level"):
+        assert np.array_equal(g[k][m], fr[k][m]), k
+    assert g["nmatches"] == nm and nm > min_nm
+    assert np.array_equal(g["assign"], assign)
+
+
 @pytest.mark.parametrize("seed,cos_limit,th", [(11, 0.5, 1.0), (12, 0.5, 3.0), (13, 0.8, 1.0)])
 def test_track_local_map(ctx, seed, cos_limit, th):
     """lorb_track_local_map_dev vs the oracle chain of EstimatePoseLocal
     (src/visual_odometry.cpp:173-201) -- tracking fields and assignments bit-exact."""
     pr = synth.local_map_problem(seed=seed, bad_frac=0.02)
-    g = ctx.track_local_map(pr["fp"], pr["Tcw"], pr["kps"], pr["slot_state"], pr["pts"], cos_limit, th)
-    fr, assign, nm = O.track_local_map(pr["fp"], pr["Tcw"], pr["kps"], pr["slot_state"], pr["pts"], cos_limit, th)
-    assert np.array_equal(g["in_view"], fr["in_view"])
-    m = fr["in_view"].astype(bool)
-    assert m.sum() > 500
-    for k in ("proj_x", "proj_y", "proj_xr", "view_cos", "pred_level"):
-        assert np.array_equal(g[k][m], fr[k][m]), k
-    assert g["nmatches"] == nm and nm > 100
-    assert np.array_equal(g["assign"], assign)
+    _track_local_map_vs_oracle(ctx, pr, pr["slot_state"], cos_limit, th, 500, 100)
+
+
+@pytest.mark.parametrize("with_slots", [True, False])
+@pytest.mark.parametrize("seed,n_kps,n_pts,n_true,min_view,min_nm", [
+    (15, 300, 400, 150, 100, 40),       # one strided candidate pass, the grid in the kernel's LDS
+    (16, 1100, 900, 400, 300, 150),     # nk > 1024: one strided pass over a grid built by a launch
+    (11, 2000, 3000, 1200, 500, 100)])  # np nk > 2^20: count / scan / write
+def test_track_local_map_paths(ctx, seed, n_kps, n_pts, n_true, min_view, min_nm, with_slots):
+    """The same on every path the search takes, with a slot-state array and with none (all EMPTY)."""
+    pr = synth.local_map_problem(seed=seed, n_kps=n_kps, n_pts=n_pts, n_true=n_true, bad_frac=0.02)
+    _track_local_map_vs_oracle(ctx, pr, pr["slot_state"] if with_slots else None, 0.5, 1.0, min_view, min_nm)
 
 
 def test_track_local_map_edges(ctx):

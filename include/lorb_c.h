@@ -743,7 +743,8 @@ int lorb_ctx_ba_solver(lorb_ctx* ctx, lorb_ba_solver** out);
  * caller's order), [8] 1: the point-major Schur path (the only one since round 6; point groups span
  * <= 128 cameras), [9] its partial-reduction width (threads per block: 256, 512 or 1024), [10] partial
  * runs of the last build (0: one partial per point group; else the runs of several groups that
- * k_ba_ls_sup folds into one partial each -- windows of more than 512 point groups) */
+ * k_ba_ls_sup folds into one partial each -- windows of more than 512 point groups), [11] kernel
+ * launches in the captured graph of the last solve (0: none captured) */
 int lorb_ba_plan_info(lorb_ba_plan* plan, int32_t* info, int32_t n);
 /* the last solve's per-iteration records of window w (at most min(cap, LORB_LM_TRACE_CAP)); *n_out =
  * records written.  Synchronises. */
@@ -765,7 +766,8 @@ int lorb_ba_plan_debug_stamps(lorb_ba_plan* plan, unsigned long long* out8);
 typedef struct lorb_ba_group lorb_ba_group;
 int lorb_ba_group_create(lorb_ctx* ctx, int32_t n_plans, lorb_ba_plan* const* plans, lorb_ba_group** out);
 int lorb_ba_group_solve(lorb_ba_group* group, const lorb_lm_options* opt);
-/* first n of: [0] member plans, [1] solves that ran as one set of launches, [2] graph captures */
+/* first n of: [0] member plans, [1] solves that ran as one set of launches, [2] graph captures,
+ * [3] kernel launches in the captured graph */
 int lorb_ba_group_info(lorb_ba_group* group, int32_t* info, int32_t n);
 int lorb_ba_group_destroy(lorb_ba_group* group);
 

@@ -58,7 +58,7 @@ using lorb::residual_s;
 
 // K0: start of a solve, one launch: window states, x[0] <- the initial values, and the
 // per-camera rotation states of that first linearisation point (transcendentals once per
-// camera; later ones come from k_ba_lm_end on acceptance).
+// camera; later ones come from the Cholesky's epilogue, with the candidate pose).
 __device__ __forceinline__ void init_run(const BaDev& d, int W, int ctot, int n_pt, int nf, const LMOpt& o, const int i,
                                          const int stride) {
   if (i < W) {
@@ -68,6 +68,7 @@ __device__ __forceinline__ void init_run(const BaDev& d, int W, int ctot, int n_
     s.done = d.win[i].n_obs_all == 0 ? 1 : 0;
     s.relin = 1; s.cur = 0; s.last_successful = 1; s.term = 0; s.chol_fail = 0; s.pad = 0;
     d.st[i] = s;
+    d.ls_fail[i] = 0;
     if (d.sharded) d.wfail_part[i] = 0.0;  // point-block failures (set by k_ba_ls, cleared by k_ba_lm_end)
   }
   if (i < ctot) {
@@ -136,11 +137,13 @@ __device__ __forceinline__ bool prep_point(const double (&Eu)[6], const double (
   }
   return true;
 }
-__device__ __forceinline__ void prep_fail(const BaDev& d, int win) {
+__device__ __forceinline__ void prep_fail(const BaDev& d, int win, int fold) {
   // benign race: every writer stores the same value; sharded plans reduce the flag (K5).  The
   // flag is cleared by k_ba_lm_end (and k_ba_init), not by k_ba_lm_begin: k_ba_ls sets it
-  // before k_ba_lm_begin runs.
-  if (d.sharded) d.wfail_part[win] = 1.0;
+  // before k_ba_lm_begin runs.  fold: the launch's other groups read st.chol_fail as the previous
+  // iteration's, so the flag goes to ls_fail (the Cholesky's head moves it into st and clears it).
+  if (fold) d.ls_fail[win] = 1;
+  else if (d.sharded) d.wfail_part[win] = 1.0;
   else d.st[win].chol_fail = 1;
 }
 
@@ -178,22 +181,37 @@ __global__ __launch_bounds__(64) void k_ba_lm_begin(BaDev d, LMOpt o) {
 }
 
 // the iteration's record (lorb_lm_iteration; S is the state the step was computed from)
-__device__ __forceinline__ void lm_record(const BaDev& d, int w, const WinState& S, int outcome, double mcc,
-                                          double ncost, double step_norm) {
-  if (S.iter < 1 || S.iter > LORB_LM_TRACE_CAP) return;
+__device__ __forceinline__ lorb_lm_iteration lm_rec(const WinState& S, int outcome, double mcc, double ncost,
+                                                    double step_norm) {
   lorb_lm_iteration r;
   r.iteration = S.iter; r.outcome = outcome;
   r.cost = S.cost; r.model_cost_change = mcc; r.new_cost = ncost; r.radius = S.radius; r.step_norm = step_norm;
-  d.trace[(size_t)w * LORB_LM_TRACE_CAP + S.iter - 1] = r;
+  return r;
+}
+__device__ __forceinline__ void lm_record(const BaDev& d, int w, const lorb_lm_iteration& r) {
+  if (r.iteration < 1 || r.iteration > LORB_LM_TRACE_CAP) return;
+  d.trace[(size_t)w * LORB_LM_TRACE_CAP + r.iteration - 1] = r;
 }
 
-// K8 decision (lane 0): step validity, tolerances, accept/reject; returns 1 if accepted
-__device__ int lm_decide(BaDev d, const LMOpt& o, int w, WinState S, bool valid, double mccs,
-                         double ncost, double sn2) {
+// A window state copied field by field (the aggregate copy of a state that is modified in between
+// leaves a memcpy through a private slot, which the backend then places in LDS: 16 B per thread)
+__device__ __forceinline__ WinState state_copy(const WinState& s) {
+  WinState r;
+  r.radius = s.radius; r.decrease_factor = s.decrease_factor; r.cost = s.cost; r.x_norm = s.x_norm; r.gmax = s.gmax;
+  r.initial_cost = s.initial_cost; r.iter = s.iter; r.n_success = s.n_success; r.n_invalid = s.n_invalid;
+  r.done = s.done; r.relin = s.relin; r.cur = s.cur; r.last_successful = s.last_successful; r.term = s.term;
+  r.chol_fail = s.chol_fail; r.pad = s.pad;
+  return r;
+}
+
+// K8 decision (lane 0): step validity, tolerances, accept/reject.  No side effects: S becomes the
+// state after the decision, rec the iteration's record; returns 1 if accepted
+__device__ __forceinline__ int lm_decide(const LMOpt& o, WinState& S, bool valid, double mccs, double ncost,
+                                         double sn2, lorb_lm_iteration& rec) {
   const double model_cost_change = -mccs;
   valid = valid && isfinite(model_cost_change) && isfinite(sn2) && model_cost_change > 0.0;
   if (!valid) {
-    lm_record(d, w, S, LORB_LM_STEP_INVALID, model_cost_change, ncost, sqrt(sn2));
+    rec = lm_rec(S, LORB_LM_STEP_INVALID, model_cost_change, ncost, sqrt(sn2));
     if (++S.n_invalid >= o.max_invalid) {
       S.done = 1; S.term = LORB_TERM_FAILURE;
     } else {
@@ -202,24 +220,23 @@ __device__ int lm_decide(BaDev d, const LMOpt& o, int w, WinState S, bool valid,
       S.last_successful = 0;
       if (S.iter >= o.max_iter) { S.done = 1; S.term = LORB_TERM_NO_CONVERGENCE; }
     }
-    d.st[w] = S;
     return 0;
   }
   S.n_invalid = 0;
   const double new_cost = isfinite(ncost) ? ncost : 1.7976931348623157e308;
   const double step_norm = sqrt(sn2);
   if (step_norm <= o.ptol * (S.x_norm + o.ptol)) {
-    lm_record(d, w, S, LORB_LM_STEP_PARAM_TOL, model_cost_change, new_cost, step_norm);
-    S.done = 1; S.term = LORB_TERM_PARAMETER_TOL; d.st[w] = S; return 0;
+    rec = lm_rec(S, LORB_LM_STEP_PARAM_TOL, model_cost_change, new_cost, step_norm);
+    S.done = 1; S.term = LORB_TERM_PARAMETER_TOL; return 0;
   }
   const double cost_change = S.cost - new_cost;
   if (fabs(cost_change) <= o.ftol * S.cost) {
-    lm_record(d, w, S, LORB_LM_STEP_FUNC_TOL, model_cost_change, new_cost, step_norm);
-    S.done = 1; S.term = LORB_TERM_FUNCTION_TOL; d.st[w] = S; return 0;
+    rec = lm_rec(S, LORB_LM_STEP_FUNC_TOL, model_cost_change, new_cost, step_norm);
+    S.done = 1; S.term = LORB_TERM_FUNCTION_TOL; return 0;
   }
   const double rel = cost_change / model_cost_change;
-  lm_record(d, w, S, rel > o.min_rel ? LORB_LM_STEP_ACCEPTED : LORB_LM_STEP_REJECTED, model_cost_change, new_cost,
-            step_norm);
+  rec = lm_rec(S, rel > o.min_rel ? LORB_LM_STEP_ACCEPTED : LORB_LM_STEP_REJECTED, model_cost_change, new_cost,
+               step_norm);
   if (rel > o.min_rel) {
     S.cur ^= 1;
     S.relin = 1;
@@ -237,50 +254,50 @@ __device__ int lm_decide(BaDev d, const LMOpt& o, int w, WinState S, bool valid,
   // the head of the next iteration would stop here (iteration budget spent): the solve needs no
   // final linearisation, S.cost is the cost at the final point
   if (S.iter >= o.max_iter) { S.done = 1; S.term = LORB_TERM_NO_CONVERGENCE; }
-  d.st[w] = S;
   return rel > o.min_rel;
 }
 
 // K8: per-window iteration tail: camera candidate, step validity, tolerances, accept/reject, on one
-// wavefront (no workgroup barrier: the decision is broadcast with readfirstlane).  (Run instead by
+// wavefront (no workgroup barrier).  (Run instead by
 // the last-finishing point group of the back-substitution -- a per-window counter behind agent-scope
 // release / acquire fences -- it measured far slower: on the 8-XCD device those fences write back
 // and invalidate L2, C4 step 1.076 -> 1.294 ms.)
+// lm_end_eval is the tail without side effects: from the state S after the iteration's head (not
+// done) to the state after the decision and the iteration's record, both valid in lane 0.
+// k_ba_lm_end commits them (lm_end_run); the folded iteration evaluates the tail in the prologue of
+// every workgroup of the next k_ba_ls, and the window's first group commits (ls_group).
 template <bool SH>
-__device__ __forceinline__ void lm_end_run(const BaDev& d, const LMOpt& o, int w, int lane) {
-  const WinState* Sp = d.st + w;
-  WinState S = *Sp;
-  const BaWin W = d.win[w];  // issued with the state, before the done test
-  if (S.done) return;
+__device__ __forceinline__ void lm_end_eval(const BaDev& d, const LMOpt& o, int w, int lane, WinState& S,
+                                            const BaWin& W, lorb_lm_iteration& rec) {
   bool valid = !S.chol_fail;
   double mccs = 0.0, ncost = 0.0, sn2 = 0.0;
-  double xc[6] = {0, 0, 0, 0, 0, 0};  // candidate pose of camera pose_base + lane (kept for its jet)
   if (valid) {
     const int cur = S.cur;
     // the first 64 cameras' poses are requested before the group partials (one round trip for both;
     // the partials' loop would otherwise keep them behind it)
     const int c0 = W.pose_base + lane;
     const bool has0 = lane < W.n_poses;
+    const double* xp = cur ? d.x_pose[1] : d.x_pose[0];   // the iterate
+    const double* xpn = cur ? d.x_pose[0] : d.x_pose[1];  // the candidate (written by k_ba_chol)
     double x0[6], xn0[6];
     bool act0 = false;
     if (has0) {
       act0 = d.cam_active[c0];
 #pragma unroll
-      for (int k = 0; k < 6; ++k) { x0[k] = d.x_pose[cur][6 * c0 + k]; xn0[k] = d.x_pose[cur ^ 1][6 * c0 + k]; }
+      for (int k = 0; k < 6; ++k) { x0[k] = xp[6 * c0 + k]; xn0[k] = xpn[6 * c0 + k]; }
     }
     if (!SH) group_partials<3, 4, 5, false>(d.part, W.pblk_base, W.n_pblk, lane, mccs, ncost, sn2);
     if (has0) {
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         if (act0) sn2 += (x0[k] - xn0[k]) * (x0[k] - xn0[k]);  // (the same order as the loop below)
-        xc[k] = xn0[k];
       }
     }
     for (int c = c0 + 64; c < W.pose_base + W.n_poses; c += 64) {
       const bool active = d.cam_active[c];
       for (int k = 0; k < 6; ++k) {
-        const double x = d.x_pose[cur][6 * c + k];
-        const double xn = d.x_pose[cur ^ 1][6 * c + k];  // written by k_ba_chol
+        const double x = xp[6 * c + k];
+        const double xn = xpn[6 * c + k];
         if (active) sn2 += (x - xn) * (x - xn);
       }
     }
@@ -290,16 +307,22 @@ __device__ __forceinline__ void lm_end_run(const BaDev& d, const LMOpt& o, int w
   // point-block / Cholesky failures are per iteration: cleared here for the next one (k_ba_ls
   // sets them before k_ba_lm_begin runs)
   S.chol_fail = 0;
-  if (SH && lane == 0) d.wfail_part[w] = 0.0;
-  int acc = 0;
-  if (lane == 0) acc = lm_decide(d, o, w, S, valid, mccs, ncost, sn2);
-  acc = __builtin_amdgcn_readfirstlane(acc);  // lane 0's decision, wave-uniform
-  // accepted: the candidate is the new linearisation point -> its rotation states for k_ba_ls
-  // (an accepted step is a valid one, so the first 64 candidates are already in registers)
-  if (acc) {
-    if (lane < W.n_poses) d.rot_lin[W.pose_base + lane] = lorb::rot_jet(xc);
-    for (int c = W.pose_base + lane + 64; c < W.pose_base + W.n_poses; c += 64)
-      d.rot_lin[c] = lorb::rot_jet(d.x_pose[S.cur ^ 1] + 6 * c);
+  // accepted: the candidate is the new linearisation point; its rotation states are in
+  // rot_lin[cur ^ 1] already (the Cholesky's epilogue), so acceptance only flips cur
+  if (lane == 0) (void)lm_decide(o, S, valid, mccs, ncost, sn2, rec);
+}
+template <bool SH>
+__device__ __forceinline__ void lm_end_run(const BaDev& d, const LMOpt& o, int w, int lane) {
+  const WinState* Sp = d.st + w;
+  WinState S = *Sp;
+  const BaWin W = d.win[w];  // issued with the state, before the done test
+  if (S.done) return;
+  lorb_lm_iteration rec;
+  lm_end_eval<SH>(d, o, w, lane, S, W, rec);
+  if (lane == 0) {
+    if (SH) d.wfail_part[w] = 0.0;
+    d.st[w] = S;
+    lm_record(d, w, rec);
   }
 }
 template <bool SH>
@@ -360,7 +383,16 @@ __device__ __forceinline__ void block_red3w(double& a, double& b, double& c, dou
 
 // The linearisation of one observation at the current linearisation point (k_ba_ls and k_ba_bs2
 // evaluate the same expression on the same inputs, so both see the same bits).
-__device__ __forceinline__ void pm_lin(const BaDev& d, const BaWin& W, int cur, int p, int c, int fx, double2 uv,
+// Camera c's entry of d.rot_lin for the iterate x_pose[cur], as one opaque register: the index
+// arithmetic stays out of pm_lin's two branches, which the compiler then lays out as it always has
+// (k_ba_ls and k_ba_bs2 must keep their bits).
+__device__ __forceinline__ int rot_idx(const BaDev& d, int cur, int c) {
+  int cr = rot_off(d, cur) + c;
+  asm volatile("" : "+v"(cr));
+  return cr;
+}
+// (cr: rot_idx of camera c)
+__device__ __forceinline__ void pm_lin(const BaDev& d, const BaWin& W, int cur, int cr, int p, int c, int fx, double2 uv,
                                        double (&r)[2], double (&Jp)[6], double (&Jc)[12]) {
   double X[3];
 #pragma unroll
@@ -369,7 +401,7 @@ __device__ __forceinline__ void pm_lin(const BaDev& d, const BaWin& W, int cur, 
     double tr[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) tr[k] = d.x_pose[cur][6 * c + 3 + k];
-    residual_jac_s(d.rot_lin[c], tr, X, W.fx, W.fy, W.cx, W.cy, uv.x, uv.y, r, Jp, Jc);
+    residual_jac_s(d.rot_lin[cr], tr, X, W.fx, W.fy, W.cx, W.cy, uv.x, uv.y, r, Jp, Jc);
   } else {  // a fixed keyframe: its rotation state from k_ba_init (rot_jet of the same pose: the same bits)
     double tr[3];
 #pragma unroll
@@ -395,8 +427,23 @@ struct LsSup {
   double* gsp;  // the super-group's partial
   int cmin;     // its first camera (plan numbering)
 };
+// a wave-uniform value out of a VGPR (the decided state comes through LDS)
+__device__ __forceinline__ double uniform_d(double v) {
+  const unsigned long long u = __double_as_longlong(v);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((int)(u & 0xffffffffu)), hi = __builtin_amdgcn_readfirstlane((int)(u >> 32));
+  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
+// d.fold (a launch argument: the folded iteration tail, 1; 2: a plan of one window, whose state is
+// requested before the group record arrives): the previous iteration has run no k_ba_lm_end.  One
+// kernel serves both forms, so that the linearisation is the same machine code, hence the same bits,
+// with the tail folded or not.  Wave 0 of every workgroup evaluates that tail for the group's window
+// (lm_end_eval: the same loads in the same order, so every group decides the same bits) and hands the
+// decided state to the group through LDS; the window's first group also commits it, to st2 (the
+// launch's other groups still read st) with the iteration's record.  Nothing a workgroup reads here
+// is written by this launch.
 template <bool SUP>
 __device__ __forceinline__ void ls_group(const BaDev& d, const LMOpt& o, const unsigned bid, const LsSup& su) {
+  const int fold = SUP ? 0 : d.fold;  // (partial runs keep the k_ba_lm_end kernel)
   __shared__ double s_jc[kGB][12];   // B / C: per point Ei (0..5), bs (6..8), sp (9..11); D: Jc per slot
   __shared__ double s_qj[kGB][12];   // A / B: Jp^T Jp (6) | Jp^T r (3) per observation; D: Q | Jps per slot
   __shared__ double s_rg[kGB][4];    // D: r | g per slot
@@ -420,6 +467,15 @@ __device__ __forceinline__ void ls_group(const BaDev& d, const LMOpt& o, const u
     d.dbg[8 * bid + 6] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8) |
                                 (__builtin_amdgcn_s_getreg((31 << 11) | 20) & 255);
 #endif
+  // fold == 2: the window is 0, so its state and the tail's part of its layout are requested with
+  // the group record, not after it (the fold then adds one dependent round trip, the tail's loads)
+  WinState S0{};
+  BaWin W0{};  // (pose_base, n_poses, pblk_base, n_pblk: what lm_end_eval reads)
+  if (fold == 2) {
+    S0 = state_copy(d.st[0]);
+    W0.pose_base = d.win[0].pose_base; W0.n_poses = d.win[0].n_poses;
+    W0.pblk_base = d.win[0].pblk_base; W0.n_pblk = d.win[0].n_pblk;
+  }
   const PBlk g = d.pblk[bid];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const bool has = t < g.no;
@@ -436,11 +492,36 @@ __device__ __forceinline__ void ls_group(const BaDev& d, const LMOpt& o, const u
 #pragma unroll
     for (int k = 0; k < 3; ++k) { Xp[0][k] = d.x_pt[0][3 * p + k]; Xp[1][k] = d.x_pt[1][3 * p + k]; spp[k] = d.scale_pt[3 * p + k]; }
   }
-  const WinState& S = d.st[g.win];
-  if (S.done) return;
-  const BaWin& W = d.win[g.win];
-  const int cur = S.cur;
-  const double rad = S.radius;
+  __shared__ WinState s_dec;
+  int win = 0;
+  if (fold != 2) {
+    win = g.win;
+    S0 = state_copy(d.st[win]);
+    if (fold) {
+      W0.pose_base = d.win[win].pose_base; W0.n_poses = d.win[win].n_poses;
+      W0.pblk_base = d.win[win].pblk_base; W0.n_pblk = d.win[win].n_pblk;
+    }
+  }
+  if (S0.done) return;
+  const BaWin& W = d.win[win];
+  int cur = S0.cur, iter = S0.iter;
+  double rad = S0.radius;
+  if (fold) {
+    if (wv == 0) {
+      WinState Sn = S0;
+      lorb_lm_iteration rec;
+      lm_end_eval<false>(d, o, win, lane, Sn, W0, rec);
+      if (lane == 0) {
+        s_dec = Sn;
+        if ((int)bid == W0.pblk_base) { d.st2[win] = Sn; lm_record(d, win, rec); }
+      }
+    }
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane(s_dec.done)) return;
+    cur = __builtin_amdgcn_readfirstlane(s_dec.cur);
+    iter = __builtin_amdgcn_readfirstlane(s_dec.iter);
+    rad = uniform_d(s_dec.radius);
+  }
   if (t < kGB) { s_mask[0][t] = 0ull; s_mask[1][t] = 0ull; }
   // A
   double r[2] = {0, 0}, Jp[6] = {0, 0, 0, 0, 0, 0}, Jc[12];
@@ -448,7 +529,7 @@ __device__ __forceinline__ void ls_group(const BaDev& d, const LMOpt& o, const u
   for (int k = 0; k < 12; ++k) Jc[k] = 0.0;
   double cost = 0.0;
   if (has) {
-    pm_lin(d, W, cur, p_, c_, fx_, uv, r, Jp, Jc);
+    pm_lin(d, W, cur, rot_idx(d, cur, c_), p_, c_, fx_, uv, r, Jp, Jc);
     cost = 0.5 * (r[0] * r[0] + r[1] * r[1]);
     double* v = s_qj[t];
     v[0] = Jp[0] * Jp[0] + Jp[3] * Jp[3]; v[1] = Jp[0] * Jp[1] + Jp[3] * Jp[4];
@@ -484,7 +565,7 @@ __device__ __forceinline__ void ls_group(const BaDev& d, const LMOpt& o, const u
 #pragma unroll
     for (int k = 0; k < 3; ++k) d.etb[3 * p + k] = b[k];
     double sp[3];
-    if (S.iter == 0) {
+    if (iter == 0) {
       sp[0] = 1.0 / (1.0 + sqrt(E[0]));
       sp[1] = 1.0 / (1.0 + sqrt(E[3]));
       sp[2] = 1.0 / (1.0 + sqrt(E[5]));
@@ -503,7 +584,7 @@ __device__ __forceinline__ void ls_group(const BaDev& d, const LMOpt& o, const u
       }
     }
     double Ei[6], bs[3];
-    if (!prep_point(E, b, sp, rad, o, Ei, bs)) prep_fail(d, g.win);
+    if (!prep_point(E, b, sp, rad, o, Ei, bs)) prep_fail(d, win, fold);
 #pragma unroll
     for (int k = 0; k < 6; ++k) { d.pinv[6 * p + k] = Ei[k]; s_jc[t][k] = Ei[k]; }
 #pragma unroll
@@ -754,7 +835,7 @@ __device__ __forceinline__ void red_run(const BaDev& d, const LMOpt& o, const un
   const BlockPair bp = d.bp[bid];
   const bool diag = bp.ch == bp.cl;
   if (MODE == 0 && !diag) return;
-  const WinState& S = d.st[bp.win];
+  const WinState& S = (d.fold ? d.st2 : d.st)[bp.win];  // (fold: the state k_ba_ls decided)
   const BaWin& W = d.win[bp.win];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   // the finalisation's scales (and MODE 1's camera diagonal) go out with the state
@@ -765,7 +846,8 @@ __device__ __forceinline__ void red_run(const BaDev& d, const LMOpt& o, const un
     scj = d.scale_pose[6 * bp.cl + fj];
     if (MODE == 1 && diag) udg = d.U[21 * bp.ch + u21(fi, fi)];
   }
-  if (S.done) return;
+  // (fold: st done -- the head ended the solve earlier -- leaves st2 stale; both requested at once)
+  if (S.done | d.st[bp.win].done) return;
   const int h = bp.ch - W.pose_base, l = bp.cl - W.pose_base, dd = h - l;
   // entries: [0, 36) the block, [36, 54) the camera terms (U diag, V, R); MODE 0: U diag, V only
   const int e0 = MODE == 0 ? 36 : 0, ne = MODE == 0 ? 12 : (diag ? 54 : 36);
@@ -944,7 +1026,7 @@ __device__ __forceinline__ void bs2_run(const BaDev& d, const unsigned bid) {
   double r[2] = {0, 0}, Jp[6] = {0, 0, 0, 0, 0, 0}, Jc[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) Jc[k] = 0.0;
-  if (has) pm_lin(d, W, cur, p_, c_, fx_, uv, r, Jp, Jc);
+  if (has) pm_lin(d, W, cur, rot_idx(d, cur, c_), p_, c_, fx_, uv, r, Jp, Jc);
   const int lp = p_ - g.p0;
   __syncthreads();
   // W^T y = Jps^T (Jcs y): this observation's push into its point's rhs
@@ -1456,6 +1538,7 @@ void launch_red(const lorb_ba_plan* P, hipStream_t s, const BaDev& d, const LMOp
 }
 
 // the linearisation: one workgroup per point group, or per partial run (k_ba_ls_sup)
+// (d.fold: the previous iteration's tail in its prologue, ls_group)
 void launch_ls(const lorb_ba_plan* P, hipStream_t s, const BaDev& d, const LMOpt& o) {
   lorb::KernelTimer kt(P->ctx, LORB_K_BA_LINEARIZE);
   if (P->has_super) {
@@ -1463,6 +1546,22 @@ void launch_ls(const lorb_ba_plan* P, hipStream_t s, const BaDev& d, const LMOpt
   } else if (P->grid_pblk) {
     hipLaunchKernelGGL(k_ba_ls, dim3(P->grid_pblk), dim3(kLsThreads), 0, s, d, o);
   }
+}
+
+// LORB_NO_FOLD=1 (read at every solve): every iteration ends with the k_ba_lm_end kernel.  Else the
+// fused iterations of an unsharded plan on the two-sided Cholesky without partial runs fold the
+// previous iteration's tail into their k_ba_ls -- unless a window has cameras and no point group (no
+// workgroup of k_ba_ls would commit its state).  The fold trades a launch for one more dependent round
+// trip and a redundant evaluation in every workgroup: it pays where k_ba_ls is one round of
+// workgroups (two per CU: the C4 window's 346), and costs where the launch fills the GPU several
+// times over (8 C4 windows in one plan or in concurrent groups: -1.7 % / -2.8 %, profiles/r11/), so
+// launches of more than kFoldMaxGroups workgroups keep the kernel.
+constexpr int kFoldMaxGroups = 512;
+bool fold_of(const lorb_ba_plan* P) {
+  if (env_flag("LORB_NO_FOLD") || no_fuse() || P->comm || P->has_super || chol_kind_of(P) != 2) return false;
+  for (const BaWin& w : P->hwin)
+    if (w.n_poses > 0 && w.n_pblk == 0) return false;
+  return P->grid_pblk > 0 && P->grid_pblk <= kFoldMaxGroups;
 }
 
 lorb_ba_plan::GraphKey graph_key(const lorb_ba_plan* P) {
@@ -1476,6 +1575,7 @@ lorb_ba_plan::GraphKey graph_key(const lorb_ba_plan* P) {
   k.red_wide = red_threads(P);
   k.sup = P->has_super ? 1 : 0;
   k.grid_sg = P->grid_sg;
+  k.fold = P->fold ? 1 : 0;
   return k;
 }
 
@@ -1508,11 +1608,16 @@ int enqueue_linearize(lorb_ba_plan* P, const LMOpt& o) {
 // the two-sided Cholesky run fused: k_ba_red<2> writes the band, rhs and camera terms at once (the
 // Jacobi scale is iteration 0's) and the head runs inside the Cholesky (k_ba_lm_begin's work), so
 // k_ba_ls -> k_ba_red<2> -> k_ba_chol_2s<true> -> k_ba_bs2 -> k_ba_lm_end: five launches.
-int enqueue_iteration(lorb_ba_plan* P, const LMOpt& o, bool first) {
+// A folding plan (lorb_ba_plan::fold) drops k_ba_lm_end from every iteration but the last (fold_out:
+// a fused iteration follows and runs the tail in its k_ba_ls, fold_in), four launches: the decided
+// state goes to st2, which k_ba_red<2> and the Cholesky's head read (their BaDev has fold set).
+int enqueue_iteration(lorb_ba_plan* P, const LMOpt& o, bool first, bool last) {
   lorb_ctx* ctx = P->ctx;
   hipStream_t s = ctx->stream;
-  const BaDev& d = P->dev;
   const bool fused = !first && chol_kind_of(P) == 2 && !no_fuse();
+  const bool fold_in = P->fold && fused, fold_out = P->fold && !last;
+  BaDev d = P->dev;
+  d.fold = fold_in ? (P->W == 1 ? 2 : 1) : 0;
   if (fused) {
     launch_ls(P, s, d, o);
   } else {
@@ -1555,7 +1660,7 @@ int enqueue_iteration(lorb_ba_plan* P, const LMOpt& o, bool first) {
       LORB_TRY(lorb::comm_allreduce(P->comm, d.wstep_part, d.wstep, 3 * (size_t)P->W, LORB_OP_SUM));
     }
     hipLaunchKernelGGL(k_ba_lm_end<true>, dim3(P->W), dim3(64), 0, s, d, o);
-  } else {
+  } else if (!fold_out) {
     hipLaunchKernelGGL(k_ba_lm_end<false>, dim3(P->W), dim3(64), 0, s, d, o);
   }
   LORB_CHECK_LAUNCH(ctx);
@@ -1574,13 +1679,14 @@ int enqueue_solve(lorb_ba_plan* P, const LMOpt& o) {
   LORB_CHECK_LAUNCH(ctx);
   // no iterations: one linearisation (cost, termination) as the head of a first iteration
   if (o.max_iter <= 0) return enqueue_linearize(P, o);
-  for (int it = 0; it < o.max_iter; ++it) LORB_TRY(enqueue_iteration(P, o, it == 0));
+  for (int it = 0; it < o.max_iter; ++it) LORB_TRY(enqueue_iteration(P, o, it == 0, it + 1 == o.max_iter));
   return LORB_OK;
 }
 
 int plan_solve(lorb_ba_plan* P, const lorb_lm_options* opt) {
   lorb_ctx* ctx = P->ctx;
   LMOpt o = to_dev_opt(opt);
+  P->fold = fold_of(P);
   // per-kernel events cannot live inside a graph, and neither can a host-transport exchange
   const bool timing = ctx->ktime || no_graph() || (P->comm && !P->comm->rccl);
   if (timing) return enqueue_solve(P, o);
@@ -1700,12 +1806,18 @@ int enqueue_group_solve(lorb_ba_group* G, const LMOpt& o) {
   const GrpGrid g_w = grp_grid(G, [](const lorb_ba_plan* P) { return P->W; });
   size_t lds = 0;
   for (const lorb_ba_plan* P : G->plans) lds = std::max(lds, sizeof(double) * (size_t)P->max_env_w);
-  auto linearise = [&]() {
+  // the folded iteration tail (enqueue_iteration): every member folds, or none
+  const bool fold = G->plans[0]->fold;
+  bool one_win = true;
+  for (const lorb_ba_plan* P : G->plans) one_win = one_win && P->W == 1;
+  BaGrp bgf = bg;  // for k_ba_ls, k_ba_red<2> and the Cholesky's head of a folding iteration
+  for (int k = 0; k < n; ++k) bgf.d[k].fold = one_win ? 2 : 1;
+  auto linearise = [&](bool fold_in) {
     lorb::KernelTimer kt(ctx, LORB_K_BA_LINEARIZE);
-    if (g_pb.pre[n]) hipLaunchKernelGGL(k_ba_ls_g, dim3(g_pb.pre[n]), dim3(kLsThreads), 0, s, bg, g_pb, o);
+    if (g_pb.pre[n]) hipLaunchKernelGGL(k_ba_ls_g, dim3(g_pb.pre[n]), dim3(kLsThreads), 0, s, fold_in ? bgf : bg, g_pb, o);
   };
   if (o.max_iter <= 0) {  // one linearisation (cost, termination) as the head of a first iteration
-    linearise();
+    linearise(false);
     launch_red_g<0>(G, s, bg, o);
     hipLaunchKernelGGL(k_ba_lm_begin_g, dim3(g_w.pre[n]), dim3(64), 0, s, bg, g_w, o);
     LORB_CHECK_LAUNCH(ctx);
@@ -1713,7 +1825,9 @@ int enqueue_group_solve(lorb_ba_group* G, const LMOpt& o) {
   }
   for (int it = 0; it < o.max_iter; ++it) {
     const bool first = it == 0;
-    linearise();
+    const bool fold_in = fold && !first, fold_out = fold && it + 1 < o.max_iter;
+    const BaGrp& bi = fold_in ? bgf : bg;
+    linearise(fold_in);
     if (first) {
       {
         lorb::KernelTimer kt(ctx, LORB_K_BA_SCHUR);
@@ -1727,14 +1841,14 @@ int enqueue_group_solve(lorb_ba_group* G, const LMOpt& o) {
     {
       lorb::KernelTimer kt(ctx, LORB_K_BA_SCHUR);
       if (first) launch_red_g<1>(G, s, bg, o);
-      else launch_red_g<2>(G, s, bg, o);
+      else launch_red_g<2>(G, s, bi, o);
     }
     {
       lorb::KernelTimer kt(ctx, LORB_K_BA_CHOLESKY);
-      launch_chol_2s_g(s, bg, g_w, o, !first, lds);
+      launch_chol_2s_g(s, bi, g_w, o, !first, lds);
     }
     if (g_pb.pre[n]) hipLaunchKernelGGL(k_ba_bs2_g, dim3(g_pb.pre[n]), dim3(kGB), 0, s, bg, g_pb);
-    hipLaunchKernelGGL(k_ba_lm_end_g, dim3(g_w.pre[n]), dim3(64), 0, s, bg, g_w, o);
+    if (!fold_out) hipLaunchKernelGGL(k_ba_lm_end_g, dim3(g_w.pre[n]), dim3(64), 0, s, bg, g_w, o);
   }
   for (lorb_ba_plan* P : G->plans) P->chol_kind = 2;
   LORB_CHECK_LAUNCH(ctx);
@@ -1749,6 +1863,11 @@ int group_solve(lorb_ba_group* G, const lorb_lm_options* opt) {
     return LORB_OK;
   }
   const LMOpt o = to_dev_opt(opt);
+  bool fold = true;
+  int groups = 0;
+  for (const lorb_ba_plan* P : G->plans) { fold = fold && fold_of(P); groups += P->grid_pblk; }
+  fold = fold && groups <= kFoldMaxGroups;
+  for (lorb_ba_plan* P : G->plans) P->fold = fold;  // (part of the members' graph keys)
   if (no_graph() || ctx->ktime) {  // per-kernel timing: eager launches (events cannot live in a graph)
     LORB_TRY(enqueue_group_solve(G, o));
     G->n_fused++;
@@ -1833,9 +1952,9 @@ int lorb_ba_plan_info(lorb_ba_plan* plan, int32_t* info, int32_t n) {
     for (size_t c = 0; c < m.size(); ++c) reordered |= m[c] != (int)c;
   int runs = 0;
   for (const BaWin& w : plan->hwin) runs += w.n_sg;
-  const int32_t v[11] = {bw, plan->chol_kind, plan->n_bp, plan->n_pblk, plan->K, plan->Ptot, plan->Ctot, reordered,
-                         1, red_threads(plan), plan->has_super ? runs : 0};
-  for (int i = 0; i < n && i < 11; ++i) info[i] = v[i];
+  const int32_t v[12] = {bw, plan->chol_kind, plan->n_bp, plan->n_pblk, plan->K, plan->Ptot, plan->Ctot, reordered,
+                         1, red_threads(plan), plan->has_super ? runs : 0, plan->cache.kernel_nodes};
+  for (int i = 0; i < n && i < 12; ++i) info[i] = v[i];
   return LORB_OK;
 }
 
@@ -1864,8 +1983,8 @@ int lorb_ba_group_solve(lorb_ba_group* group, const lorb_lm_options* opt) {
 
 int lorb_ba_group_info(lorb_ba_group* group, int32_t* info, int32_t n) {
   if (!group || !info || n < 0) return LORB_E_INVALID;
-  const int32_t v[3] = {(int32_t)group->plans.size(), group->n_fused, group->cache.captures};
-  for (int i = 0; i < n && i < 3; ++i) info[i] = v[i];
+  const int32_t v[4] = {(int32_t)group->plans.size(), group->n_fused, group->cache.captures, group->cache.kernel_nodes};
+  for (int i = 0; i < n && i < 4; ++i) info[i] = v[i];
   return LORB_OK;
 }
 

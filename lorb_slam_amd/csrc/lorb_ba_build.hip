@@ -545,7 +545,7 @@ int build_plan(lorb_ctx* ctx, int nw, const lorb_ba_window* win_in, lorb_ba_plan
   LORB_TRY(alloc_exchange(P, C, (size_t)nw, (size_t)P->env_total + P->n_total + nw, &sol, &solp));
   d.env = sol; d.rhs = sol + P->env_total; d.wfail = sol + P->env_total + P->n_total;
   d.env_part = solp; d.rhs_part = solp + P->env_total; d.wfail_part = solp + P->env_total + P->n_total;
-  LORB_TRY(dalloc(P, (size_t)P->Ctot, &d.rot_lin));
+  LORB_TRY(dalloc(P, 2 * (size_t)P->Ctot, &d.rot_lin)); d.rot_stride = P->Ctot;
   LORB_TRY(dalloc(P, (size_t)P->Ctot, &d.rot_cand));
   LORB_TRY(dalloc(P, (size_t)std::max(P->NF, 1), &d.rot_fix));
   LORB_TRY(dalloc(P, (size_t)std::max(P->NF, 1), &d.rotv_fix));
@@ -554,6 +554,7 @@ int build_plan(lorb_ctx* ctx, int nw, const lorb_ba_window* win_in, lorb_ba_plan
   LORB_TRY(dalloc(P, dbg_words((size_t)nw, (size_t)std::max(P->n_pblk, nw)), &d.dbg));
   LORB_TRY(dalloc(P, ((size_t)P->n_total / 16 + nw + 1) * 1024, &d.kco));
   LORB_TRY(dalloc(P, (size_t)nw, &P->d_state)); d.st = P->d_state;
+  LORB_TRY(dalloc(P, (size_t)nw, &d.st2)); LORB_TRY(dalloc(P, (size_t)nw, &d.ls_fail));
   LORB_TRY(dalloc(P, (size_t)nw * LORB_LM_TRACE_CAP, &d.trace));
   LORB_TRY(dalloc(P, (size_t)std::max(part_total, 1ll), &d.gpart));
   LORB_TRY(dalloc(P, (size_t)std::max(P->grid_sg, 1), &d.gspan));
@@ -1040,12 +1041,13 @@ int dev_alloc(lorb_ctx* ctx, const lorb_ba_window_dev* w, lorb_ba_plan* P) {
   LORB_TRY(alloc_exchange(P, C, 1, P->x2_off + n * n, &sol, &solp));
   d.rhs = sol; d.wfail = sol + n; d.env = sol + P->x2_off;
   d.rhs_part = solp; d.wfail_part = solp + n; d.env_part = solp + P->x2_off;
-  LORB_TRY(dalloc(P, C, &d.rot_lin)); LORB_TRY(dalloc(P, C, &d.rot_cand));
+  LORB_TRY(dalloc(P, 2 * C, &d.rot_lin)); d.rot_stride = (int)C; LORB_TRY(dalloc(P, C, &d.rot_cand));
   LORB_TRY(dalloc(P, (size_t)std::max(b.F, 1), &d.rot_fix)); LORB_TRY(dalloc(P, (size_t)std::max(b.F, 1), &d.rotv_fix));
   LORB_TRY(dalloc(P, n, &d.ycam));
   LORB_TRY(dalloc(P, dbg_words(1, K + Pn + 1), &d.dbg));  // stamps: >= 8 per point group at any build
   LORB_TRY(dalloc(P, ((size_t)n / 16 + 2) * 1024, &d.kco));
   LORB_TRY(dalloc(P, (size_t)1, &P->d_state)); d.st = P->d_state;
+  LORB_TRY(dalloc(P, (size_t)1, &d.st2)); LORB_TRY(dalloc(P, (size_t)1, &d.ls_fail));
   LORB_TRY(dalloc(P, (size_t)LORB_LM_TRACE_CAP, &d.trace));
   P->W = 1;
   P->hwin.assign(1, BaWin{});

@@ -17,6 +17,18 @@ namespace {
 
 using namespace lorb::ba;
 
+// The second pass of k_ba_chol's and k_ba_chol_w's epilogues: the linearisation state of candidate
+// camera c, which its own thread has just stored to x_pose[k], into rot_lin[k] (k = cur ^ 1; an
+// accepted step then only flips cur).  A pass of its own: rot_jet beside rot_val in one block would
+// share subexpressions with it, and the candidate's rot_val must stay the code it is.  (k_ba_chol_2s
+// forms these states on other threads, beside the candidates' pass.)
+__device__ __forceinline__ void rot_lin_of(const BaDev& d, int k, int c) {
+  double x[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) x[q] = d.x_pose[k][6 * c + q];
+  d.rot_lin[rot_off(d, k) + c] = lorb::rot_jet(x);
+}
+
 typedef double v4d __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void wave_sync_lds() {
@@ -321,6 +333,7 @@ __global__ __launch_bounds__(256) void k_ba_chol(BaDev d) {
       }
       d.rot_cand[c] = lorb::rot_val(xn);
     }
+    for (int ci = t; ci < W.n_poses; ci += 256) rot_lin_of(d, cur ^ 1, W.pose_base + ci);
   }
 }
 
@@ -516,6 +529,7 @@ __global__ __launch_bounds__(256) void k_ba_chol_w(BaDev d) {
     }
     d.rot_cand[c] = lorb::rot_val(xn);
   }
+  for (int ci2 = lane; ci2 < W.n_poses; ci2 += 64) rot_lin_of(d, cur ^ 1, W.pose_base + ci2);
 }
 
 // K6t: two-sided ("twisted") banded Cholesky for band <= 48 and n >= 128.  The chain of
@@ -1197,10 +1211,23 @@ __device__ __forceinline__ void chol_2s_run(const BaDev& d, const LMOpt& o, cons
   __shared__ int s_head_done;
 
   // window, state and failure flag requested together (one round trip before the band copy)
+  // (a folding iteration, d.fold: the state k_ba_ls decided, and its point-block failure flag)
+  const bool fold = HEAD && d.fold;
   const BaWin W = d.win[w];
-  const WinState S0 = d.st[w];
+  const int ls_fail = fold ? d.ls_fail[w] : 0;
+  const WinState S0 = [&] {
+    WinState S = (fold ? d.st2 : d.st)[w];
+    if (fold) S.chol_fail = ls_fail;
+    return S;
+  }();
   const int done = S0.done;
   const double wfail = d.sharded ? d.wfail[w] : 0.0;
+  if (fold) {
+    // a solve the head ended earlier has st done (k_ba_ls decides nothing then: st2 is stale); one
+    // the tail has just ended is done in st2 alone, and st takes it here, as k_ba_lm_end stores it
+    if (d.st[w].done) return;
+    if (done && threadIdx.x == 0) d.st[w] = S0;
+  }
   if (done) return;
   if (wfail > 0.0) {  // a rank's point block was not PD: the step is invalid
     if (HEAD) {       // the fused sharded iteration's head still runs (it advances the iteration)
@@ -1351,6 +1378,7 @@ __device__ __forceinline__ void chol_2s_run(const BaDev& d, const LMOpt& o, cons
   if (HEAD && wv == 4) {  // the iteration head while the first panels factor
     const WinState S = d.sharded ? lm_head<true>(d, o, w, lane, S0, W) : lm_head<false>(d, o, w, lane, S0, W);
     if (lane == 0) s_head_done = S.done;
+    if (fold && lane == 0) d.ls_fail[w] = 0;  // (the head has stored it as st.chol_fail)
   }
   // diagonal-block inverses (waves 4 / 5; on waves 6 / 7 after their staging, off the chain waves'
   // SIMDs, they measured no faster)
@@ -1531,6 +1559,23 @@ __device__ __forceinline__ void chol_2s_run(const BaDev& d, const LMOpt& o, cons
       d.x_pose[cur ^ 1][6 * c + k] = xn[k];
     }
     d.rot_cand[c] = lorb::rot_val(xn);
+  }
+  // The candidates' linearisation states (rot_lin[cur ^ 1]: an accepted step then only flips cur) on
+  // the 128 threads before those (waves 4 / 5), at the same time, from the same expression for the
+  // pose: behind the candidates' pass on their threads they cost the kernel 1.8 us.
+  const int el = t - (NT - 256);
+  for (int ci2 = el; el >= 0 && el < 128 && ci2 < W.n_poses; ci2 += 128) {
+    const int c = W.pose_base + ci2;
+    double xn[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int row = 6 * ci2 + k;
+      const double y = row < rt ? zt[row] : zb[n16 - 1 - row];
+      const double xp = d.x_pose[cur][6 * c + k];
+      const double sp = d.scale_pose[6 * c + k];
+      xn[k] = xp + (-y) * sp;
+    }
+    d.rot_lin[rot_off(d, cur ^ 1) + c] = lorb::rot_jet(xn);
   }
 #ifdef LORB_CHOL_TRACE
   if (t == 0) d.dbg[512 * w + 251] = __builtin_amdgcn_s_memtime();  // raw: epilogue issued (thread 0)

@@ -192,7 +192,9 @@ __device__ __forceinline__ double s3(const double m[6], int a, int b) {
 
 // ------------------------------------------------------------------------------------------
 struct BaDev {
-  lorb::RotJet* rot_lin;           // Ctot: rotation state (with d/daa) of x_pose[cur], per linearisation
+  lorb::RotJet* rot_lin;           // 2 x rot_stride: rotation state (with d/daa) of x_pose[k] at k rot_stride
+                                   // (rot_off): k = 0 by k_ba_init, cur ^ 1 by the Cholesky's epilogue with
+                                   // the candidate pose (one array: the kernels index it as they did one buffer)
   lorb::RotVal* rot_cand;          // Ctot: rotation state of the candidate pose x_pose[cur ^ 1]
   lorb::RotJet* rot_fix;           // NF: rotation states of the fixed poses (k_ba_init; they never change)
   lorb::RotVal* rotv_fix;          // NF: the same, value only (the candidate cost)
@@ -233,6 +235,15 @@ struct BaDev {
                              // ((row_base >> 4) + w) * 1024 doubles, top side's blocks then the
                              // bottom side's, [block][16][64] (BandSide::bsk_block)
   WinState* st;
+  // The folded iteration tail (k_ba_ls<FOLD>): the window's first point group stores the state it
+  // decided to st2 (the other groups of that launch still read the undecided st); k_ba_red and the
+  // Cholesky's head of that iteration read st2 (fold != 0 in their copy of BaDev), the head stores
+  // to st again.  ls_fail: a point block of that linearisation was not invertible (st.chol_fail
+  // is an input of the same launch); the head moves it into st.chol_fail and clears it.
+  WinState* st2;
+  int* ls_fail;
+  int fold;  // 0; 1 a folding iteration; 2 of a plan of one window
+  int rot_stride;
   // partials (k_ba_ls -> k_ba_red), per super-group (its first camera - pose_base, camera span)
   double* gpart;
   int2* gspan;
@@ -247,6 +258,9 @@ __device__ __forceinline__ int u21(int a, int b) {  // packed upper index of 6x6
   if (a > b) { const int t = a; a = b; b = t; }
   return a * 6 - (a * (a - 1)) / 2 + (b - a);
 }
+
+// first entry of x_pose[k]'s rotation states in rot_lin
+__device__ __forceinline__ int rot_off(const BaDev& d, int k) { return k ? d.rot_stride : 0; }
 
 // broadcast lane `l` (wave-uniform) of a double through two v_readlane_b32
 __device__ __forceinline__ double readlane_d(double v, int l) {

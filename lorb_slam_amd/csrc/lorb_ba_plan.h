@@ -33,6 +33,7 @@ struct GraphCache {
   hipGraphExec_t exec = nullptr;
   bool valid = false;
   int captures = 0;
+  int kernel_nodes = 0;  // kernel launches the captured solve holds
   explicit GraphCache(const char* what_) : what(what_) {}
   GraphCache(const GraphCache&) = delete;  // owns the two handles
   GraphCache& operator=(const GraphCache&) = delete;
@@ -55,6 +56,18 @@ struct GraphCache {
       if (e != hipSuccess) return lorb::set_error(ctx, LORB_E_DEVICE, "%s capture failed: %s", what, hipGetErrorString(e));
       graph = g;
       LORB_HIP(ctx, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+      {
+        size_t nn = 0;
+        LORB_HIP(ctx, hipGraphGetNodes(graph, nullptr, &nn));
+        std::vector<hipGraphNode_t> nodes(nn);
+        if (nn) LORB_HIP(ctx, hipGraphGetNodes(graph, nodes.data(), &nn));
+        kernel_nodes = 0;
+        for (size_t i = 0; i < nn; ++i) {
+          hipGraphNodeType ty;
+          LORB_HIP(ctx, hipGraphNodeGetType(nodes[i], &ty));
+          kernel_nodes += ty == hipGraphNodeTypeKernel;
+        }
+      }
       remember();
       valid = true;
       captures++;
@@ -97,11 +110,15 @@ struct lorb_ba_plan {
   struct GraphKey {
     int kind = -1, lds = 0, memset_env = 0, env_total = 0, grid_pblk = 0, grid_bp = 0, pt_launch = 0, x2_n = 0;
     int red_wide = 0, sup = 0, grid_sg = 0;
+    int fold = 0;  // the folded iteration tail (lorb_ba_plan::fold)
     bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) == 0; }
   } gkey;
   int grid_pblk = 0, grid_bp = 0;  // launch grids of the point-group and block-pair kernels
   int grid_sg = 0;                 // k_ba_ls_sup's grid (partial runs)
   bool has_super = false;          // some window's partial runs hold more than one point group
+  // this solve folds every iteration's tail but the last into the next k_ba_ls (fold_of, decided at
+  // every solve: LORB_NO_FOLD=1 keeps the k_ba_lm_end kernel)
+  bool fold = false;
   int pt_launch = 0;               // points k_ba_init copies (Ptot, or the capacity)
   int* live = nullptr;             // device [n_pblk, n_bp] (BaDev::live)
   lorb_comm* comm = nullptr;  // sharded plan (not owned)

@@ -26,7 +26,12 @@ namespace {
 
 constexpr uint32_t kIdxBits = 23;
 constexpr uint32_t kIdxMask = (1u << kIdxBits) - 1u;
-constexpr uint32_t kSentinel = 256u << kIdxBits;  // "dist 256, index 0": never beaten by d=256
+constexpr uint32_t kSentinel = 256u << kIdxBits;  // top-2: "dist 256, index 0": never beaten by d=256
+// top-1 (crossCheck): "nothing scanned".  OpenCV's crossCheck takes a train's arg-min whatever its
+// value, so a nearest query at distance 256 is a key like any other; real keys are at most
+// (256 << 23) | (2^23 - 1) < all-ones, the value the train keys idle at between calls.
+constexpr uint32_t kNone = 0xffffffffu;
+static_assert((kSentinel | kIdxMask) < kNone, "every top-1 key is below kNone");
 
 struct BfTile {
   int32_t lane_base;   // first lane descriptor (global index into the lane array)
@@ -93,7 +98,7 @@ __device__ __forceinline__ void scan_tile(const uint4* __restrict__ lane_desc, c
       a[r][0] = lane_desc[2 * (size_t)(tl.lane_base + l)];
       a[r][1] = lane_desc[2 * (size_t)(tl.lane_base + l) + 1];
     }
-    k1[r] = kSentinel;
+    k1[r] = TOP2 ? kSentinel : kNone;
     k2[r] = kSentinel;
   }
   const uint4* __restrict__ u = uni_desc + 2 * (size_t)tl.uni_base;
@@ -147,7 +152,7 @@ __device__ __forceinline__ void scan_tile(const uint4* __restrict__ lane_desc, c
     const int l = threadIdx.x + 256 * r;
     if (l < tl.lane_count) {
       if (ATOM) {
-        if (k1[r] < kSentinel) atomicMin(&k1_out[tl.lane_base + l], k1[r]);
+        if (k1[r] != kNone) atomicMin(&k1_out[tl.lane_base + l], k1[r]);
       } else {
         k1_out[tl.out_base + l] = k1[r];
         if (TOP2) k2_out[tl.out_base + l] = k2[r];
@@ -204,8 +209,8 @@ __global__ __launch_bounds__(256) void k_cc_merge1(uint32_t* __restrict__ tkey, 
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nt) return;
   const uint32_t k = tkey[t];
-  if (k >= kSentinel) return;
-  tkey[t] = 0xffffffffu;
+  if (k == kNone) return;
+  tkey[t] = kNone;
   const unsigned long long v = ((unsigned long long)(k >> kIdxBits) << 32) | (unsigned)t;
   atomicMin(&qkey[k & kIdxMask], v);
 }
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(256) void k_bf_merge(const uint32_t* __restrict__ k
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_init) kinit[i] = ~0ull;  // crossCheck query keys, folded in instead of a fill launch
   if (i >= n) return;
-  uint32_t k1 = kSentinel, k2 = kSentinel;
+  uint32_t k1 = TOP2 ? kSentinel : kNone, k2 = kSentinel;
   for (int c = 0; c < n_chunks; ++c) {
     const uint32_t a = k1p[(size_t)c * n + i];
     if (TOP2) k2 = umed3(k1, a, k2);
@@ -288,7 +293,7 @@ __global__ __launch_bounds__(256) void k_cc_scatter(const uint32_t* __restrict__
   if (t >= nt) return;
   const int p = find_problem(t_off, np, t);
   const uint32_t k = tkey[t];
-  if (k >= kSentinel) return;  // no query anywhere
+  if (k == kNone) return;  // no query anywhere
   uint32_t q = k & kIdxMask;
   const uint32_t d = k >> kIdxBits;
   if (q_base) {
@@ -395,8 +400,8 @@ __global__ __launch_bounds__(256) void k_bf_cc1(const uint4* __restrict__ lane_d
   __threadfence();
   for (int t = threadIdx.x; t < g.nl; t += 256) {  // k_cc_merge1
     const uint32_t k = __hip_atomic_load(&tkey[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k >= kSentinel) continue;
-    tkey[t] = 0xffffffffu;
+    if (k == kNone) continue;
+    tkey[t] = kNone;
     atomicMin(&qkey[k & kIdxMask], ((unsigned long long)(k >> kIdxBits) << 32) | (unsigned)t);
   }
   __threadfence();
@@ -406,7 +411,7 @@ __global__ __launch_bounds__(256) void k_bf_cc1(const uint4* __restrict__ lane_d
 }
 
 // train keys <-> doubles for the all-reduce(min) (keys < 2^32 are exact in double); trains of
-// problems without local queries were not scanned and offer the sentinel
+// problems without local queries were not scanned and offer kNone
 __global__ void k_u32_f64(const uint32_t* __restrict__ a, double* __restrict__ b, int n, int dir,
                           uint32_t* __restrict__ c, const int32_t* __restrict__ q_off,
                           const int32_t* __restrict__ t_off, int np) {
@@ -414,7 +419,7 @@ __global__ void k_u32_f64(const uint32_t* __restrict__ a, double* __restrict__ b
   if (i >= n) return;
   if (dir == 0) {
     const int p = find_problem(t_off, np, i);
-    b[i] = q_off[p + 1] > q_off[p] ? (double)a[i] : (double)kSentinel;
+    b[i] = q_off[p + 1] > q_off[p] ? (double)a[i] : (double)kNone;
   } else {
     c[i] = (uint32_t)b[i];
   }
@@ -842,7 +847,7 @@ int lorb_bf_match_sharded_dev(lorb_ctx* ctx, lorb_comm* comm, int32_t np, const 
       hipLaunchKernelGGL(k_u32_f64, dim3(lorb::ceil_div(nt, 256)), dim3(256), 0, ctx->stream, k1, kd, nt, 0,
                          (uint32_t*)nullptr, (const int32_t*)d_off, (const int32_t*)(d_off + np + 1), np);
     } else {
-      std::vector<double> sent(nt, (double)kSentinel);
+      std::vector<double> sent(nt, (double)kNone);
       LORB_HIP(ctx, hipMemcpyAsync(kd, sent.data(), sizeof(double) * nt, hipMemcpyHostToDevice, ctx->stream));
       LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }

@@ -53,16 +53,50 @@ def ties():
     return d_off, np.concatenate(d)
 
 
-@pytest.mark.parametrize("case", ["lists", "ties"])
+def strides():
+    """list lengths around the kernel's 64-lane stride (one wavefront per point walks its list in
+    blocks of 64: one short of, exactly and one past 1 and 2 strides, then 3 and 4 full strides plus
+    a remainder), a list whose first median is 256 (the top of the binary search's range) and 130
+    identical descriptors (every median 0 in all three strides: index 0 has to win); 15 points, so
+    the last workgroup (4 points each) is partial"""
+    rng = np.random.default_rng(17)
+    descs = []
+    for n in [0, 1, 2, 3, 63, 64, 65, 127, 128, 129, 200, 300, 5]:
+        src = synth.random_desc(rng, 1)
+        d = synth.flip_bits(rng, np.repeat(src, n, 0), 24)
+        k = n // 5
+        if k:
+            d[rng.choice(n, size=k, replace=False)] = synth.random_desc(rng, k)
+        descs.append(d)
+    d = np.full((3, 32), 255, np.uint8)
+    d[0] = 0  # medians 256, 0, 0 -> best = 1
+    descs.append(d)
+    descs.append(np.repeat(synth.random_desc(rng, 1), 130, 0))  # best = 0
+    d_off = np.concatenate([[0], np.cumsum([len(x) for x in descs])]).astype(np.int32)
+    return d_off, np.concatenate(descs)
+
+
+CASES = {"lists": lists, "ties": ties, "strides": strides}
+
+
+@pytest.mark.parametrize("case", ["lists", "ties", "strides"])
 def test_oracle_vs_numpy(case):
-    d_off, desc = lists() if case == "lists" else ties()
-    assert np.array_equal(O.compute_descriptor(d_off, desc), numpy_ref(d_off, desc))
+    d_off, desc = CASES[case]()
+    ref = numpy_ref(d_off, desc)
+    assert np.array_equal(O.compute_descriptor(d_off, desc), ref)
+    if case == "strides":
+        assert len(ref) == 15 and ref[13] == 1 and ref[14] == 0
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", ["lists", "ties"])
+@pytest.mark.parametrize("case", ["lists", "ties", "strides", "strides[:1]", "strides[:2]", "strides[:5]"])
 def test_gpu_compute_descriptor(ctx, case):
-    d_off, desc = lists() if case == "lists" else ties()
+    if case.startswith("strides[:"):  # the same lists cut to 1, 2 and 5 points (partial workgroups)
+        n = int(case[9:-1])
+        d_off, desc = strides()
+        d_off, desc = d_off[:n + 1], desc[:d_off[n]]
+    else:
+        d_off, desc = CASES[case]()
     best, out = ctx.compute_descriptor(d_off, desc)
     ref = O.compute_descriptor(d_off, desc)
     assert np.array_equal(best, ref)

@@ -95,6 +95,58 @@ def test_local_mapping_ragged_keyframes(ctx):
     M.close()
 
 
+def duplicate_descriptor_sequence():
+    """the small sequence with the first two keyframes' descriptors drawn from 7 of the initial
+    map's point descriptors: every train's nearest query is tied among the copies (the first copy
+    has to win, across the query chunks' atomicMin); depths are kept, so step 0 appends points with
+    duplicate descriptors and from step 1 on queries tie between trains as well.
+
+    The 7 points are ones both keyframes re-observe, and the keypoints (x, y, depth; they come in no
+    particular order) are permuted so that the first copy of each descriptor, the one the crossCheck
+    has to pick, sits on the keypoint that does observe its point: the 7 matches are then true
+    observations and the LM solve after them is as well conditioned as in the other chains (with the
+    matches on arbitrary keypoints its first trial step is rejected at 9 times the cost, where the
+    two solves' round-off differs by more than the trace comparison allows)."""
+    seq = synth.mapping_sequence(seed=5, n_kf=10, n_fixed=2, n_new=40, obs_lens=(3, 4), steps=3, n_kps=300)
+    rng = np.random.default_rng(55)
+    pd = seq["init"]["point_desc"]
+    seen = []  # per keyframe: keypoint -> the initial point it re-observes (at most 20 flipped bits), or -1
+    for k in seq["steps"][:2]:
+        D = np.bitwise_count(k["desc"][:, None, :] ^ pd[None, :, :]).sum(2)
+        seen.append(np.where(D.min(1) <= 20, D.argmin(1), -1))
+    both = np.intersect1d(seen[0][seen[0] >= 0], seen[1][seen[1] >= 0])
+    pts = rng.choice(both, size=7, replace=False)
+    for i in (0, 1):
+        k = seq["steps"][i]
+        n = len(k["desc"])
+        draw = rng.integers(0, 7, n)
+        first = np.array([np.nonzero(draw == j)[0][0] for j in range(7)])
+        obs = np.array([np.nonzero(seen[i] == p)[0][0] for p in pts])
+        perm = np.empty(n, np.int64)
+        perm[first] = obs
+        perm[np.setdiff1d(np.arange(n), first)] = np.setdiff1d(np.arange(n), obs)
+        seq["steps"][i] = dict(k, desc=np.ascontiguousarray(pd[pts][draw]), x=k["x"][perm], y=k["y"][perm],
+                               depth=k["depth"][perm])
+    return seq
+
+
+def test_local_mapping_duplicate_descriptors(ctx):
+    """the map's own crossCheck (the two-launch k_bf_scan1 + k_cc_merge1 into the map's key buffers,
+    the only caller of match1_keys_into) on tie-heavy data: match_train, the counts and the appended
+    map structure bit for bit against the oracle, 3 steps.
+
+    The LM solve runs 4 iterations: a keyframe tied to the map by 7 matches leaves the window weakly
+    constrained, and from the fifth iteration on the oracle's own trace is a walk along a flat valley
+    (rejected trial steps at relative cost changes of 1e-4 .. 1) where the trace comparison's 1e-10
+    is below the two solves' round-off; the first four iterations are the descent (every step accepted,
+    the cost falling by 98 % .. 0.04 % per iteration) and are compared as strictly as in the other chains."""
+    seq = duplicate_descriptor_sequence()
+    opt4 = A.LMOptions.default(max_num_iterations=4, function_tolerance=0.0, gradient_tolerance=0.0,
+                               parameter_tolerance=0.0)
+    M, g = run_chain(ctx, seq, opt4, 3)
+    M.close()
+
+
 def test_local_mapping_capacity_error(ctx):
     """a step that would overflow the map's point capacity is refused and leaves the map unchanged;
     the next step (a keyframe without stereo depth: matches only, no new points) runs from the

@@ -405,7 +405,8 @@ int lorb_orb_extract_capacity(int32_t rows, int32_t cols, int32_t n_levels, cons
  *
  * Left to the host: Frame::AssignFeaturesToGrid (:87-103) is NOT an output -- every consumer
  * (the grid of lorb_search_by_projection_*, lorb_track_*) builds its grid from x, y -- and the
- * map-point slots (mvpMapPoints, mnMapPoints = 0).
+ * map-point slots (mvpMapPoints, mnMapPoints = 0), which lorb_frame_slots_fill_dev and
+ * lorb_track_motion_frames_dev (below) keep as a device object of the caller's.
  * -------------------------------------------------------------------------------------- */
 typedef struct lorb_frame_config {
   int32_t rows, cols;                    /* both images */
@@ -648,6 +649,83 @@ int lorb_track_local(lorb_ctx* ctx, const lorb_frame_params* frame, const float 
                      const lorb_map_points_dev* pts, const lorb_track_local_params* par,
                      const lorb_lm_options* opt, uint8_t* in_view, float* track, int32_t* level,
                      int32_t* assign, lorb_track_local_result* result, float* Tcw_out);
+
+/* ----------------------------------------------------------------------------------------
+ * The map-point slots of a built frame as a device object, and motion tracking straight from two
+ * device-built frames: VisualOdometry::EstimatePoseMotion(pF) after its SetPose
+ * (src/visual_odometry.cpp:121-137) enqueued behind lorb_frame_build_dev with the keypoint counts
+ * never read by the host.
+ *
+ * lorb_frame_slots is Frame::mvpMapPoints as the matchers see it: state is d_slot_state of the
+ * tracking calls, pos their d_slot_pos; (state != EMPTY, state == LOCKED, pos, desc) are has_mp,
+ * mp_locked, mp_pos and mp_desc of the next frame's lorb_last_frame.  MapPoint::mNormalVector and
+ * mfMaxDistance / mfMinDistance of created points are NOT produced: UpdateNormalAndDepth's OpenCV
+ * arithmetic (cv::norm, Mat division) is unpinned, so they stay with the host.
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_frame_slots {   /* Frame::mvpMapPoints as the matchers see it; device arrays of n_max entries */
+  uint8_t* state;                   /* LORB_SLOT_EMPTY / LORB_SLOT_FREE / LORB_SLOT_LOCKED */
+  float*   pos;                     /* n_max x 3, GetPos() of the held point */
+  uint8_t* desc;                    /* n_max x 32, GetDescriptor() of the held point */
+} lorb_frame_slots;
+
+#define LORB_SLOTS_UPDATE_FRAME 0   /* VisualOdometry::UpdateFrame, src/visual_odometry.cpp:215-230 */
+#define LORB_SLOTS_INITIALIZE   1   /* VisualOdometry::Initialize's loop, src/visual_odometry.cpp:86-99 */
+
+/* Gives the slots of a built frame their map points.  frame and Tcw (the frame's pose) are host
+ * values; d_frame is a host struct of DEVICE pointers (its left x, y, desc, its depth and counts[0]
+ * are read), d_slots a host struct of device arrays of n_max entries each, d_n_created (nullable)
+ * one device int.  n_left = d_frame->counts[0] is read on the device; nothing at or past n_left
+ * is written.  A count that is negative or above n_max writes no slot and stores -1 at
+ * d_n_created.
+ *   LORB_SLOTS_UPDATE_FRAME: every EMPTY slot i < n_left becomes FREE (the MapPoint constructor of
+ *     src/map_point.cpp:26-35 leaves mnObs = 0) with pos = UnprojectStereo(i) -- the bits of
+ *     lorb_unproject_stereo_dev, so (0,0,0) for a keypoint without depth -- and desc = the frame's
+ *     descriptor i; non-empty slots are untouched.  *d_n_created = slots filled.
+ *   LORB_SLOTS_INITIALIZE: slots with depth >= 0 become LOCKED (AddObservation: mnObs = 1) with the
+ *     unprojected pos and the frame's descriptor (ComputeDescriptor over one observation is that
+ *     descriptor); slots with depth < 0 become EMPTY.  *d_n_created = slots LOCKED.  The
+ *     mnMapPoints < 300 gate (src/visual_odometry.cpp:80) stays the caller's.
+ * Asynchronous on the ctx stream: one launch, no stream synchronise, no copy. */
+int lorb_frame_slots_fill_dev(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16],
+                              const lorb_frame_out* d_frame, int32_t n_max, int32_t mode,
+                              const lorb_frame_slots* d_slots, int32_t* d_n_created);
+
+typedef struct lorb_track_frames_result {
+  lorb_track_motion_result motion;
+  int32_t n_last, n_cur;   /* the counts the call read */
+  int32_t n_created;       /* points UpdateFrame made */
+  int32_t status;          /* 0, or 1: a count was negative or above its bound: nothing else was written */
+} lorb_track_frames_result;
+
+/* EstimatePoseMotion(pF) after its SetPose (src/visual_odometry.cpp:121-137) on two frames built by
+ * lorb_frame_build_dev.  cur, cur_Tcw (the predicted pose), pose_init (the same pose as mRvec |
+ * mTvec), last_Tcw, par, opt, the bounds and cur_slots_given are host values; d_cur / d_last are
+ * host structs of device pointers; the slot structs are host structs of device arrays (n_max_cur /
+ * n_max_last entries); d_last_outlier (n_max_last bytes, Frame::mvbOutlier) may be NULL: none.
+ *   1. The LORB_SLOTS_UPDATE_FRAME fill of d_last_slots (:121).
+ *   2. Both a4 passes and the tail exactly as lorb_track_motion_dev, with the last frame
+ *      {n = d_last->counts[0], has_mp = state != EMPTY, mp_locked = state == LOCKED, mp_pos / mp_desc
+ *      = the slots, octave / angle = d_last->left} and the current keypoints d_cur's left arrays +
+ *      u_right, n = d_cur->counts[0].  On entry d_cur_slots is taken as all EMPTY (and never read)
+ *      unless cur_slots_given.
+ *   3. The codes that count applied to d_cur_slots: i >= 0 copies last slot i (state, pos, desc);
+ *      LORB_ASSIGN_NULL gives EMPTY; UNCHANGED keeps the entry state when pass 1 stood and gives
+ *      EMPTY when the retry ran (:128 empties first), as for pass 0.
+ * d_assign: n_max_cur ints.  d_result: one record; status 1 (a count negative or above its bound)
+ * leaves assign, both slot sets and the rest of the record untouched.  Nothing at or past a count
+ * is written.  The bounds size grids, strides and scratch: a caller who knows nfeatures passes a
+ * little more than that rather than the builder's capacity, whose square would leave a4's one-pass
+ * candidate layout.  LORB_E_INVALID when n_max_last * n_max_cur > 8M (the asynchronous limit of a4).
+ * Asynchronous on the ctx stream: no stream synchronise, no device-to-host read and no
+ * host-to-device copy.  The slots left behind are d_slot_state / d_slot_pos of lorb_track_local_dev
+ * and the last-frame arrays of the next frame's call. */
+int lorb_track_motion_frames_dev(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16],
+                                 const float pose_init[6], const lorb_frame_out* d_cur, int32_t n_max_cur,
+                                 const lorb_frame_slots* d_cur_slots, int32_t cur_slots_given,
+                                 const float last_Tcw[16], const lorb_frame_out* d_last, int32_t n_max_last,
+                                 const lorb_frame_slots* d_last_slots, const uint8_t* d_last_outlier,
+                                 const lorb_track_motion_params* par, const lorb_lm_options* opt,
+                                 int32_t* d_assign, lorb_track_frames_result* d_result);
 
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.

@@ -202,6 +202,18 @@ class FrameOut(C.Structure):  # lorb_frame_out
                 ("counts", C.c_void_p)]
 
 
+LORB_SLOTS_UPDATE_FRAME, LORB_SLOTS_INITIALIZE = 0, 1
+
+
+class FrameSlots(C.Structure):  # lorb_frame_slots (device addresses)
+    _fields_ = [("state", C.c_void_p), ("pos", C.c_void_p), ("desc", C.c_void_p)]
+
+
+class TrackFramesResult(C.Structure):  # lorb_track_frames_result
+    _fields_ = [("motion", TrackMotionResult), ("n_last", C.c_int32), ("n_cur", C.c_int32), ("n_created", C.c_int32),
+                ("status", C.c_int32)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

@@ -1453,7 +1453,8 @@ __device__ __forceinline__ void tail_run(const TailSlots& s, bool solve, double 
 // calls), one workgroup: which pass counts (pass 1 unless it found <= min_matches, then the retry,
 // which must itself find more), the final assign codes, and tail_run over the slots holding a map
 // point afterwards (the retry starts from emptied slots: only its own matches count).
-__global__ __launch_bounds__(kPoThreads) void k_track_tail(lorb::TrackTail a, LMOpt o) {
+// (the body, shared with k_track_frames_tail; returns whether the retry ran)
+__device__ __forceinline__ bool track_tail_run(const lorb::TrackTail& a, const LMOpt& o) {
   const int nm1 = *a.nm1;
   const bool retry = nm1 <= a.min_matches;
   const int nm2 = retry ? *a.nm2 : -1;
@@ -1462,6 +1463,37 @@ __global__ __launch_bounds__(kPoThreads) void k_track_tail(lorb::TrackTail a, LM
   const TailSlots s = {a.nk, retry ? a.assign2 : a.assign, !retry, a.slot_state, a.slot_pos, a.last_pos, a.x, a.y,
                        a.list, retry ? a.assign : nullptr, a.assign_out};
   tail_run(s, pass != 0, a.fx, a.fy_eff, a.cx, a.cy, a.pose_init, o, &a.rec->n_residuals, a.rec->pose, &a.rec->summary);
+  return retry;
+}
+__global__ __launch_bounds__(kPoThreads) void k_track_tail(lorb::TrackTail a, LMOpt o) { track_tail_run(a, o); }
+
+// The tail of lorb_track_motion_frames_dev: k_track_tail with the keypoint count read from device
+// memory (a.nk is the bound on entry), then the codes that count -- a.assign after the body -- applied
+// to the current frame's slots: code i >= 0 copies last slot i (state, pos, desc); NULL empties the
+// slot; UNCHANGED keeps a given slot when pass 1 stood and empties it otherwise (the retry starts from
+// emptied slots, src/visual_odometry.cpp:128; slots not given are all EMPTY whatever the array holds).
+// The apply runs after the LM: the solve has read slot_pos (the kept slots' points) by then, and the
+// few dozen bytes per slot are not worth a launch of their own.
+__global__ __launch_bounds__(kPoThreads) void k_track_frames_tail(lorb::TrackTail a, lorb::FramesTail f, LMOpt o) {
+  int n_last;
+  if (!lorb::frame_counts(f.dc, &n_last, &a.nk)) return;
+  const bool retry = track_tail_run(a, o);
+  __syncthreads();  // every thread's codes are in a.assign, every read of the entry slots is done
+  const bool keep = !retry && f.given;
+  const uint4* ld = reinterpret_cast<const uint4*>(f.last.desc);
+  uint4* cd = reinterpret_cast<uint4*>(f.cur.desc);
+  for (int j = threadIdx.x; j < a.nk; j += kPoThreads) {
+    const int c = a.assign[j];
+    if (c >= 0) {
+      f.cur.state[j] = f.last.state[c];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) f.cur.pos[3 * (size_t)j + k] = f.last.pos[3 * (size_t)c + k];
+      cd[2 * (size_t)j] = ld[2 * (size_t)c];
+      cd[2 * (size_t)j + 1] = ld[2 * (size_t)c + 1];
+    } else if (c == LORB_ASSIGN_NULL || !keep) {
+      f.cur.state[j] = LORB_SLOT_EMPTY;
+    }
+  }
 }
 
 // The tail of the local-map tracking chain (VisualOdometry::EstimatePoseLocal after its matcher
@@ -1895,6 +1927,11 @@ int launch_local_tail(lorb_ctx* ctx, const LocalTail& t, const lorb_lm_options* 
 }
 int launch_track_tail(lorb_ctx* ctx, const TrackTail& t, const lorb_lm_options* opt) {
   hipLaunchKernelGGL(k_track_tail, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, to_dev_opt(opt));
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
+int launch_track_frames_tail(lorb_ctx* ctx, const TrackTail& t, const FramesTail& f, const lorb_lm_options* opt) {
+  hipLaunchKernelGGL(k_track_frames_tail, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, f, to_dev_opt(opt));
   LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
 }

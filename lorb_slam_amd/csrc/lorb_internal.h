@@ -403,6 +403,30 @@ struct TrackTail {
 };
 int launch_track_tail(lorb_ctx* ctx, const TrackTail& t, const lorb_lm_options* opt);
 
+// The device-count form of the a4 chain (lorb_track_motion_frames_dev): the two keypoint counts live
+// in device memory (entry 0 of each built frame's counts, the left side) and the host knows only the
+// caller's bounds, which size every grid, stride and scratch buffer.  A kernel of that form reads both
+// counts once, through wave-uniform (scalar) loads, and checks them before any other load.
+struct FrameCounts {
+  const int *last, *cur;
+  int max_last, max_cur;
+};
+// false: a count is negative or above its bound (the chain's status 1: the kernel writes nothing)
+__device__ __forceinline__ bool frame_counts(const FrameCounts& c, int* n_last, int* n_cur) {
+  const int l = c.last[0], k = c.cur[0];
+  *n_last = l;
+  *n_cur = k;
+  return l >= 0 && l <= c.max_last && k >= 0 && k <= c.max_cur;
+}
+// What k_track_frames_tail (lorb_ba.hip) has beyond k_track_tail: TrackTail::nk is read from the
+// counts, and after the LM the codes that count are applied to the current frame's slots.
+struct FramesTail {
+  FrameCounts dc;
+  lorb_frame_slots cur, last;
+  int given;  // 0: the current slots are all EMPTY on entry, whatever the arrays hold
+};
+int launch_track_frames_tail(lorb_ctx* ctx, const TrackTail& t, const FramesTail& f, const lorb_lm_options* opt);
+
 // The tail of the local-map tracking chain (lorb_track_local*, lorb_window.hip): one launch of
 // k_local_tail (lorb_ba.hip) after a8 + a5 -- the in-view count, the nmatches > min_matches gate,
 // residual compaction, pose-only LM, result record.  All pointers are device pointers.
@@ -544,12 +568,13 @@ inline constexpr SlotFamily
     S_KP = {24, 10, false},   // keypoint grid of a search (7 .. 9; 0 .. 6 are free: the keypoints travel in the InPack)
     S_WX = {34, 8, false},    // windowed-matcher working buffers
     S_ST = {48, 15, false},   // stereo matcher
-    S_ORB = {48, 51, false},  // ORB extractor.  Alias: over S_ST, S_TL, S_TM and S_TLC -- no call runs two of them
+    S_ORB = {48, 51, false},  // ORB extractor.  Alias: over S_ST, S_TL, S_TM, S_TF and S_TLC -- no call runs two of them
     S_TL = {64, 20, false},   // lorb_track_local_map's staging.  Alias: inside S_ORB's range, as above
     S_TM = {88, 3, false},    // motion chain: pass 2's codes + both counts, the residual list, the host form's codes
+    S_TF = {91, 1, false},    // frames chain (which also uses S_TM 0 and 1): the last frame's mp_locked flags
     S_TLC = {92, 6, false};   // local-map chain: match count, residual list; the host form's codes, in-view flags, fields, levels
 inline constexpr SlotFamily kSlotPlan[] = {
-    {S_BF_Q, 14, false}, {S_W0, 10, false}, S_KP, S_WX, S_ST, S_ORB, S_TL, S_TM, S_TLC,
+    {S_BF_Q, 14, false}, {S_W0, 10, false}, S_KP, S_WX, S_ST, S_ORB, S_TL, S_TM, S_TF, S_TLC,
     {S_BF_TKEY, 1, true}, {S_IO_IN, 1, true}, {S_IO_OUT, 1, true}, {S_BF_DONE, 1, true}, {S_TM_ZERO, 1, true}};
 
 // slot K of family F; an offset past the family's end does not compile

@@ -123,10 +123,18 @@ __device__ __forceinline__ void grid_place(int* idx, const int* off, int* cur, c
     }
   }
 }
+// kDevCount (the frames chain): n is the current frame's count in device memory, dc.max_cur bounds
+// it and sizes cell_idx / kp_cell
+template <bool kDevCount = false>
 __global__ __launch_bounds__(1024) void k_grid_build(const float* __restrict__ x, const float* __restrict__ y,
                                                      int n, lorb_frame_params fp,
                                                      int* __restrict__ cell_off,  // kCells+1
-                                                     int* __restrict__ cell_idx, int* __restrict__ kp_cell) {
+                                                     int* __restrict__ cell_idx, int* __restrict__ kp_cell,
+                                                     lorb::FrameCounts dc = {}) {
+  if (kDevCount) {
+    int nl;
+    if (!lorb::frame_counts(dc, &nl, &n)) return;
+  }
   __shared__ int off[kCells + 1];  // counts, then offsets
   __shared__ int cur[kCells];
   __shared__ int s_idx[kGridLds];
@@ -365,7 +373,10 @@ __device__ __forceinline__ int cand_frame_one(const KpDev& K, const WinParams& P
   }
   return cnt;
 }
-template <bool WRITE, bool GRID = false>
+// kDevCount (the frames chain): launched over the bounds (nl = dc.max_last, K.n = dc.max_cur, which
+// is also the stride); the counts are read first, a workgroup wholly past n_last leaves before it
+// stages anything, a wave past it loads no query
+template <bool WRITE, bool GRID = false, bool kDevCount = false>
 __global__ __launch_bounds__(64 * kCandWaves) void k_cand_frame(KpDev K, WinParams P, int nl,
                                                     const uint8_t* __restrict__ has_mp,
                                                     const uint8_t* __restrict__ outlier,
@@ -374,11 +385,17 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_cand_frame(KpDev K, WinPara
                                                     const uint4* __restrict__ ldesc,
                                                     int* __restrict__ cand_cnt, const int* __restrict__ cand_off,
                                                     int2* __restrict__ cand, int stride = 0,
-                                                    const int* __restrict__ skip_unless = nullptr, int skip_max = 0) {
+                                                    const int* __restrict__ skip_unless = nullptr, int skip_max = 0,
+                                                    lorb::FrameCounts dc = {}) {
+  if (kDevCount) {
+    if (!lorb::frame_counts(dc, &nl, &K.n)) return;
+    if ((int)blockIdx.x * kCandWaves >= nl) return;
+  }
   // a predicated pass (the motion chain's retry): runs only if *skip_unless <= skip_max
   if (skip_unless && *skip_unless > skip_max) return;
   const int i = blockIdx.x * kCandWaves + (threadIdx.x >> 6);
   // the query's inputs requested first (GRID: they arrive while the keypoints are staged)
+  // (kDevCount: a workgroup that got here has blockIdx.x * kCandWaves < nl, so nl - 1 >= 0)
   FrameQuery q = frame_query(min(i, nl - 1), has_mp, outlier, pos, loct);
   q.act = q.act && (unsigned)q.o < (unsigned)P.oct_limit;
   if constexpr (GRID) {
@@ -393,7 +410,14 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_cand_frame(KpDev K, WinPara
 }
 
 // exclusive scan of candidate counts (one workgroup, chunked)
-__global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ cnt, int n, int* __restrict__ off) {
+// kDevCount (the frames chain): n is the last frame's count in device memory (cnt holds nothing past it)
+template <bool kDevCount = false>
+__global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ cnt, int n, int* __restrict__ off,
+                                               lorb::FrameCounts dc = {}) {
+  if (kDevCount) {
+    int nk;
+    if (!lorb::frame_counts(dc, &n, &nk)) return;
+  }
   __shared__ int wsum[16];
   int carry = 0;
   for (int base = 0; base < n; base += 1024) {
@@ -599,7 +623,9 @@ inline int resolve_lds_mode(int np, int nk, size_t* bytes) {
   *bytes = 0;
   return 0;
 }
-template <int MODE>
+// kDevCount (the frames chain): np and nk are the two counts in device memory; the bounds chose
+// lds_mode, the stride and the sizes of the global working arrays, so whatever the counts are fits
+template <int MODE, bool kDevCount = false>
 __global__ __launch_bounds__(1024) void k_resolve(int np, int nk, const int* __restrict__ cand_off,
                                                   const int2* __restrict__ cand,
                                                   const uint8_t* __restrict__ pt_locked,
@@ -609,7 +635,9 @@ __global__ __launch_bounds__(1024) void k_resolve(int np, int nk, const int* __r
                                                   int* __restrict__ assign, int* __restrict__ bins,
                                                   int* __restrict__ nulls, int* __restrict__ nmatches, int lds_mode,
                                                   int stride = 0, int* __restrict__ out = nullptr,
-                                                  const int* __restrict__ skip_unless = nullptr, int skip_max = 0) {
+                                                  const int* __restrict__ skip_unless = nullptr, int skip_max = 0,
+                                                  lorb::FrameCounts dc = {}) {
+  if (kDevCount && !lorb::frame_counts(dc, &np, &nk)) return;
   if (skip_unless && *skip_unless > skip_max) return;  // a predicated pass, as k_cand_frame
   // the working set in LDS (dynamic shared memory) as far as it fits (resolve_lds_mode), else global
   extern __shared__ int s_dyn[];
@@ -758,17 +786,89 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_cand_local_fr(KpDev K, WinP
   if (lane0) cand_cnt[m] = cnt;
 }
 
-// (a20) Frame::UnprojectStereo, one thread per keypoint; Twc = mTcw.inv() given
+// (a20) Frame::UnprojectStereo of one keypoint: the origin where it has no depth (src/frame.cpp:352-355)
+__device__ __forceinline__ void unproject_kp(const lorb_frame_params& fp, const lorb::Mat4f& Twc, float x, float y,
+                                             float z, float* out) {
+  if (z > 0) {
+    lorb::unproject_point(fp.fx, fp.fy, fp.cx, fp.cy, Twc, x, y, z, out);
+  } else {
+    out[0] = 0.0f; out[1] = 0.0f; out[2] = 0.0f;
+  }
+}
+// one thread per keypoint; Twc = mTcw.inv() given
 __global__ __launch_bounds__(256) void k_unproject(lorb_frame_params fp, lorb::Mat4f Twc, int n,
                                                    const float* __restrict__ x, const float* __restrict__ y,
                                                    const float* __restrict__ depth, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float z = depth[i];
-  if (z > 0) {
-    lorb::unproject_point(fp.fx, fp.fy, fp.cx, fp.cy, Twc, x[i], y[i], z, out + 3 * i);
+  unproject_kp(fp, Twc, x[i], y[i], depth[i], out + 3 * i);
+}
+
+// The map-point slots of a built frame (lorb_frame_slots_fill_dev; the first launch of
+// lorb_track_motion_frames_dev), one 1024-thread workgroup walking the frame's n_left keypoints:
+// the count of created points is then a workgroup sum -- no atomic, no counter to clear -- and a
+// frame has a few thousand keypoints at most.
+//   MODE LORB_SLOTS_UPDATE_FRAME (src/visual_odometry.cpp:215-230): an EMPTY slot becomes FREE with
+//     the unprojected keypoint and the frame's descriptor; others are left alone.
+//   MODE LORB_SLOTS_INITIALIZE (:86-99): depth >= 0 -> LOCKED with the same; depth < 0 -> EMPTY.
+// CHAIN (the frames chain): both counts are checked and the record's status, counts and n_created
+// written here, the chain's first kernel; `locked` receives state == LOCKED (a4's mp_locked).
+struct SlotFill {
+  lorb_frame_params fp;
+  lorb::Mat4f Twc;
+  const int* count;  // the frame's counts (entry 0); !CHAIN only
+  int n_max;
+  const float *x, *y, *depth;
+  const uint4* desc;
+  uint8_t* state;
+  float* pos;
+  uint4* sdesc;
+  uint8_t* locked;  // or null
+  int* n_created;   // or null
+};
+template <int MODE, bool CHAIN>
+__global__ __launch_bounds__(1024) void k_slots_fill(SlotFill a, lorb::FrameCounts dc,
+                                                     lorb_track_frames_result* __restrict__ rec) {
+  __shared__ int wsum[16];
+  const int t = threadIdx.x;
+  int n, n_cur = 0;
+  if (CHAIN) {
+    const bool ok = lorb::frame_counts(dc, &n, &n_cur);
+    if (t == 0) rec->status = ok ? 0 : 1;
+    if (!ok) return;
   } else {
-    out[3 * i] = 0.0f; out[3 * i + 1] = 0.0f; out[3 * i + 2] = 0.0f;
+    n = a.count[0];
+    if (n < 0 || n > a.n_max) {
+      if (t == 0 && a.n_created) *a.n_created = -1;
+      return;
+    }
+  }
+  int made = 0;
+  for (int i = t; i < n; i += 1024) {
+    uint8_t st;
+    bool fill;
+    if (MODE == LORB_SLOTS_UPDATE_FRAME) {
+      st = a.state[i];
+      fill = st == LORB_SLOT_EMPTY;
+      if (fill) st = LORB_SLOT_FREE;
+    } else {
+      fill = a.depth[i] >= 0;
+      st = fill ? LORB_SLOT_LOCKED : LORB_SLOT_EMPTY;
+    }
+    if (fill) {
+      unproject_kp(a.fp, a.Twc, a.x[i], a.y[i], a.depth[i], a.pos + 3 * (size_t)i);
+      a.sdesc[2 * (size_t)i] = a.desc[2 * (size_t)i];
+      a.sdesc[2 * (size_t)i + 1] = a.desc[2 * (size_t)i + 1];
+      made++;
+    }
+    if (fill || MODE == LORB_SLOTS_INITIALIZE) a.state[i] = st;
+    if (a.locked) a.locked[i] = st == LORB_SLOT_LOCKED;
+  }
+  int tot;
+  lorb::block_excl_scan_1024(made, wsum, &tot);
+  if (t == 0) {
+    if (a.n_created) *a.n_created = tot;
+    if (CHAIN) { rec->n_last = n; rec->n_cur = n_cur; rec->n_created = tot; }
   }
 }
 
@@ -833,15 +933,21 @@ KpDev kps_finish(const lorb::InPack& in, const KpParts& p, int n) {
   return K;
 }
 // The keypoint grid of a frame (src/frame.cpp:87-115) for a *K that has none yet: the one place that
-// launches k_grid_build.  A second search over the same *K reuses the grid.
-int ensure_grid(lorb_ctx* ctx, KpDev* K, const lorb_frame_params& fp) {
+// launches k_grid_build.  A second search over the same *K reuses the grid.  dc (the frames chain):
+// K->n is the bound, the count is read on the device.
+int ensure_grid(lorb_ctx* ctx, KpDev* K, const lorb_frame_params& fp, const lorb::FrameCounts* dc = nullptr) {
   if (K->cell_off) return LORB_OK;
   const size_t n = (size_t)std::max(K->n, 1);
   int *cell_off, *cell_idx, *kp_cell;
   LORB_TRY(lorb::scratch_t(ctx, slot<S_KP, 7>(), kCells + 1, &cell_off));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_KP, 8>(), n, &cell_idx));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_KP, 9>(), n, &kp_cell));
-  hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(1024), 0, ctx->stream, K->x, K->y, K->n, fp, cell_off, cell_idx, kp_cell);
+  if (dc)
+    hipLaunchKernelGGL(k_grid_build<true>, dim3(1), dim3(1024), 0, ctx->stream, K->x, K->y, K->n, fp, cell_off, cell_idx,
+                       kp_cell, *dc);
+  else
+    hipLaunchKernelGGL(k_grid_build<false>, dim3(1), dim3(1024), 0, ctx->stream, K->x, K->y, K->n, fp, cell_off, cell_idx,
+                       kp_cell);
   LORB_CHECK_LAUNCH(ctx);
   K->cell_off = cell_off; K->cell_idx = cell_idx;
   return LORB_OK;
@@ -920,7 +1026,10 @@ int empty_slots(lorb_ctx* ctx, int n, const uint8_t** out) {
 // the candidate lists of the nq queries (one strided pass up to kCandStrided entries, else count /
 // scan / write), the resolver.  What differs per search is `launch`: called as launch(CandPass<WRITE,
 // GRID>, workgroups, cnt, off, cand, stride), it launches that instantiation of its candidate kernel.
-// The working buffers (S_WX, S_W9) are the same for every search.
+// The working buffers (S_WX, S_W9) are the same for every search.  dc (the frames chain, MODE 1 only):
+// nq and K->n are the caller's bounds -- they size the grids, the stride, the LDS mode and every
+// buffer -- and each kernel reads the two counts from device memory (its kDevCount form); `launch`
+// passes *dc on to its candidate kernel.
 template <bool WRITE, bool GRID>
 struct CandPass {
   static constexpr bool write = WRITE, grid = GRID;
@@ -933,13 +1042,13 @@ struct SearchOut {
 };
 template <int MODE, typename Launch>
 int search_issue(lorb_ctx* ctx, KpDev* K, const lorb_frame_params& fp, int nq, const uint8_t* locked,
-                 const float* last_angle, const SearchOut& o, Launch&& launch) {
+                 const float* last_angle, const SearchOut& o, Launch&& launch, const lorb::FrameCounts* dc = nullptr) {
   const int nk = K->n;
   // a query has at most nk candidates: up to kCandStrided entries one pass writes them at i * nk
   // (no count pass, no scan); past it the count / scan / write passes size the list exactly
   const bool strided = (size_t)nq * (size_t)nk <= kCandStrided;
   const bool lds_grid = strided && nk <= kStageKps;  // the candidate kernel builds the grid itself
-  if (!lds_grid) LORB_TRY(ensure_grid(ctx, K, fp));
+  if (!lds_grid) LORB_TRY(ensure_grid(ctx, K, fp, dc));
   int *cnt, *off, *res, *claim, *bins = nullptr, *nulls = nullptr;
   LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 0>(), (size_t)nq + 1, &cnt));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_WX, 1>(), (size_t)nq + 1, &off));
@@ -964,16 +1073,23 @@ int search_issue(lorb_ctx* ctx, KpDev* K, const lorb_frame_params& fp, int nq, c
       launch(CandPass<false, false>{}, g, cnt, (const int*)nullptr, (int2*)nullptr, 0);
     }
     // a skipped pass leaves cnt as the pass before wrote it: the scan then sizes a list nobody fills
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, ctx->stream, cnt, nq, off);
+    if (dc) hipLaunchKernelGGL(k_scan<true>, dim3(1), dim3(1024), 0, ctx->stream, cnt, nq, off, *dc);
+    else hipLaunchKernelGGL(k_scan<false>, dim3(1), dim3(1024), 0, ctx->stream, cnt, nq, off);
     LORB_TRY(alloc_candidates(ctx, off + nq, (size_t)nq * (size_t)nk, &cand));
     if (nq > 0) launch(CandPass<true, false>{}, g, cnt, (const int*)off, cand, 0);
   }
   size_t rlds = 0;
   const int rmode = resolve_lds_mode(nq, nk, &rlds);
-  hipLaunchKernelGGL(k_resolve<MODE>, dim3(1), dim3(1024), rlds, ctx->stream, nq, nk,
-                     strided ? (const int*)cnt : (const int*)off, cand, locked, last_angle,
-                     MODE == 1 ? K->angle : (const float*)nullptr, res, claim, o.assign, bins, nulls, o.nmatches, rmode,
-                     strided ? nk : 0, o.out, o.skip_unless, o.skip_max);
+  if (dc)
+    hipLaunchKernelGGL((k_resolve<MODE, true>), dim3(1), dim3(1024), rlds, ctx->stream, nq, nk,
+                       strided ? (const int*)cnt : (const int*)off, cand, locked, last_angle,
+                       MODE == 1 ? K->angle : (const float*)nullptr, res, claim, o.assign, bins, nulls, o.nmatches, rmode,
+                       strided ? nk : 0, o.out, o.skip_unless, o.skip_max, *dc);
+  else
+    hipLaunchKernelGGL((k_resolve<MODE, false>), dim3(1), dim3(1024), rlds, ctx->stream, nq, nk,
+                       strided ? (const int*)cnt : (const int*)off, cand, locked, last_angle,
+                       MODE == 1 ? K->angle : (const float*)nullptr, res, claim, o.assign, bins, nulls, o.nmatches, rmode,
+                       strided ? nk : 0, o.out, o.skip_unless, o.skip_max);
   LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
 }
@@ -981,14 +1097,19 @@ int search_issue(lorb_ctx* ctx, KpDev* K, const lorb_frame_params& fp, int nq, c
 // a4 on device-resident inputs, for the host-array call, the device-pointer call and the motion
 // chain (whose second pass over the same *K is predicated on the first's count)
 int a4_issue(lorb_ctx* ctx, KpDev* K, const WinParams& P, const LastDev& L, int* dassign, int* dnm, int* out,
-             const int* skip_unless = nullptr, int skip_max = 0) {
-  return search_issue<1>(ctx, K, P.fp, L.n, L.lk, L.la, {dassign, dnm, out, skip_unless, skip_max},
-                         [&](auto pass, unsigned g, int* cnt, const int* off, int2* cand, int stride) {
-                           using Pass = decltype(pass);
-                           hipLaunchKernelGGL((k_cand_frame<Pass::write, Pass::grid>), dim3(g), dim3(256), 0, ctx->stream,
-                                              *K, P, L.n, L.hm, L.ol, L.pos, L.lo, L.ld, cnt, off, cand, stride,
-                                              skip_unless, skip_max);
-                         });
+             const int* skip_unless = nullptr, int skip_max = 0, const lorb::FrameCounts* dc = nullptr) {
+  return search_issue<1>(
+      ctx, K, P.fp, L.n, L.lk, L.la, {dassign, dnm, out, skip_unless, skip_max},
+      [&](auto pass, unsigned g, int* cnt, const int* off, int2* cand, int stride) {
+        using Pass = decltype(pass);
+        if (dc)
+          hipLaunchKernelGGL((k_cand_frame<Pass::write, Pass::grid, true>), dim3(g), dim3(256), 0, ctx->stream, *K, P, L.n,
+                             L.hm, L.ol, L.pos, L.lo, L.ld, cnt, off, cand, stride, skip_unless, skip_max, *dc);
+        else
+          hipLaunchKernelGGL((k_cand_frame<Pass::write, Pass::grid, false>), dim3(g), dim3(256), 0, ctx->stream, *K, P, L.n,
+                             L.hm, L.ol, L.pos, L.lo, L.ld, cnt, off, cand, stride, skip_unless, skip_max);
+      },
+      dc);
 }
 
 struct LocalDev {  // a5's queries on the device: lorb_local_points' arrays, or a8's output
@@ -1114,12 +1235,16 @@ int lorb_search_by_projection_frame_dev(lorb_ctx* ctx, const lorb_frame_params* 
 // always enqueued, its kernels returning at once unless the first pass found <= min_matches --
 // then the tail kernel (pass decision, final codes, residual gathering, pose-only LM).  The second
 // pass reuses the first's keypoint grid and working buffers (the stream orders them).
+// fr (lorb_track_motion_frames_dev): K.n and L.n are the caller's bounds (both >= 1), every kernel
+// reads the counts of fr->dc, and the tail is k_track_frames_tail, which also applies the codes to
+// the current frame's slots.
 static int track_motion_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const float* cur_Tcw,
                               const float* pose_init, KpDev K, const float* slot_pos, const LastDev& L,
                               const float* last_Tcw, const lorb_track_motion_params* par,
                               const lorb_lm_options* opt, int* d_assign, lorb_track_motion_result* rec,
-                              int* assign_out) {
+                              int* assign_out, const lorb::FramesTail* fr = nullptr) {
   const int nk = K.n;
+  const lorb::FrameCounts* dc = fr ? &fr->dc : nullptr;
   int* tm;  // pass 2's codes (nk) | its count | pass 1's count
   float* list;
   LORB_TRY(lorb::scratch_t(ctx, slot<S_TM, 0>(), (size_t)nk + 2, &tm));
@@ -1133,10 +1258,10 @@ static int track_motion_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const
     LORB_TRY(empty_slots(ctx, nk, &z));
     if (!given) K.slot_state = z;
     LORB_TRY(a4_issue(ctx, &K, frame_params_a4(cur, cur_Tcw, last_Tcw, par->th_first, cur->n_levels), L, d_assign, nm1,
-                      nullptr));
+                      nullptr, nullptr, 0, dc));
     K.slot_state = z;  // src/visual_odometry.cpp:128: the retry starts from emptied slots
     LORB_TRY(a4_issue(ctx, &K, frame_params_a4(cur, cur_Tcw, last_Tcw, par->th_retry, cur->n_levels), L, tm, nm2, nullptr,
-                      nm1, par->min_matches));
+                      nm1, par->min_matches, dc));
   }
   lorb::TrackTail t{};
   t.nk = nk; t.nm1 = nm1; t.nm2 = nm2; t.assign2 = tm; t.assign = d_assign;
@@ -1145,6 +1270,7 @@ static int track_motion_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const
   t.fx = cur->fx; t.fy_eff = par->fy_eff; t.cx = cur->cx; t.cy = cur->cy;
   memcpy(t.pose_init, pose_init, sizeof(t.pose_init));
   t.list = list; t.rec = rec; t.assign_out = assign_out;
+  if (fr) return lorb::launch_track_frames_tail(ctx, t, *fr, opt);
   return lorb::launch_track_tail(ctx, t, opt);
 }
 
@@ -1203,6 +1329,92 @@ int lorb_track_motion(lorb_ctx* ctx, const lorb_frame_params* cur, const float c
     lorb_pose_to_Tcw(R, T, Tcw_out);
   }
   return LORB_OK;
+}
+
+// the fill launch of lorb_frame_slots_fill_dev and of the frames chain (dc / rec given)
+static int slots_fill_issue(lorb_ctx* ctx, const lorb_frame_params* frame, const float* Tcw, const lorb_frame_out* f,
+                            int n_max, int mode, const lorb_frame_slots* s, uint8_t* locked, int* n_created,
+                            const lorb::FrameCounts* dc, lorb_track_frames_result* rec) {
+  SlotFill a{};
+  a.fp = *frame;
+  float Twc[16];
+  inv4_lu32f(Tcw, Twc);
+  memcpy(a.Twc.v, Twc, sizeof(a.Twc.v));
+  a.count = f->counts; a.n_max = n_max;
+  a.x = f->left.x; a.y = f->left.y; a.depth = f->depth; a.desc = reinterpret_cast<const uint4*>(f->left.desc);
+  a.state = s->state; a.pos = s->pos; a.sdesc = reinterpret_cast<uint4*>(s->desc);
+  a.locked = locked; a.n_created = n_created;
+  if (dc)
+    hipLaunchKernelGGL((k_slots_fill<LORB_SLOTS_UPDATE_FRAME, true>), dim3(1), dim3(1024), 0, ctx->stream, a, *dc, rec);
+  else if (mode == LORB_SLOTS_UPDATE_FRAME)
+    hipLaunchKernelGGL((k_slots_fill<LORB_SLOTS_UPDATE_FRAME, false>), dim3(1), dim3(1024), 0, ctx->stream, a,
+                       lorb::FrameCounts{}, (lorb_track_frames_result*)nullptr);
+  else
+    hipLaunchKernelGGL((k_slots_fill<LORB_SLOTS_INITIALIZE, false>), dim3(1), dim3(1024), 0, ctx->stream, a,
+                       lorb::FrameCounts{}, (lorb_track_frames_result*)nullptr);
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
+static bool slots_ok(const lorb_frame_slots* s) { return s && s->state && s->pos && s->desc; }
+static bool frame_left_ok(const lorb_frame_out* f) {
+  return f && f->counts && f->depth && f->left.x && f->left.y && f->left.desc;
+}
+
+int lorb_frame_slots_fill_dev(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16],
+                              const lorb_frame_out* d_frame, int32_t n_max, int32_t mode,
+                              const lorb_frame_slots* d_slots, int32_t* d_n_created) {
+  if (!ctx || !frame || !Tcw || !d_frame || !d_slots) return LORB_E_INVALID;
+  if (n_max < 0) return lorb::set_error(ctx, LORB_E_INVALID, "negative bound %d", n_max);
+  if (mode != LORB_SLOTS_UPDATE_FRAME && mode != LORB_SLOTS_INITIALIZE)
+    return lorb::set_error(ctx, LORB_E_INVALID, "unknown fill mode %d", mode);
+  if (!frame_left_ok(d_frame) || !slots_ok(d_slots)) return lorb::set_error(ctx, LORB_E_INVALID, "null array");
+  return slots_fill_issue(ctx, frame, Tcw, d_frame, n_max, mode, d_slots, nullptr, d_n_created, nullptr, nullptr);
+}
+
+// VisualOdometry::EstimatePoseMotion(pF) after its SetPose (src/visual_odometry.cpp:121-137) on two
+// built frames whose counts stay in device memory: the UpdateFrame fill of the last frame's slots
+// (which also checks the counts and writes the record's status), the motion chain in its device-count
+// form over the caller's bounds, and the tail that applies the codes to the current frame's slots.
+int lorb_track_motion_frames_dev(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16],
+                                 const float pose_init[6], const lorb_frame_out* d_cur, int32_t n_max_cur,
+                                 const lorb_frame_slots* d_cur_slots, int32_t cur_slots_given,
+                                 const float last_Tcw[16], const lorb_frame_out* d_last, int32_t n_max_last,
+                                 const lorb_frame_slots* d_last_slots, const uint8_t* d_last_outlier,
+                                 const lorb_track_motion_params* par, const lorb_lm_options* opt,
+                                 int32_t* d_assign, lorb_track_frames_result* d_result) {
+  if (!ctx || !cur || !cur_Tcw || !pose_init || !d_cur || !d_cur_slots || !last_Tcw || !d_last || !d_last_slots || !par ||
+      !opt || !d_assign || !d_result)
+    return LORB_E_INVALID;
+  if (n_max_cur < 1 || n_max_last < 1)
+    return lorb::set_error(ctx, LORB_E_INVALID, "bounds %d / %d must be positive", n_max_last, n_max_cur);
+  // a4's candidate list is allocated from the bounds: past this it would need the total read back
+  if ((int64_t)n_max_last * (int64_t)n_max_cur > (int64_t(8) << 20))
+    return lorb::set_error(ctx, LORB_E_INVALID, "bounds %d x %d exceed the asynchronous limit of 8M candidates",
+                           n_max_last, n_max_cur);
+  if (cur->n_levels < 1 || cur->n_levels > LORB_MAX_LEVELS)
+    return lorb::set_error(ctx, LORB_E_INVALID, "n_levels %d out of range", cur->n_levels);
+  if (par->min_matches < 0) return lorb::set_error(ctx, LORB_E_INVALID, "min_matches %d is negative", par->min_matches);
+  if (!frame_left_ok(d_cur) || !frame_left_ok(d_last) || !slots_ok(d_cur_slots) || !slots_ok(d_last_slots) ||
+      !d_cur->left.octave || !d_cur->left.angle || !d_cur->u_right || !d_last->left.octave || !d_last->left.angle)
+    return lorb::set_error(ctx, LORB_E_INVALID, "null array");
+  lorb::FramesTail fr{};
+  fr.dc = {d_last->counts, d_cur->counts, n_max_last, n_max_cur};
+  fr.cur = *d_cur_slots; fr.last = *d_last_slots; fr.given = cur_slots_given != 0;
+  uint8_t* lk;
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TF, 0>(), (size_t)n_max_last, &lk));
+  LORB_TRY(slots_fill_issue(ctx, cur, last_Tcw, d_last, n_max_last, LORB_SLOTS_UPDATE_FRAME, d_last_slots, lk, nullptr,
+                            &fr.dc, d_result));
+  KpDev K;
+  K.x = d_cur->left.x; K.y = d_cur->left.y; K.angle = d_cur->left.angle; K.uR = d_cur->u_right;
+  K.octave = d_cur->left.octave; K.desc = reinterpret_cast<const uint4*>(d_cur->left.desc);
+  K.slot_state = fr.given ? d_cur_slots->state : nullptr;
+  K.cell_off = nullptr; K.cell_idx = nullptr; K.n = n_max_cur;
+  // has_mp is "state != EMPTY": the kernels test the byte for non-zero, so the states serve as they are
+  static_assert(LORB_SLOT_EMPTY == 0, "the slot states are read as has_mp flags");
+  const LastDev L = {n_max_last, d_last_slots->state, d_last_outlier, lk, d_last_slots->pos, d_last->left.angle,
+                     d_last->left.octave, reinterpret_cast<const uint4*>(d_last_slots->desc)};
+  return track_motion_issue(ctx, cur, cur_Tcw, pose_init, K, d_cur_slots->pos, L, last_Tcw, par, opt, d_assign,
+                            &d_result->motion, nullptr, &fr);
 }
 
 int lorb_is_in_frustum(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16],

@@ -62,6 +62,98 @@ class DeviceFrame:
         self._all = []
 
 
+class DeviceSlots:
+    """lorb_frame_slots of n_max entries in device memory (Frame::mvpMapPoints as the matchers see it).
+    Each array is ORB_GUARD entries longer than the calls are told and starts as ORB_SENTINEL bytes
+    (guard bands; an entry state of ORB_SENTINEL is no slot state, so a caller that wants EMPTY slots
+    passes state=0 or an array).  state / pos / desc: host arrays of up to n_max entries to start from."""
+
+    def __init__(self, ctx, n_max, state=None, pos=None, desc=None):
+        self.ctx, self.n_max = ctx, int(n_max)
+        n = self.n_max + ORB_GUARD
+        hs, hp, hd = (np.full(n, ORB_SENTINEL, np.uint8), np.full(n * 12, ORB_SENTINEL, np.uint8).view(np.float32).reshape(n, 3),
+                      np.full((n, 32), ORB_SENTINEL, np.uint8))
+        if state is not None:
+            state = np.full(self.n_max, state, np.uint8) if np.isscalar(state) else np.asarray(state, np.uint8)
+            hs[:len(state)] = state
+        if pos is not None:
+            hp[:len(pos)] = np.asarray(pos, np.float32)
+        if desc is not None:
+            hd[:len(desc)] = np.asarray(desc, np.uint8)
+        self.state, self.pos, self.desc = ctx.to_device(hs), ctx.to_device(hp), ctx.to_device(hd)
+        self.c = A.FrameSlots(self.state.ptr.value, self.pos.ptr.value, self.desc.ptr.value)
+
+    def numpy(self):
+        """The whole guarded arrays: dict(state (n,), pos (n, 3), desc (n, 32)), n = n_max + ORB_GUARD."""
+        return dict(state=self.state.numpy(), pos=self.pos.numpy(), desc=self.desc.numpy())
+
+    def free(self):
+        for a in (self.state, self.pos, self.desc):
+            a.free()
+
+
+def fill_slots(ctx, fp, Tcw, frame, slots, mode, n_max=None):
+    """lorb_frame_slots_fill_dev on a DeviceFrame and a DeviceSlots -> n_created (waits for the stream).
+    mode: A.LORB_SLOTS_UPDATE_FRAME or A.LORB_SLOTS_INITIALIZE; n_max defaults to the slots' size."""
+    fps = A.make_frame_params(fp)
+    T = A.f32(Tcw).reshape(16)
+    made = ctx.to_device(np.full(1 + ORB_GUARD, -7, np.int32))
+    try:
+        ctx.check(lib().lorb_frame_slots_fill_dev(ctx.handle, C.byref(fps), A.ptr(T, C.c_float), C.byref(frame.out),
+                                                  C.c_int32(slots.n_max if n_max is None else n_max), C.c_int32(mode),
+                                                  C.byref(slots.c), made.ptr), "lorb_frame_slots_fill_dev")
+        m = made.numpy()
+        if not (m[1:] == -7).all():
+            raise LorbError("lorb_frame_slots_fill_dev wrote past d_n_created")
+        return int(m[0])
+    finally:
+        made.free()
+
+
+def track_motion_frames(ctx, fp, cur_Tcw, pose_init, cur, cur_slots, last_Tcw, last, last_slots, n_max_cur=None,
+                        n_max_last=None, cur_slots_given=False, last_outlier=None, th_first=15.0, th_retry=30.0,
+                        min_matches=20, fy_eff=None, opt=None, assign_fill=-77):
+    """lorb_track_motion_frames_dev on two DeviceFrames and their DeviceSlots: EstimatePoseMotion(pF)
+    after its SetPose with both keypoint counts read on the device.  One fetch after the call brings
+    back the record; returns dict(status, n_last, n_cur, n_created, the fields of Context.track_motion's
+    result, assign: the whole n_max_cur + ORB_GUARD array (pre-filled with assign_fill), cur_slots and
+    last_slots: DeviceSlots.numpy())."""
+    fps = A.make_frame_params(fp)
+    par = A.TrackMotionParams(th_first, th_retry, min_matches, fps.fx if fy_eff is None else fy_eff)
+    opt = opt or A.LMOptions.default()
+    T, TL = A.f32(cur_Tcw).reshape(16), A.f32(last_Tcw).reshape(16)
+    pi = A.f32(pose_init).reshape(6)
+    nc = cur_slots.n_max if n_max_cur is None else int(n_max_cur)
+    nl = last_slots.n_max if n_max_last is None else int(n_max_last)
+    held = [ctx.to_device(np.full(max(nc, 0) + ORB_GUARD, assign_fill, np.int32)),
+            ctx.to_device(np.full(C.sizeof(A.TrackFramesResult), ORB_SENTINEL, np.uint8))]
+    asg, drec = held
+    ol = None
+    if last_outlier is not None:
+        ol = ctx.to_device(A.u8(last_outlier))
+        held.append(ol)
+    try:
+        ctx.check(lib().lorb_track_motion_frames_dev(
+            ctx.handle, C.byref(fps), A.ptr(T, C.c_float), A.ptr(pi, C.c_float), C.byref(cur.out), C.c_int32(nc),
+            C.byref(cur_slots.c), C.c_int32(1 if cur_slots_given else 0), A.ptr(TL, C.c_float), C.byref(last.out),
+            C.c_int32(nl), C.byref(last_slots.c), ol.ptr if ol else None, C.byref(par), C.byref(opt), asg.ptr, drec.ptr),
+            "lorb_track_motion_frames_dev")
+        raw = drec.numpy()  # the one fetch: it waits for the stream
+        rec = A.TrackFramesResult.from_buffer_copy(raw.tobytes())
+        m = rec.motion
+        Tout = np.zeros((4, 4), np.float32)
+        if rec.status == 0:
+            rv, tv = A.f32(m.pose[:3]), A.f32(m.pose[3:])  # Frame::SetPose from the rounded pose
+            lib().lorb_pose_to_Tcw(A.ptr(rv, C.c_float), A.ptr(tv, C.c_float), A.ptr(Tout, C.c_float))
+        return dict(status=rec.status, n_last=rec.n_last, n_cur=rec.n_cur, n_created=rec.n_created, pass_=m.pass_,
+                    nmatches_first=m.nmatches_first, nmatches_retry=m.nmatches_retry, n_residuals=m.n_residuals,
+                    pose=np.array(m.pose[:], np.float64), summary=m.summary.as_dict(), Tcw=Tout, record_bytes=raw,
+                    assign=asg.numpy(), cur_slots=cur_slots.numpy(), last_slots=last_slots.numpy())
+    finally:
+        for a in held:
+            a.free()
+
+
 class FrameBuilder:
     """lorb_frame_builder of one geometry.  fp: frame-params dict (n_levels, scale_factors, bf, b are
     read); n_desired: features per level (n_levels entries); pattern: the 256 test pairs (1024 ints)."""

@@ -471,6 +471,8 @@ struct Arena {
 
 // The extractor over a stereo pair (lorb_orb.hip; used by lorb_frame.hip's builder): the plan and
 // scratch of one geometry, and its 13 launches per frame on the ctx stream -- no host copy, no wait.
+// The kernels and launch sites are the one-image entry points' (k_orb_copy, k_orb_resize, k_orb_fast,
+// k_orb_octree, k_orb_gather, k_orb_blur, k_orb_desc), the image grid dimension at extent 2.
 // Per image the outputs of lorb_orb_extract_dev; d_counts[2] receives {n_left, n_right} (-1: that
 // image's quadtree overflowed its node capacity).
 struct OrbPair;
@@ -568,7 +570,7 @@ inline constexpr SlotFamily
     S_KP = {24, 10, false},   // keypoint grid of a search (7 .. 9; 0 .. 6 are free: the keypoints travel in the InPack)
     S_WX = {34, 8, false},    // windowed-matcher working buffers
     S_ST = {48, 15, false},   // stereo matcher
-    S_ORB = {48, 51, false},  // ORB extractor.  Alias: over S_ST, S_TL, S_TM, S_TF and S_TLC -- no call runs two of them
+    S_ORB = {48, 50, false},  // ORB extractor.  Alias: over S_ST, S_TL, S_TM, S_TF and S_TLC -- no call runs two of them
     S_TL = {64, 20, false},   // lorb_track_local_map's staging.  Alias: inside S_ORB's range, as above
     S_TM = {88, 3, false},    // motion chain: pass 2's codes + both counts, the residual list, the host form's codes
     S_TF = {91, 1, false},    // frames chain (which also uses S_TM 0 and 1): the last frame's mp_locked flags

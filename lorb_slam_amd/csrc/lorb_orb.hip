@@ -24,9 +24,9 @@ namespace {
 constexpr int kHalfPatch = 15;
 constexpr int kTileW = 64, kTileH = 16;
 
+// The geometry of a pyramid (every image of a launch shares it) and the constants of the blur and of
+// IC_Angle; the images' own buffers travel beside it (OrbSide, DescSide).
 struct OrbPyr {
-  const uint8_t* data;
-  uint8_t* blur;  // same layout (offsets / steps) as data
   int64_t offset[LORB_MAX_LEVELS];
   int rows[LORB_MAX_LEVELS], cols[LORB_MAX_LEVELS], step[LORB_MAX_LEVELS];
   int tile_off[LORB_MAX_LEVELS + 1];  // first tile of each level
@@ -80,24 +80,19 @@ __device__ __forceinline__ void blur_tile(const OrbPyr& P, const uint8_t* __rest
   }
 }
 
-__global__ __launch_bounds__(256) void k_orb_blur(OrbPyr P) {
-  __shared__ int in[kTileH + 6][kTileW + 6 + 1];
-  __shared__ int rowp[kTileH + 6][kTileW + 1];
-  blur_tile(P, P.data, P.blur, blockIdx.x, in, rowp);
-}
-
-// The second image of a stereo pair (same geometry, its own raw / blurred pyramids): the kernels
-// suffixed 2 run both images in one launch, image = blockIdx.y (blockIdx.z for the resize).
-struct OrbSide2 {
+// Every kernel of this unit runs one image or the two images of a stereo pair (same geometry) in one
+// launch: image = blockIdx.y (blockIdx.z for the resize), a grid dimension of extent 1 or 2.  A
+// one-image launch leaves the second image's arguments zeroed; no workgroup reads them.
+struct OrbSide {
   const uint8_t* data;
-  uint8_t* blur;
+  uint8_t* blur;  // same layout (offsets / steps) as data
 };
 
-__global__ __launch_bounds__(256) void k_orb_blur2(OrbPyr P, OrbSide2 right) {
+__global__ __launch_bounds__(256) void k_orb_blur(OrbPyr P, OrbSide s0, OrbSide s1) {
   __shared__ int in[kTileH + 6][kTileW + 6 + 1];
   __shared__ int rowp[kTileH + 6][kTileW + 1];
-  const bool r = blockIdx.y != 0;
-  blur_tile(P, r ? right.data : P.data, r ? right.blur : P.blur, blockIdx.x, in, rowp);
+  const OrbSide& s = blockIdx.y ? s1 : s0;
+  blur_tile(P, s.data, s.blur, blockIdx.x, in, rowp);
 }
 
 // cv::fastAtan2 (OpenCV 3.1), degrees
@@ -184,20 +179,7 @@ __device__ __forceinline__ void desc_key(const OrbPyr& P, const uint8_t* __restr
   if (lane == 0) angle_out[i] = ang;
 }
 
-__global__ __launch_bounds__(64 * kDescWaves) void k_orb_desc(OrbPyr P, int n, const int* __restrict__ d_n,
-                                                              const float* __restrict__ kx,
-                                                              const float* __restrict__ ky,
-                                                              const int* __restrict__ klev,
-                                                              const int* __restrict__ pattern,
-                                                              float* __restrict__ angle_out,
-                                                              uint8_t* __restrict__ desc_out) {
-  __shared__ int s_pat[1024];
-  for (int e = threadIdx.x; e < 1024; e += 64 * kDescWaves) s_pat[e] = pattern[e];
-  __syncthreads();
-  desc_key(P, P.data, P.blur, n, d_n, kx, ky, klev, s_pat, angle_out, desc_out);
-}
-
-// per-image keypoint arrays of k_orb_desc2 (d_n: that image's device count, never null)
+// per-image keypoint arrays of k_orb_desc (d_n: that image's device count, or null when n is exact)
 struct DescSide {
   const uint8_t* data;
   const uint8_t* blur;
@@ -208,14 +190,15 @@ struct DescSide {
   uint8_t* desc;
 };
 
-// launched over the capacity `cap` per image; a wave at or past its image's count exits in desc_key
-__global__ __launch_bounds__(64 * kDescWaves) void k_orb_desc2(OrbPyr P, int cap, DescSide s0, DescSide s1,
-                                                               const int* __restrict__ pattern) {
+// launched over n keypoints per image: the exact count, or with device counts the capacity (a wave
+// at or past its image's count exits in desc_key)
+__global__ __launch_bounds__(64 * kDescWaves) void k_orb_desc(OrbPyr P, int n, DescSide s0, DescSide s1,
+                                                              const int* __restrict__ pattern) {
   __shared__ int s_pat[1024];
   for (int e = threadIdx.x; e < 1024; e += 64 * kDescWaves) s_pat[e] = pattern[e];
   __syncthreads();
   const DescSide& s = blockIdx.y ? s1 : s0;
-  desc_key(P, s.data, s.blur, cap, s.d_n, s.kx, s.ky, s.klev, s_pat, s.angle, s.desc);
+  desc_key(P, s.data, s.blur, n, s.d_n, s.kx, s.ky, s.klev, s_pat, s.angle, s.desc);
 }
 
 // cv::getGaussianKernel(7, 2, CV_32F) * 256, rounded (convertTo CV_32S, float arithmetic)
@@ -247,7 +230,9 @@ void orb_umax(int* umax) {
   }
 }
 
-int64_t pyr_extent(const lorb_image_pyramid* p) {
+// bytes spanned by a pyramid buffer (a lorb_image_pyramid or its OrbPyr)
+template <typename Pyr>
+int64_t pyr_extent(const Pyr* p) {
   int64_t e = 0;
   for (int l = 0; l < p->n_levels; l++)
     if (p->rows[l] > 0) e = std::max<int64_t>(e, p->offset[l] + (int64_t)(p->rows[l] - 1) * p->step[l] + p->cols[l]);
@@ -264,26 +249,43 @@ int check_orb(lorb_ctx* ctx, const lorb_image_pyramid* p, int n) {
   return LORB_OK;
 }
 
-int enqueue_orb(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const uint8_t* d_data, int n, const int* d_n, const float* d_x,
-                const float* d_y, const int* d_lev, const int* d_pat, float* d_ang, uint8_t* d_desc) {
+// the OrbPyr of a pyramid layout (any row step >= cols): geometry, blur tile table, taps, umax
+OrbPyr orb_geometry(const lorb_image_pyramid& L) {
   OrbPyr P{};
-  P.data = d_data;
-  P.n_levels = pyr->n_levels;
+  P.n_levels = L.n_levels;
   int tiles = 0;
-  for (int l = 0; l < pyr->n_levels; l++) {
-    P.offset[l] = pyr->offset[l]; P.rows[l] = pyr->rows[l]; P.cols[l] = pyr->cols[l]; P.step[l] = pyr->step[l];
+  for (int l = 0; l < L.n_levels; l++) {
+    P.offset[l] = L.offset[l]; P.rows[l] = L.rows[l]; P.cols[l] = L.cols[l]; P.step[l] = L.step[l];
     P.tile_off[l] = tiles;
-    P.tiles_x[l] = (pyr->cols[l] + kTileW - 1) / kTileW;
-    tiles += P.tiles_x[l] * ((pyr->rows[l] + kTileH - 1) / kTileH);
+    P.tiles_x[l] = (L.cols[l] + kTileW - 1) / kTileW;
+    tiles += P.tiles_x[l] * ((L.rows[l] + kTileH - 1) / kTileH);
   }
-  P.tile_off[pyr->n_levels] = tiles;
+  P.tile_off[L.n_levels] = tiles;
   gauss_taps(P.k);
   orb_umax(P.umax);
-  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 0>(), (size_t)pyr_extent(pyr), &P.blur));
-  hipLaunchKernelGGL(k_orb_blur, dim3(tiles), dim3(256), 0, ctx->stream, P);
+  return P;
+}
+
+// One launch site per kernel.  `ni` is the number of images in the launch (1 or 2): the extent of the
+// image grid dimension.  A one-image caller passes null / zeroed arguments for the second image.
+void launch_blur(hipStream_t st, int ni, const OrbPyr& P, const OrbSide& s0, const OrbSide& s1) {
+  hipLaunchKernelGGL(k_orb_blur, dim3(P.tile_off[P.n_levels], ni), dim3(256), 0, st, P, s0, s1);
+}
+
+void launch_desc(hipStream_t st, int ni, const OrbPyr& P, int n, const DescSide& s0, const DescSide& s1,
+                 const int* d_pat) {
   if (n > 0)
-    hipLaunchKernelGGL(k_orb_desc, dim3(lorb::ceil_div(n, kDescWaves)), dim3(64 * kDescWaves), 0, ctx->stream, P, n, d_n,
-                       d_x, d_y, d_lev, d_pat, d_ang, d_desc);
+    hipLaunchKernelGGL(k_orb_desc, dim3(lorb::ceil_div(n, kDescWaves), ni), dim3(64 * kDescWaves), 0, st, P, n, s0, s1,
+                       d_pat);
+}
+
+// blur + describe of one image on the ctx stream; the blurred pyramid is per-call scratch
+int enqueue_describe(lorb_ctx* ctx, const OrbPyr& P, const uint8_t* d_data, int n, const int* d_n, const float* d_x,
+                     const float* d_y, const int* d_lev, const int* d_pat, float* d_ang, uint8_t* d_desc) {
+  uint8_t* blur;
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 0>(), (size_t)pyr_extent(&P), &blur));
+  launch_blur(ctx->stream, 1, P, OrbSide{d_data, blur}, OrbSide{});
+  launch_desc(ctx->stream, 1, P, n, DescSide{d_data, blur, d_n, d_x, d_y, d_lev, d_ang, d_desc}, DescSide{}, d_pat);
   LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
 }
@@ -326,29 +328,21 @@ __device__ __forceinline__ void resize_px(const uint8_t* __restrict__ src, int s
   dst[(int64_t)dy * dstep + dx] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-__global__ __launch_bounds__(256) void k_orb_resize(const uint8_t* __restrict__ src, int sh, int sw, int sstep,
-                                                    uint8_t* __restrict__ dst, int dh, int dw, int dstep,
-                                                    const int* __restrict__ xofs, const short2* __restrict__ ia,
-                                                    const int* __restrict__ yofs, const short2* __restrict__ ib,
-                                                    int xmax, int xs) {
-  resize_px(src, sh, sw, sstep, dst, dh, dw, dstep, xofs, ia, yofs, ib, xmax, xs);
-}
-
-// level l-1 -> level l of both pyramids (blockIdx.z = image; offsets inside the pyramid buffers)
-__global__ __launch_bounds__(256) void k_orb_resize2(uint8_t* __restrict__ pyr0, uint8_t* __restrict__ pyr1,
-                                                     int64_t soff, int sh, int sw, int sstep, int64_t doff, int dh,
-                                                     int dw, int dstep, const int* __restrict__ xofs,
-                                                     const short2* __restrict__ ia, const int* __restrict__ yofs,
-                                                     const short2* __restrict__ ib, int xmax, int xs) {
+// level l-1 -> level l of every pyramid (blockIdx.z = image; offsets inside the pyramid buffers)
+__global__ __launch_bounds__(256) void k_orb_resize(uint8_t* __restrict__ pyr0, uint8_t* __restrict__ pyr1,
+                                                    int64_t soff, int sh, int sw, int sstep, int64_t doff, int dh,
+                                                    int dw, int dstep, const int* __restrict__ xofs,
+                                                    const short2* __restrict__ ia, const int* __restrict__ yofs,
+                                                    const short2* __restrict__ ib, int xmax, int xs) {
   uint8_t* pyr = blockIdx.z ? pyr1 : pyr0;
   resize_px(pyr + soff, sh, sw, sstep, pyr + doff, dh, dw, dstep, xofs, ia, yofs, ib, xmax, xs);
 }
 
-// level 0 of both pyramids: the two images (row strides step0 / step1) packed to `cols` bytes per
-// row; blockIdx.y = image, one thread per pixel
-__global__ __launch_bounds__(256) void k_orb_copy2(const uint8_t* __restrict__ img0, int step0,
-                                                   const uint8_t* __restrict__ img1, int step1, int rows, int cols,
-                                                   uint8_t* __restrict__ pyr0, uint8_t* __restrict__ pyr1) {
+// level 0 of every pyramid: the images (row strides step0 / step1) packed to `cols` bytes per row;
+// blockIdx.y = image, one thread per pixel
+__global__ __launch_bounds__(256) void k_orb_copy(const uint8_t* __restrict__ img0, int step0,
+                                                  const uint8_t* __restrict__ img1, int step1, int rows, int cols,
+                                                  uint8_t* __restrict__ pyr0, uint8_t* __restrict__ pyr1) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= (int64_t)rows * cols) return;
   const int r = (int)(p / cols), c = (int)(p - (int64_t)r * cols);
@@ -402,10 +396,30 @@ int pyramid_layout(int rows, int cols, int n_levels, const float* sf, lorb_image
   return (int)std::min<int64_t>(off, INT32_MAX);
 }
 
-int enqueue_pyramid(lorb_ctx* ctx, const uint8_t* d_img, int rows, int cols, int step, const lorb_image_pyramid& P,
-                    uint8_t* d_out) {
-  LORB_HIP(ctx, hipMemcpy2DAsync(d_out, P.cols[0], d_img, step, P.cols[0], P.rows[0], hipMemcpyDeviceToDevice,
-                                 ctx->stream));
+// the tap tables of one level on the device (resize_tabs; xs = simd_cols of the level's width)
+struct ResizeTabs {
+  int *xofs, *yofs;
+  short2 *ia, *ib;
+  int xmax, xs;
+};
+
+void launch_copy(hipStream_t st, int ni, const uint8_t* img0, int step0, const uint8_t* img1, int step1, int rows,
+                 int cols, uint8_t* pyr0, uint8_t* pyr1) {
+  hipLaunchKernelGGL(k_orb_copy, dim3(lorb::ceil_div((size_t)rows * cols, 256), ni), dim3(256), 0, st, img0, step0, img1,
+                     step1, rows, cols, pyr0, pyr1);
+}
+
+// level l - 1 -> level l of layout L inside each pyramid buffer
+void launch_resize(hipStream_t st, int ni, uint8_t* pyr0, uint8_t* pyr1, const lorb_image_pyramid& L, int l,
+                   const ResizeTabs& T) {
+  hipLaunchKernelGGL(k_orb_resize, dim3(lorb::ceil_div(L.cols[l], 64), lorb::ceil_div(L.rows[l], 4), ni), dim3(256), 0, st,
+                     pyr0, pyr1, L.offset[l - 1], L.rows[l - 1], L.cols[l - 1], L.step[l - 1], L.offset[l], L.rows[l],
+                     L.cols[l], L.step[l], T.xofs, T.ia, T.yofs, T.ib, T.xmax, T.xs);
+}
+
+// The pyramid of one image on the ctx stream, its tap tables staged per call (OrbPair holds them).
+int enqueue_pyramid(lorb_ctx* ctx, const uint8_t* d_img, int step, const lorb_image_pyramid& P, uint8_t* d_out) {
+  launch_copy(ctx->stream, 1, d_img, step, nullptr, 0, P.rows[0], P.cols[0], d_out, nullptr);
   // the tap tables stay alive until the stream has consumed them (synchronised below)
   std::vector<std::vector<int>> keep_i(2 * P.n_levels);
   std::vector<std::vector<short2>> keep_s(2 * P.n_levels);
@@ -427,10 +441,7 @@ int enqueue_pyramid(lorb_ctx* ctx, const uint8_t* d_img, int rows, int cols, int
     LORB_TRY(lorb::upload_t(ctx, tabs[1], ia.data(), ia.size(), &dia));
     LORB_TRY(lorb::upload_t(ctx, tabs[2], yofs.data(), yofs.size(), &dyo));
     LORB_TRY(lorb::upload_t(ctx, tabs[3], ib.data(), ib.size(), &dib));
-    const dim3 grid(lorb::ceil_div(P.cols[l], 64), lorb::ceil_div(P.rows[l], 4));
-    hipLaunchKernelGGL(k_orb_resize, grid, dim3(256), 0, ctx->stream, d_out + P.offset[l - 1], P.rows[l - 1],
-                       P.cols[l - 1], P.step[l - 1], d_out + P.offset[l], P.rows[l], P.cols[l], P.step[l], dxo, dia, dyo,
-                       dib, xmax, simd_cols(P.cols[l]));
+    launch_resize(ctx->stream, 1, d_out, nullptr, P, l, ResizeTabs{dxo, dyo, dia, dib, xmax, simd_cols(P.cols[l])});
   }
   LORB_CHECK_LAUNCH(ctx);
   LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -581,22 +592,14 @@ __device__ __forceinline__ void fast_cell(const uint8_t* __restrict__ data, cons
   if (t == 0) *ocount = run;
 }
 
-__global__ __launch_bounds__(kFastThreads) void k_orb_fast(const uint8_t* __restrict__ data, OrbPyr P,
-                                                           const FastCell* __restrict__ cells, int ini_th, int min_th,
+// every image over one cell table: image blockIdx.y writes its corners fast_cap floats and its cell
+// counts n_cells ints after image 0's
+__global__ __launch_bounds__(kFastThreads) void k_orb_fast(const uint8_t* __restrict__ data0,
+                                                           const uint8_t* __restrict__ data1, OrbPyr P,
+                                                           const FastCell* __restrict__ cells, int n_cells,
+                                                           int fast_cap, int ini_th, int min_th,
                                                            float* __restrict__ ox, float* __restrict__ oy,
                                                            float* __restrict__ oresp, int* __restrict__ ocount) {
-  __shared__ FastSh sh;
-  fast_cell(data, P, cells[blockIdx.x], ini_th, min_th, ox, oy, oresp, ocount + blockIdx.x, sh);
-}
-
-// both images over one cell table: image blockIdx.y writes its corners fast_cap floats and its cell
-// counts n_cells ints after image 0's
-__global__ __launch_bounds__(kFastThreads) void k_orb_fast2(const uint8_t* __restrict__ data0,
-                                                            const uint8_t* __restrict__ data1, OrbPyr P,
-                                                            const FastCell* __restrict__ cells, int n_cells,
-                                                            int fast_cap, int ini_th, int min_th,
-                                                            float* __restrict__ ox, float* __restrict__ oy,
-                                                            float* __restrict__ oresp, int* __restrict__ ocount) {
   __shared__ FastSh sh;
   const int im = blockIdx.y;
   const size_t fo = (size_t)im * fast_cap;
@@ -678,7 +681,6 @@ struct OctArgs {
   lorb::I4* cnt;
   int* out_key;                      // kept key per final node (node_base)
   int* out_cnt;                      // nodes per level, -1: failure (capacity / iteration cap)
-  int* trace;                        // diagnostics (nullable): per level 8 ints per pass, 64 passes
 };
 
 constexpr int kOctThreads = 1024;
@@ -965,13 +967,6 @@ __device__ __forceinline__ void oct_global(const OctArgs& A, OctSh& sh, long lon
     __syncthreads();
     // G. termination (:703-707, :767-768)
     if (t == 0) {
-      if (A.trace && pass < 64) {
-        int* tr = A.trace + (l * 64 + pass) * 72;
-        tr[0] = L; tr[1] = mode; tr[2] = n_act; tr[3] = cm; tr[4] = E; tr[5] = n_surv; tr[6] = newL; tr[7] = n_pend;
-        for (int q = 0; q < 16 && q < newL; q++) {
-          tr[8 + 4 * q] = nxt[q].beg; tr[9 + 4 * q] = nxt[q].end; tr[10 + 4 * q] = nxt[q].x0; tr[11 + 4 * q] = nxt[q].y0;
-        }
-      }
       int state = 0, m = mode;
       if (newL >= V.N || newL == L) state = 1;
       else if (mode == 0 && newL + 3 * n_pend > V.N) m = 1;
@@ -1075,11 +1070,6 @@ __device__ __forceinline__ lorb::I4 oct_wave_base(const OctWaves& ww, int wv) {
 // chunks and waves).  Segment heads are pass-stamped (hd[p] = (pass + 1) << 16 | node): no
 // clearing pass.  The keys are gathered from the cells one thread per key.
 __device__ __forceinline__ void oct_lds(const OctArgs& A, OctSh& sh, OctLds& S, OctWaves& ww, long long* s_key) {
-  // lorb_orb_debug_octree only: cycle stamps of the phases in the trace's spare words
-  const unsigned long long oct_t0 = __builtin_amdgcn_s_memtime();
-  int oct_ns = 0;
-#define OCT_STAMP() do { if (A.trace && threadIdx.x == 0 && oct_ns < 60) \
-    A.trace[A.n_levels * 64 * 72 + blockIdx.x * 16384 + oct_ns++] = (int)(__builtin_amdgcn_s_memtime() - oct_t0); } while (0)
   int* wsum = sh.wsum;
   const int l = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const OctLevel V = A.lv[l];
@@ -1137,7 +1127,6 @@ __device__ __forceinline__ void oct_lds(const OctArgs& A, OctSh& sh, OctLds& S, 
     }
   }
   __syncthreads();  // the keys written above are read by other threads below
-  OCT_STAMP();
   // wave wv sweeps positions [c0, c1), 64 per step
   const int chunk = (n + kOctThreads - 1) / kOctThreads * 64;
   const int c0 = min(n, wv * chunk), c1 = min(n, c0 + chunk);
@@ -1206,7 +1195,6 @@ __device__ __forceinline__ void oct_lds(const OctArgs& A, OctSh& sh, OctLds& S, 
     }
     __syncthreads();
   }
-  OCT_STAMP();
 
   // the owner sweep shared by the passes and the final step: ww.last = each wave's last head
   auto wave_last_head = [&](int stamp) {
@@ -1319,7 +1307,6 @@ __device__ __forceinline__ void oct_lds(const OctArgs& A, OctSh& sh, OctLds& S, 
       }
     }
     __syncthreads();
-    OCT_STAMP();
     // C. children per dividing node; processing order
     for (int i = t; i < L; i += kOctThreads) {
       if (!S.act[i]) { S.ech[i] = 0; continue; }
@@ -1390,7 +1377,6 @@ __device__ __forceinline__ void oct_lds(const OctArgs& A, OctSh& sh, OctLds& S, 
     __syncthreads();
     const int n_surv = oct_scan(S.tmp, L, wsum);  // tmp[i] = survivor rank
     const int newL = E + n_surv;
-    OCT_STAMP();
     if (newL > V.node_cap || newL > kOctNC) { if (t == 0) A.out_cnt[l] = -1; return; }
     // F. the keys in their new positions (stable partition of the divided segments), the new list
     for (int p0 = c0 + lane; p0 < c1; p0 += 64 * kQB) {
@@ -1449,13 +1435,6 @@ __device__ __forceinline__ void oct_lds(const OctArgs& A, OctSh& sh, OctLds& S, 
     __syncthreads();
     // G. termination (:703-707, :767-768)
     if (t == 0) {
-      if (A.trace && pass < 64) {
-        int* tr = A.trace + (l * 64 + pass) * 72;
-        tr[0] = L; tr[1] = mode; tr[2] = n_act; tr[3] = cm; tr[4] = E; tr[5] = n_surv; tr[6] = newL; tr[7] = n_pend;
-        for (int q = 0; q < 16 && q < newL; q++) {
-          tr[8 + 4 * q] = nxt[q].beg; tr[9 + 4 * q] = nxt[q].end; tr[10 + 4 * q] = nxt[q].x0; tr[11 + 4 * q] = nxt[q].y0;
-        }
-      }
       int state = 0, m = mode;
       if (newL >= V.N || newL == L) state = 1;
       else if (mode == 0 && newL + 3 * n_pend > V.N) m = 1;
@@ -1467,7 +1446,6 @@ __device__ __forceinline__ void oct_lds(const OctArgs& A, OctSh& sh, OctLds& S, 
       int* w2 = pxy0; pxy0 = pxy1; pxy1 = w2;
     }
     __syncthreads();
-    OCT_STAMP();
   }
   // 4. the strongest key of each node (:776-794: strict >, so the first of the strongest in vKeys
   //    order): the final segment heads stamped once more, every key's owner as in a pass, and a
@@ -1515,38 +1493,24 @@ __device__ __forceinline__ void oct_lds(const OctArgs& A, OctSh& sh, OctLds& S, 
       A.out_key[V.node_base + i] = pk0[pos];
     }
   }
-  OCT_STAMP();
-#undef OCT_STAMP
   if (t == 0) A.out_cnt[l] = L;
 }
 
-__global__ __launch_bounds__(kOctThreads) void k_orb_octree(OctArgs A) {
-  __shared__ OctSh sh;
-  __shared__ long long s_key[kOctKeyChunk];
-  __shared__ OctLds S;
-  __shared__ OctWaves ww;
-  const OctLevel& V = A.lv[blockIdx.x];
-  // the LDS path when the level's node list and cells fit
-  if (V.node_cap <= kOctNC && V.cell_end - V.cell_begin <= kOctCells)
-    oct_lds(A, sh, S, ww, s_key);
-  else
-    oct_global(A, sh, s_key);
-}
-
-// Both images' quadtrees in one launch: 2 * n_levels workgroups, level = blockIdx.x and image =
-// blockIdx.y (each image has its own OctArgs: the same plan over its own scratch).  The LDS of a
-// workgroup is k_orb_octree's.
-struct OctArgs2 {
+// Each image has its own OctArgs: the same plan over its own scratch (a[1] stays zeroed in a
+// one-image launch).
+struct OctPair {
   OctArgs a[2];
 };
 
-__global__ __launch_bounds__(kOctThreads) void k_orb_octree2(OctArgs2 AA) {
+// Every image's quadtrees in one launch: level = blockIdx.x, image = blockIdx.y.
+__global__ __launch_bounds__(kOctThreads) void k_orb_octree(OctPair AA) {
   __shared__ OctSh sh;
   __shared__ long long s_key[kOctKeyChunk];
   __shared__ OctLds S;
   __shared__ OctWaves ww;
   const OctArgs& A = AA.a[blockIdx.y];
   const OctLevel& V = A.lv[blockIdx.x];
+  // the LDS path when the level's node list and cells fit
   if (V.node_cap <= kOctNC && V.cell_end - V.cell_begin <= kOctCells)
     oct_lds(A, sh, S, ww, s_key);
   else
@@ -1590,16 +1554,6 @@ __device__ __forceinline__ void gather_keys(const OctArgs& A, int cap, float* __
   oct[i] = l; size[i] = V.size; resp[i] = A.kr[V.key_base + k];
 }
 
-__global__ __launch_bounds__(256) void k_orb_gather(OctArgs A, int cap, float* __restrict__ lx, float* __restrict__ ly,
-                                                    float* __restrict__ sx, float* __restrict__ sy,
-                                                    int* __restrict__ oct, float* __restrict__ size,
-                                                    float* __restrict__ resp, int* __restrict__ level_off,
-                                                    int* __restrict__ n_total) {
-  __shared__ int off[LORB_MAX_LEVELS + 1];
-  __shared__ int bad;
-  gather_keys(A, cap, lx, ly, sx, sy, oct, size, resp, level_off, n_total, off, bad);
-}
-
 struct GatherOut {
   float *lx, *ly, *sx, *sy;
   int* oct;
@@ -1607,16 +1561,16 @@ struct GatherOut {
   int *level_off, *n_total;
 };
 
-// both images (blockIdx.y), each into its own outputs; n_total is that image's entry of counts[2]
-__global__ __launch_bounds__(256) void k_orb_gather2(OctArgs2 AA, int cap, GatherOut o0, GatherOut o1) {
+// every image (blockIdx.y) into its own outputs; n_total is that image's device count
+__global__ __launch_bounds__(256) void k_orb_gather(OctPair AA, int cap, GatherOut o0, GatherOut o1) {
   __shared__ int off[LORB_MAX_LEVELS + 1];
   __shared__ int bad;
   const GatherOut& o = blockIdx.y ? o1 : o0;
   gather_keys(AA.a[blockIdx.y], cap, o.lx, o.ly, o.sx, o.sy, o.oct, o.size, o.resp, o.level_off, o.n_total, off, bad);
 }
 
-// Host plan of the keypoint stage: cells, capacities and the octree arguments (device pointers are
-// filled by orb_alloc).
+// Host plan of the keypoint stage: cells, capacities and the per-level part of the octree arguments
+// (A's device pointers stay null: orb_alloc / orb_pair_create set them in their own copies).
 struct OrbPlan {
   std::vector<FastCell> cells;
   int fast_cap = 0, key_total = 0, node_total = 0, out_cap = 0;
@@ -1668,20 +1622,55 @@ int orb_plan(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const int32_t* n_desi
   return LORB_OK;
 }
 
-// allocates the scratch of a plan (S_ORB slots 20 ..) and fills the device pointers of P->A
-int orb_alloc(lorb_ctx* ctx, OrbPlan* P, FastCell** d_cells, int** d_cnt) {
-  OctArgs& A = P->A;
-  const size_t K = (size_t)std::max(P->key_total, 1), NN = (size_t)std::max(P->node_total, 1);
-  const size_t F = (size_t)std::max(P->fast_cap, 1);
-  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 20>(), P->cells.data(), P->cells.size(), d_cells));
-  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 21>(), std::max<size_t>(P->cells.size(), 1), d_cnt));
-  float *fx, *fy, *fr, *kx, *ky, *kr;
-  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 22>(), F, &fx));
-  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 23>(), F, &fy));
-  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 24>(), F, &fr));
-  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 25>(), K, &kx));
-  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 26>(), K, &ky));
-  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 27>(), K, &kr));
+// Device side of the keypoint stage of one or two images: the cell table they share, FAST's output
+// (image im writes fast_cap floats / n_cells counts after image 0's) and each image's quadtree arguments.
+struct OrbKeys {
+  FastCell* cells;
+  int n_cells, fast_cap;
+  float *fx, *fy, *fr;
+  int* cnt;
+  OctPair AA;
+};
+
+void launch_fast(hipStream_t st, int ni, const uint8_t* data0, const uint8_t* data1, const OrbPyr& P, const OrbKeys& K,
+                 int ini_th, int min_th) {
+  if (K.n_cells)
+    hipLaunchKernelGGL(k_orb_fast, dim3((unsigned)K.n_cells, ni), dim3(kFastThreads), 0, st, data0, data1, P, K.cells,
+                       K.n_cells, K.fast_cap, ini_th, min_th, K.fx, K.fy, K.fr, K.cnt);
+}
+
+void launch_octree(hipStream_t st, int ni, const OrbKeys& K) {
+  hipLaunchKernelGGL(k_orb_octree, dim3(K.AA.a[0].n_levels, ni), dim3(kOctThreads), 0, st, K.AA);
+}
+
+void launch_gather(hipStream_t st, int ni, const OrbKeys& K, int cap, const GatherOut& o0, const GatherOut& o1) {
+  hipLaunchKernelGGL(k_orb_gather, dim3(lorb::ceil_div(cap, 256), ni), dim3(256), 0, st, K.AA, cap, o0, o1);
+}
+
+// FAST cells + DistributeOctTree of every level (device pyramids)
+void launch_keypoints(hipStream_t st, int ni, const uint8_t* data0, const uint8_t* data1, const OrbPyr& P,
+                      const OrbKeys& K, int ini_th, int min_th) {
+  launch_fast(st, ni, data0, data1, P, K, ini_th, min_th);
+  launch_octree(st, ni, K);
+}
+
+// one image's OrbKeys over the scratch of the ctx (S_ORB slots 20 ..); uploads the plan's cells
+int orb_alloc(lorb_ctx* ctx, const OrbPlan& P, OrbKeys* keys) {
+  *keys = OrbKeys{};
+  keys->n_cells = (int)P.cells.size();
+  keys->fast_cap = std::max(P.fast_cap, 1);
+  OctArgs& A = keys->AA.a[0];
+  A = P.A;
+  const size_t K = (size_t)std::max(P.key_total, 1), NN = (size_t)std::max(P.node_total, 1);
+  const size_t F = (size_t)keys->fast_cap;
+  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 20>(), P.cells.data(), P.cells.size(), &keys->cells));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 21>(), std::max<size_t>(P.cells.size(), 1), &keys->cnt));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 22>(), F, &keys->fx));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 23>(), F, &keys->fy));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 24>(), F, &keys->fr));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 25>(), K, &A.kx));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 26>(), K, &A.ky));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 27>(), K, &A.kr));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 28>(), K, &A.perm));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 29>(), K, &A.perm2));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 30>(), K, &A.cls));
@@ -1698,25 +1687,8 @@ int orb_alloc(lorb_ctx* ctx, OrbPlan* P, FastCell** d_cells, int** d_cnt) {
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 41>(), NN, &A.cnt));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 42>(), NN, &A.out_key));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 43>(), (size_t)LORB_MAX_LEVELS, &A.out_cnt));
-  A.cells = *d_cells; A.cell_cnt = *d_cnt;
-  A.fx = fx; A.fy = fy; A.fr = fr; A.kx = kx; A.ky = ky; A.kr = kr;
-  return LORB_OK;
-}
-
-// FAST cells + DistributeOctTree of every level, enqueued on the ctx stream (device pyramid)
-int enqueue_keypoints(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const uint8_t* d_data, OrbPlan* P, int ini_th,
-                      int min_th) {
-  FastCell* dcells;
-  int* dcnt;
-  LORB_TRY(orb_alloc(ctx, P, &dcells, &dcnt));
-  OrbPyr Q{};
-  for (int l = 0; l < pyr->n_levels; l++) { Q.offset[l] = pyr->offset[l]; Q.step[l] = pyr->step[l]; }
-  if (!P->cells.empty())
-    hipLaunchKernelGGL(k_orb_fast, dim3((unsigned)P->cells.size()), dim3(kFastThreads), 0, ctx->stream, d_data, Q,
-                       dcells, ini_th, min_th, const_cast<float*>(P->A.fx), const_cast<float*>(P->A.fy),
-                       const_cast<float*>(P->A.fr), dcnt);
-  hipLaunchKernelGGL(k_orb_octree, dim3(pyr->n_levels), dim3(kOctThreads), 0, ctx->stream, P->A);
-  LORB_CHECK_LAUNCH(ctx);
+  A.cells = keys->cells; A.cell_cnt = keys->cnt;
+  A.fx = keys->fx; A.fy = keys->fy; A.fr = keys->fr;
   return LORB_OK;
 }
 
@@ -1731,7 +1703,8 @@ int lorb_orb_describe_dev(lorb_ctx* ctx, const lorb_image_pyramid* d_pyr, int32_
   LORB_TRY(check_orb(ctx, d_pyr, n));
   if (n > 0 && (!d_x || !d_y || !d_level || !d_pattern || !d_angle || !d_desc))
     return lorb::set_error(ctx, LORB_E_INVALID, "null keypoint / pattern / output array");
-  return enqueue_orb(ctx, d_pyr, d_pyr->data, n, nullptr, d_x, d_y, d_level, d_pattern, d_angle, d_desc);
+  return enqueue_describe(ctx, orb_geometry(*d_pyr), d_pyr->data, n, nullptr, d_x, d_y, d_level, d_pattern, d_angle,
+                          d_desc);
 }
 
 int lorb_orb_describe(lorb_ctx* ctx, const lorb_image_pyramid* pyr, int32_t n, const float* x, const float* y,
@@ -1762,7 +1735,7 @@ int lorb_orb_describe(lorb_ctx* ctx, const lorb_image_pyramid* pyr, int32_t n, c
   LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 5>(), pattern, (size_t)1024, &dp));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 6>(), (size_t)std::max(n, 1), &dang));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 7>(), (size_t)std::max(n, 1) * 32, &ddesc));
-  LORB_TRY(enqueue_orb(ctx, pyr, dd, n, nullptr, dx, dy, dl, dp, dang, ddesc));
+  LORB_TRY(enqueue_describe(ctx, orb_geometry(*pyr), dd, n, nullptr, dx, dy, dl, dp, dang, ddesc));
   if (n > 0) {
     LORB_HIP(ctx, hipMemcpyAsync(angle, dang, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
     LORB_HIP(ctx, hipMemcpyAsync(desc, ddesc, (size_t)32 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1787,7 +1760,7 @@ int lorb_orb_pyramid(lorb_ctx* ctx, const uint8_t* image, int32_t rows, int32_t 
   uint8_t *dimg, *dout;
   LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 16>(), image, (size_t)(rows - 1) * step + cols, &dimg));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 17>(), (size_t)need, &dout));
-  LORB_TRY(enqueue_pyramid(ctx, dimg, rows, cols, step, *layout, dout));
+  LORB_TRY(enqueue_pyramid(ctx, dimg, step, *layout, dout));
   LORB_HIP(ctx, hipMemcpyAsync(out, dout, (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
   LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   layout->data = out;
@@ -1807,7 +1780,7 @@ int lorb_orb_pyramid_dev(lorb_ctx* ctx, const uint8_t* d_image, int32_t rows, in
       return lorb::set_error(ctx, LORB_E_INVALID, "level %d smaller than 2 x 2", l);
   if (out_bytes < need) return lorb::set_error(ctx, LORB_E_INVALID, "out holds %lld bytes, %lld needed",
                                                (long long)out_bytes, (long long)need);
-  LORB_TRY(enqueue_pyramid(ctx, d_image, rows, cols, step, *layout, d_out));
+  LORB_TRY(enqueue_pyramid(ctx, d_image, step, *layout, d_out));
   layout->data = d_out;
   return LORB_OK;
 }
@@ -1836,26 +1809,20 @@ int lorb_orb_fast_cells(lorb_ctx* ctx, const lorb_image_pyramid* pyr, int32_t in
     return lorb::set_error(ctx, LORB_E_INVALID, "null argument");
   OrbPlan P;
   LORB_TRY(plan_fast_only(ctx, pyr, &P));
-  FastCell* dcells;
-  int* dcnt;
+  OrbKeys K;
   uint8_t* dd;
-  LORB_TRY(orb_alloc(ctx, &P, &dcells, &dcnt));
+  LORB_TRY(orb_alloc(ctx, P, &K));
   LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 1>(), pyr->data, (size_t)pyr_extent(pyr), &dd));
-  OrbPyr Q{};
-  for (int l = 0; l < pyr->n_levels; l++) { Q.offset[l] = pyr->offset[l]; Q.step[l] = pyr->step[l]; }
-  if (!P.cells.empty())
-    hipLaunchKernelGGL(k_orb_fast, dim3((unsigned)P.cells.size()), dim3(kFastThreads), 0, ctx->stream, dd, Q, dcells,
-                       ini_th, min_th, const_cast<float*>(P.A.fx), const_cast<float*>(P.A.fy),
-                       const_cast<float*>(P.A.fr), dcnt);
+  launch_fast(ctx->stream, 1, dd, nullptr, orb_geometry(*pyr), K, ini_th, min_th);
   LORB_CHECK_LAUNCH(ctx);
-  const size_t nc = P.cells.size(), F = (size_t)std::max(P.fast_cap, 1);
+  const size_t nc = P.cells.size(), F = (size_t)K.fast_cap;
   std::vector<int> cnt(std::max<size_t>(nc, 1));
   std::vector<float> hx(F), hy(F), hr(F);
   if (nc) {
-    LORB_HIP(ctx, hipMemcpyAsync(cnt.data(), dcnt, sizeof(int) * nc, hipMemcpyDeviceToHost, ctx->stream));
-    LORB_HIP(ctx, hipMemcpyAsync(hx.data(), P.A.fx, sizeof(float) * F, hipMemcpyDeviceToHost, ctx->stream));
-    LORB_HIP(ctx, hipMemcpyAsync(hy.data(), P.A.fy, sizeof(float) * F, hipMemcpyDeviceToHost, ctx->stream));
-    LORB_HIP(ctx, hipMemcpyAsync(hr.data(), P.A.fr, sizeof(float) * F, hipMemcpyDeviceToHost, ctx->stream));
+    LORB_HIP(ctx, hipMemcpyAsync(cnt.data(), K.cnt, sizeof(int) * nc, hipMemcpyDeviceToHost, ctx->stream));
+    LORB_HIP(ctx, hipMemcpyAsync(hx.data(), K.fx, sizeof(float) * F, hipMemcpyDeviceToHost, ctx->stream));
+    LORB_HIP(ctx, hipMemcpyAsync(hy.data(), K.fy, sizeof(float) * F, hipMemcpyDeviceToHost, ctx->stream));
+    LORB_HIP(ctx, hipMemcpyAsync(hr.data(), K.fr, sizeof(float) * F, hipMemcpyDeviceToHost, ctx->stream));
   }
   LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // the whole grid of every level (skipped cells hold no keypoint), level coordinates
@@ -1901,7 +1868,10 @@ int lorb_orb_detect(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const int32_t*
   LORB_TRY(orb_plan(ctx, pyr, n_desired, scale_factors, &P));
   uint8_t* dd;
   LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 1>(), pyr->data, (size_t)pyr_extent(pyr), &dd));
-  LORB_TRY(enqueue_keypoints(ctx, pyr, dd, &P, ini_th, min_th));
+  OrbKeys K;
+  LORB_TRY(orb_alloc(ctx, P, &K));
+  launch_keypoints(ctx->stream, 1, dd, nullptr, orb_geometry(*pyr), K, ini_th, min_th);
+  LORB_CHECK_LAUNCH(ctx);
   const size_t cap = (size_t)std::max(P.out_cap, 1);
   float *lx, *ly, *sx, *sy, *sz, *rs;
   int *oc, *lo, *nt;
@@ -1914,8 +1884,7 @@ int lorb_orb_detect(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const int32_t*
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 3>(), cap, &oc));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 4>(), (size_t)LORB_MAX_LEVELS + 1, &lo));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 5>(), (size_t)1, &nt));
-  hipLaunchKernelGGL(k_orb_gather, dim3(lorb::ceil_div(cap, 256)), dim3(256), 0, ctx->stream, P.A, (int)cap, lx, ly, sx,
-                     sy, oc, sz, rs, lo, nt);
+  launch_gather(ctx->stream, 1, K, (int)cap, GatherOut{lx, ly, sx, sy, oc, sz, rs, lo, nt}, GatherOut{});
   LORB_CHECK_LAUNCH(ctx);
   int n = 0;
   LORB_HIP(ctx, hipMemcpyAsync(&n, nt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1932,27 +1901,6 @@ int lorb_orb_detect(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const int32_t*
     LORB_HIP(ctx, hipMemcpyAsync(size, sz, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
     LORB_HIP(ctx, hipMemcpyAsync(response, rs, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
   }
-  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return LORB_OK;
-}
-
-// diagnostics: lorb_orb_detect with the per-pass trace of the device quadtree (8 ints per pass:
-// L, mode, dividing nodes, divided, new children, survivors, new L, pending children; 64 passes
-// per level; trace holds n_levels * 512 ints)
-int lorb_orb_debug_octree(lorb_ctx* ctx, const lorb_image_pyramid* pyr, const int32_t* n_desired,
-                          const float* scale_factors, int32_t ini_th, int32_t min_th, int32_t* trace) {
-  if (!ctx || !trace) return LORB_E_INVALID;
-  LORB_TRY(check_orb(ctx, pyr, 0));
-  OrbPlan P;
-  LORB_TRY(orb_plan(ctx, pyr, n_desired, scale_factors, &P));
-  uint8_t* dd;
-  int* dtr;
-  LORB_TRY(lorb::upload_t(ctx, slot<S_ORB, 1>(), pyr->data, (size_t)pyr_extent(pyr), &dd));
-  LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 50>(), (size_t)pyr->n_levels * (64 * 72 + 16384), &dtr));
-  LORB_HIP(ctx, hipMemsetAsync(dtr, 0, sizeof(int) * pyr->n_levels * (64 * 72 + 16384), ctx->stream));
-  P.A.trace = dtr;
-  LORB_TRY(enqueue_keypoints(ctx, pyr, dd, &P, ini_th, min_th));
-  LORB_HIP(ctx, hipMemcpyAsync(trace, dtr, sizeof(int) * pyr->n_levels * (64 * 72 + 16384), hipMemcpyDeviceToHost, ctx->stream));
   LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return LORB_OK;
 }
@@ -1993,26 +1941,19 @@ int lorb_orb_extract_dev(lorb_ctx* ctx, const uint8_t* d_image, int32_t rows, in
   if (max_keypoints < P.out_cap)
     return lorb::set_error(ctx, LORB_E_INVALID, "max_keypoints %d below the extractor's bound %d (lorb_orb_extract_capacity)",
                            max_keypoints, P.out_cap);
-  FastCell* dcells;
-  int* dcnt;
-  LORB_TRY(orb_alloc(ctx, &P, &dcells, &dcnt));  // uploads the cells; the pyramid's sync covers them
-  LORB_TRY(enqueue_pyramid(ctx, d_image, rows, cols, step, pyr, d_pyramid));
-  pyr.data = d_pyramid;
-  OrbPyr Q{};
-  for (int l = 0; l < n_levels; l++) { Q.offset[l] = pyr.offset[l]; Q.step[l] = pyr.step[l]; }
-  if (!P.cells.empty())
-    hipLaunchKernelGGL(k_orb_fast, dim3((unsigned)P.cells.size()), dim3(kFastThreads), 0, ctx->stream, d_pyramid, Q,
-                       dcells, ini_th, min_th, const_cast<float*>(P.A.fx), const_cast<float*>(P.A.fy),
-                       const_cast<float*>(P.A.fr), dcnt);
-  hipLaunchKernelGGL(k_orb_octree, dim3(n_levels), dim3(kOctThreads), 0, ctx->stream, P.A);
+  OrbKeys K;
+  LORB_TRY(orb_alloc(ctx, P, &K));  // uploads the cells; the pyramid's sync covers them
+  LORB_TRY(enqueue_pyramid(ctx, d_image, step, pyr, d_pyramid));
+  const OrbPyr G = orb_geometry(pyr);
+  launch_keypoints(ctx->stream, 1, d_pyramid, nullptr, G, K, ini_th, min_th);
   const size_t cap = (size_t)P.out_cap;
   float *lx, *ly;
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 44>(), cap, &lx));
   LORB_TRY(lorb::scratch_t(ctx, slot<S_ORB, 45>(), cap, &ly));
-  hipLaunchKernelGGL(k_orb_gather, dim3(lorb::ceil_div(cap, 256)), dim3(256), 0, ctx->stream, P.A, (int)cap, lx, ly, d_x,
-                     d_y, d_octave, d_size, d_response, d_level_off, d_n);
+  launch_gather(ctx->stream, 1, K, (int)cap, GatherOut{lx, ly, d_x, d_y, d_octave, d_size, d_response, d_level_off, d_n},
+                GatherOut{});
   LORB_CHECK_LAUNCH(ctx);
-  return enqueue_orb(ctx, &pyr, d_pyramid, (int)cap, d_n, lx, ly, d_octave, d_pattern, d_angle, d_desc);
+  return enqueue_describe(ctx, G, d_pyramid, (int)cap, d_n, lx, ly, d_octave, d_pattern, d_angle, d_desc);
 }
 
 int lorb_orb_extract(lorb_ctx* ctx, const uint8_t* image, int32_t rows, int32_t cols, int32_t step, int32_t n_levels,
@@ -2069,8 +2010,9 @@ int lorb_orb_extract(lorb_ctx* ctx, const uint8_t* image, int32_t rows, int32_t 
 // ---- the extractor over a stereo pair (lorb_frame.hip's builder) ---------------------------
 // Everything that depends only on the geometry is built once: the pyramid layout, the resize tap
 // tables of every level, the FAST cell table, the quadtree plan, the blur tiles, the pattern, and
-// the scratch of both images.  A frame is then 13 launches with the image as a grid dimension and
-// no host work beyond them: copy, n_levels - 1 resizes, FAST, quadtree, gather, blur, describe.
+// the scratch of both images.  A frame is then 13 launches of the same kernels and launch sites as one
+// image's, the image grid dimension at extent 2, and no host work beyond them: copy, n_levels - 1
+// resizes, FAST, quadtree, gather, blur, describe.
 namespace lorb {
 
 struct OrbPair {
@@ -2078,17 +2020,9 @@ struct OrbPair {
   lorb_image_pyramid layout{};
   int64_t pyr_bytes = 0;
   OrbPlan plan;
-  OctArgs2 AA{};
-  OrbPyr P{};  // offsets, tiles, taps, umax (data / blur are set per call)
-  int tiles = 0, n_cells = 0;
-  struct Level {
-    int *xofs, *yofs;
-    short2 *ia, *ib;
-    int xmax, xs;
-  } lvl[LORB_MAX_LEVELS] = {};
-  FastCell* d_cells = nullptr;
-  int* d_cnt = nullptr;
-  float *fx = nullptr, *fy = nullptr, *fr = nullptr;
+  OrbKeys keys{};
+  OrbPyr P{};
+  ResizeTabs lvl[LORB_MAX_LEVELS] = {};
   uint8_t* blur[2] = {};
   float *lx[2] = {}, *ly[2] = {};
   int* d_pat = nullptr;
@@ -2115,32 +2049,24 @@ int orb_pair_create(lorb_ctx* ctx, int rows, int cols, int n_levels, const float
   B->pyr_bytes = pyramid_layout(rows, cols, n_levels, sf, &B->layout);
   LORB_TRY(orb_plan(ctx, &B->layout, n_desired, sf, &B->plan));
   const lorb_image_pyramid& L = B->layout;
-  OrbPyr& P = B->P;
-  P.n_levels = n_levels;
-  for (int l = 0; l < n_levels; l++) {
-    P.offset[l] = L.offset[l]; P.rows[l] = L.rows[l]; P.cols[l] = L.cols[l]; P.step[l] = L.step[l];
-    P.tile_off[l] = B->tiles;
-    P.tiles_x[l] = (L.cols[l] + kTileW - 1) / kTileW;
-    B->tiles += P.tiles_x[l] * ((L.rows[l] + kTileH - 1) / kTileH);
-  }
-  P.tile_off[n_levels] = B->tiles;
-  gauss_taps(P.k);
-  orb_umax(P.umax);
+  B->P = orb_geometry(L);
   // device memory: one block
   Arena& M = B->arena;
-  OrbPlan& Q = B->plan;
-  B->n_cells = (int)Q.cells.size();
+  const OrbPlan& Q = B->plan;
+  OrbKeys& D = B->keys;
+  D.n_cells = (int)Q.cells.size();
+  D.fast_cap = std::max(Q.fast_cap, 1);
   const size_t K = (size_t)std::max(Q.key_total, 1), NN = (size_t)std::max(Q.node_total, 1);
-  const size_t F = (size_t)std::max(Q.fast_cap, 1), NC = (size_t)std::max(B->n_cells, 1);
+  const size_t F = (size_t)D.fast_cap, NC = (size_t)std::max(D.n_cells, 1);
   for (int l = 1; l < n_levels; l++) {
     M.add(&B->lvl[l].xofs, (size_t)L.cols[l]); M.add(&B->lvl[l].ia, (size_t)L.cols[l]);
     M.add(&B->lvl[l].yofs, (size_t)L.rows[l]); M.add(&B->lvl[l].ib, (size_t)L.rows[l]);
   }
-  M.add(&B->d_cells, NC); M.add(&B->d_cnt, 2 * NC);
-  M.add(&B->fx, 2 * F); M.add(&B->fy, 2 * F); M.add(&B->fr, 2 * F);
+  M.add(&D.cells, NC); M.add(&D.cnt, 2 * NC);
+  M.add(&D.fx, 2 * F); M.add(&D.fy, 2 * F); M.add(&D.fr, 2 * F);
   M.add(&B->d_pat, (size_t)1024);
   for (int im = 0; im < 2; im++) {
-    OctArgs& A = B->AA.a[im];
+    OctArgs& A = D.AA.a[im];
     A = Q.A;
     M.add(&A.kx, K); M.add(&A.ky, K); M.add(&A.kr, K);
     M.add(&A.perm, K); M.add(&A.perm2, K); M.add(&A.cls, K); M.add(&A.own, K); M.add(&A.hd, K);
@@ -2153,10 +2079,9 @@ int orb_pair_create(lorb_ctx* ctx, int rows, int cols, int n_levels, const float
   }
   LORB_HIP(ctx, M.commit());
   for (int im = 0; im < 2; im++) {
-    OctArgs& A = B->AA.a[im];
-    A.cells = B->d_cells; A.cell_cnt = B->d_cnt + im * NC;
-    A.fx = B->fx + im * F; A.fy = B->fy + im * F; A.fr = B->fr + im * F;
-    A.trace = nullptr;
+    OctArgs& A = D.AA.a[im];
+    A.cells = D.cells; A.cell_cnt = D.cnt + im * NC;
+    A.fx = D.fx + im * F; A.fy = D.fy + im * F; A.fr = D.fr + im * F;
   }
   // the tables (blocking copies: create is not on the per-frame path)
   for (int l = 1; l < n_levels; l++) {
@@ -2170,8 +2095,8 @@ int orb_pair_create(lorb_ctx* ctx, int rows, int cols, int n_levels, const float
     LORB_HIP(ctx, hipMemcpy(B->lvl[l].yofs, yofs.data(), sizeof(int) * yofs.size(), hipMemcpyHostToDevice));
     LORB_HIP(ctx, hipMemcpy(B->lvl[l].ib, ib.data(), sizeof(short2) * ib.size(), hipMemcpyHostToDevice));
   }
-  if (B->n_cells)
-    LORB_HIP(ctx, hipMemcpy(B->d_cells, Q.cells.data(), sizeof(FastCell) * Q.cells.size(), hipMemcpyHostToDevice));
+  if (D.n_cells)
+    LORB_HIP(ctx, hipMemcpy(D.cells, Q.cells.data(), sizeof(FastCell) * Q.cells.size(), hipMemcpyHostToDevice));
   LORB_HIP(ctx, hipMemcpy(B->d_pat, pattern, sizeof(int) * 1024, hipMemcpyHostToDevice));
   guard.b = nullptr;
   *out = B;
@@ -2189,30 +2114,16 @@ int orb_pair_enqueue(lorb_ctx* ctx, OrbPair* B, const uint8_t* d_img0, int step0
   const lorb_image_pyramid& L = B->layout;
   const int cap = B->plan.out_cap;
   hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(k_orb_copy2, dim3(ceil_div((size_t)B->rows * B->cols, 256), 2), dim3(256), 0, st, d_img0, step0,
-                     d_img1, step1, B->rows, B->cols, o0.pyramid, o1.pyramid);
-  for (int l = 1; l < B->n_levels; l++) {
-    const OrbPair::Level& T = B->lvl[l];
-    hipLaunchKernelGGL(k_orb_resize2, dim3(ceil_div(L.cols[l], 64), ceil_div(L.rows[l], 4), 2), dim3(256), 0, st,
-                       o0.pyramid, o1.pyramid, L.offset[l - 1], L.rows[l - 1], L.cols[l - 1], L.step[l - 1], L.offset[l],
-                       L.rows[l], L.cols[l], L.step[l], T.xofs, T.ia, T.yofs, T.ib, T.xmax, T.xs);
-  }
-  OrbPyr P = B->P;
-  P.data = o0.pyramid;
-  P.blur = B->blur[0];
-  if (B->n_cells)
-    hipLaunchKernelGGL(k_orb_fast2, dim3((unsigned)B->n_cells, 2), dim3(kFastThreads), 0, st, o0.pyramid, o1.pyramid, P,
-                       B->d_cells, B->n_cells, std::max(B->plan.fast_cap, 1), B->ini_th, B->min_th, B->fx, B->fy, B->fr,
-                       B->d_cnt);
-  hipLaunchKernelGGL(k_orb_octree2, dim3(B->n_levels, 2), dim3(kOctThreads), 0, st, B->AA);
-  const GatherOut g0{B->lx[0], B->ly[0], o0.x, o0.y, o0.octave, o0.size, o0.response, o0.level_off, d_counts};
-  const GatherOut g1{B->lx[1], B->ly[1], o1.x, o1.y, o1.octave, o1.size, o1.response, o1.level_off, d_counts + 1};
-  hipLaunchKernelGGL(k_orb_gather2, dim3(ceil_div(cap, 256), 2), dim3(256), 0, st, B->AA, cap, g0, g1);
-  hipLaunchKernelGGL(k_orb_blur2, dim3(B->tiles, 2), dim3(256), 0, st, P, OrbSide2{o1.pyramid, B->blur[1]});
-  const DescSide s0{o0.pyramid, B->blur[0], d_counts, B->lx[0], B->ly[0], o0.octave, o0.angle, o0.desc};
-  const DescSide s1{o1.pyramid, B->blur[1], d_counts + 1, B->lx[1], B->ly[1], o1.octave, o1.angle, o1.desc};
-  hipLaunchKernelGGL(k_orb_desc2, dim3(ceil_div(cap, kDescWaves), 2), dim3(64 * kDescWaves), 0, st, P, cap, s0, s1,
-                     B->d_pat);
+  launch_copy(st, 2, d_img0, step0, d_img1, step1, B->rows, B->cols, o0.pyramid, o1.pyramid);
+  for (int l = 1; l < B->n_levels; l++) launch_resize(st, 2, o0.pyramid, o1.pyramid, L, l, B->lvl[l]);
+  launch_keypoints(st, 2, o0.pyramid, o1.pyramid, B->P, B->keys, B->ini_th, B->min_th);
+  launch_gather(st, 2, B->keys, cap,
+                GatherOut{B->lx[0], B->ly[0], o0.x, o0.y, o0.octave, o0.size, o0.response, o0.level_off, d_counts},
+                GatherOut{B->lx[1], B->ly[1], o1.x, o1.y, o1.octave, o1.size, o1.response, o1.level_off, d_counts + 1});
+  launch_blur(st, 2, B->P, OrbSide{o0.pyramid, B->blur[0]}, OrbSide{o1.pyramid, B->blur[1]});
+  launch_desc(st, 2, B->P, cap,
+              DescSide{o0.pyramid, B->blur[0], d_counts, B->lx[0], B->ly[0], o0.octave, o0.angle, o0.desc},
+              DescSide{o1.pyramid, B->blur[1], d_counts + 1, B->lx[1], B->ly[1], o1.octave, o1.angle, o1.desc}, B->d_pat);
   LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
 }

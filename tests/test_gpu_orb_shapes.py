@@ -16,6 +16,7 @@ import golden_io
 import oracle as O
 import lorb_slam_amd.window as W
 from lorb_slam_amd import synth
+from lorb_slam_amd.frame import FrameBuilder
 from lorb_slam_amd.runtime import LorbError
 
 pytestmark = pytest.mark.gpu
@@ -164,6 +165,40 @@ def test_extract_dev(ctx, row):
     assert sentinel_intact(d["raw"]["level_off"], len(c["sf"]) + 1) and sentinel_intact(d["raw"]["n"], 1)
     assert len(d["raw_pyramid"]) == pb + W.ORB_GUARD and sentinel_intact(d["raw_pyramid"], pb)
     assert np.array_equal(d["raw_pyramid"][:pb], np.concatenate([p.reshape(-1) for p in c["pyr"]]))
+
+
+def check_extract_dev(ctx, row, what):
+    c = case(row)
+    d = extract(ctx, row, device_resident=True)
+    assert d["n"] == len(c["o"]["x"]), what
+    assert_same(d, c["o"], what=what)
+    for k in ("x", "y", "octave", "size", "angle", "response", "desc"):
+        assert sentinel_intact(d["raw"][k], d["n"]), (what, k)
+    assert sentinel_intact(d["raw"]["level_off"], len(c["sf"]) + 1) and sentinel_intact(d["raw"]["n"], 1), what
+    assert sentinel_intact(d["raw_pyramid"], d["pyramid_bytes"]), what
+
+
+@pytest.mark.parametrize("row", [11, 9])
+def test_extract_dev_around_frame_build(ctx, row):
+    """A one-image call launches the stereo pair's kernels with the image grid dimension at extent 1
+    and the second image's arguments zeroed.  lorb_orb_extract_dev twice on one context, with a
+    FrameBuilder build of another geometry (120 x 160, 3 levels, both images) in between: both calls
+    equal the oracle with every sentinel intact, and so does the pair."""
+    guard(row)
+    assert case(row)["img"].shape != (120, 160)
+    check_extract_dev(ctx, row, "before the pair")
+    left, right = synth.stereo_pair(500, 120, 160)
+    sf, nd = synth.scale_factors(n_levels=3), O.orb_features_per_level(200)[:3]
+    fb = FrameBuilder(ctx, dict(synth.frame_params(width=160, height=120), n_levels=3), 120, 160, nd, pattern())
+    try:
+        f = fb.build(left, right, device_resident=True)
+    finally:
+        fb.close()
+    for side, img in (("left", left), ("right", right)):
+        o = O.orb_extract(img, nd, sf, pattern())
+        assert len(o["x"]) > 0
+        assert_same(f[side], o, what=side)
+    check_extract_dev(ctx, row, "after the pair")
 
 
 @pytest.mark.parametrize("shape", [(333, 517), (300, 813)])

@@ -3,7 +3,8 @@ src/ORBextractor.cpp:1087-1151) through lorb_orb_extract_dev on a resident 752x4
 back-to-back frames between HIP events on the ctx stream, the per-frame wall time of the same calls
 with a stream sync after each frame, and the host-API lorb_orb_extract (H2D + D2H per call) for
 comparison.  Run under rocprofv3 --kernel-trace --stats for the per-kernel split
-(k_orb_resize / k_orb_fast / k_orb_octree / k_orb_blur / k_orb_desc).
+(k_orb_copy / k_orb_resize / k_orb_fast / k_orb_octree / k_orb_gather / k_orb_blur / k_orb_desc, the
+kernels of the stereo Frame builder at one image per launch).
 usage: python tools/time_orb.py [--frames N] [--features 1000]"""
 import argparse
 import ctypes as C

@@ -92,6 +92,115 @@ def search_by_projection_local(fp, kps, slot_state, pts, th):  # src/matcher.cpp
     return assign, nm
 
 
+def compute_three_maxima(hist):  # src/matcher.cpp:387-428
+    max1 = max2 = max3 = 0
+    ind1 = ind2 = ind3 = -1
+    for i, s in enumerate(hist):
+        s = int(s)
+        if s > max1:
+            max3, max2, max1 = max2, max1, s
+            ind3, ind2, ind1 = ind2, ind1, i
+        elif s > max2:
+            max3, max2 = max2, s
+            ind3, ind2 = ind2, i
+        elif s > max3:
+            max3, ind3 = s, i
+    if f32(max2) < f32(f32(0.1) * f32(max1)):     # int < 0.1f*(float)max1: a float comparison
+        ind2 = ind3 = -1
+    elif f32(max3) < f32(f32(0.1) * f32(max1)):
+        ind3 = -1
+    return ind1, ind2, ind3
+
+
+def _round_half_away(v):  # std::round(float)
+    v = float(v)
+    return int(math.floor(v + 0.5)) if v >= 0 else -int(math.floor(-v + 0.5))
+
+
+def _gemv3(R, x, c):  # one row of a cv::Mat float 3x3 * 3x1 + c: float operands, double accumulation
+    s = float(f32(R[0])) * float(f32(x[0])) + float(f32(R[1])) * float(f32(x[1])) + float(f32(R[2])) * float(f32(x[2]))
+    return f32(s + float(f32(c)))
+
+
+ASSIGN_UNCHANGED, ASSIGN_NULL = -1, -2  # LORB_ASSIGN_* as oracle.py returns them
+
+
+def search_by_projection_frame(fp, cur_Tcw, cur_kps, slot_state, last, th):  # src/matcher.cpp:64-218
+    """A slot whose map point has mnObs > 0 is LOCKED (2); a last-frame point with mp_locked set has
+    mnObs > 0, so the slot it takes is skipped by every later point of the call (:149-151)."""
+    n = len(cur_kps["x"])
+    state = np.array(slot_state if slot_state is not None else np.zeros(n), np.uint8).copy()
+    assign = np.full(n, ASSIGN_UNCHANGED, np.int32)
+    grid = build_grid(fp, cur_kps)
+    th = f32(th)
+    factor = f32(f32(30) / f32(360.0))                                  # :72
+    T = np.asarray(cur_Tcw, np.float32).reshape(4, 4)
+    L = np.asarray(last["Tcw"], np.float32).reshape(4, 4)
+    Rcw, tcw = T[:3, :3], T[:3, 3]
+    twc = [f32(-(float(Rcw[0, i]) * float(tcw[0]) + float(Rcw[1, i]) * float(tcw[1]) + float(Rcw[2, i]) * float(tcw[2])))
+           for i in range(3)]                                           # :77  -Rcw.t()*tcw
+    tlc_z = _gemv3(L[2, :3], twc, L[2, 3])                              # :83
+    forward = tlc_z > f32(fp["b"])                                      # :86
+    backward = f32(-tlc_z) > f32(fp["b"])                               # :87
+    fx, fy, cx, cy, bf = (f32(fp[k]) for k in ("fx", "fy", "cx", "cy", "bf"))
+    uR = cur_kps.get("u_right")
+    rot_hist = [[] for _ in range(30)]
+    nmatches = 0
+    for i in range(len(last["has_mp"])):
+        if not last["has_mp"][i]:
+            continue
+        if last.get("outlier") is not None and last["outlier"][i]:
+            continue
+        X = last["mp_pos"][i]
+        xc, yc, zc = _gemv3(Rcw[0], X, tcw[0]), _gemv3(Rcw[1], X, tcw[1]), _gemv3(Rcw[2], X, tcw[2])
+        invzc = f32(1.0 / float(zc))                                    # :105
+        if invzc < 0:
+            continue
+        u = f32(f32(f32(fx * xc) * invzc) + cx)
+        v = f32(f32(f32(fy * yc) * invzc) + cy)
+        if u < f32(fp["min_x"]) or u > f32(fp["max_x"]):
+            continue
+        if v < f32(fp["min_y"]) or v > f32(fp["max_y"]):
+            continue
+        o = int(last["octave"][i])
+        radius = f32(th * f32(fp["scale_factors"][o]))
+        if forward:
+            idx = features_in_area(fp, cur_kps, grid, u, v, radius, o)
+        elif backward:
+            idx = features_in_area(fp, cur_kps, grid, u, v, radius, 0, o)
+        else:
+            idx = features_in_area(fp, cur_kps, grid, u, v, radius, o - 1, o + 1)
+        bd, bi = 256, -1
+        for j in idx:
+            if state[j] == 2:
+                continue
+            if uR is not None and uR[j] > 0:
+                ur = f32(u - f32(bf * invzc))
+                if abs(f32(ur - f32(uR[j]))) > radius:
+                    continue
+            d = descriptor_distance(last["mp_desc"][i], cur_kps["desc"][j])
+            if d < bd:
+                bd, bi = d, j
+        if bd <= 100:
+            assign[bi] = i
+            state[bi] = 2 if last["mp_locked"][i] else 1
+            nmatches += 1
+            rot = f32(f32(last["angle"][i]) - f32(cur_kps["angle"][bi]))
+            if rot < 0:
+                rot = f32(rot + f32(360.0))
+            b = _round_half_away(f32(rot * factor))
+            if b == 30:
+                b = 0
+            rot_hist[b].append(bi)
+    keep = compute_three_maxima([len(h) for h in rot_hist])
+    for b in range(30):
+        if b not in keep:
+            for j in rot_hist[b]:
+                assign[j] = ASSIGN_NULL
+                nmatches -= 1
+    return assign, nmatches
+
+
 def compute_stereo_matches(fp, left, right, pyr_l, pyr_r):  # src/frame.cpp:125-333
     """Pure-Python ComputeStereoMatches with the same defined behaviour at the edges as oracle/stereo.c
     (clipped bands, out-of-image windows => no depth, empty => no rejection).  Windows via numpy."""

@@ -727,6 +727,79 @@ int lorb_track_motion_frames_dev(lorb_ctx* ctx, const lorb_frame_params* cur, co
                                  const lorb_track_motion_params* par, const lorb_lm_options* opt,
                                  int32_t* d_assign, lorb_track_frames_result* d_result);
 
+/* ----------------------------------------------------------------------------------------
+ * Local-map tracking straight from a built frame: VisualOdometry::EstimatePoseLocal after
+ * UpdateLocalMap (the held-slot loop, src/visual_odometry.cpp:153-171, then the tracking of
+ * src/visual_odometry.cpp:173-209) enqueued behind lorb_track_motion_frames_dev, with the pose, the keypoint count and the frame's slots never read by the host.  One tracked frame is
+ * then lorb_frame_build_dev, lorb_track_motion_frames_dev, lorb_track_local_frames_dev and ONE wait.
+ *
+ * Host values: frame, par, opt, n_max_cur (the bound on the keypoint count) and d_pts->n (the local
+ * map is the caller's: UpdateLocalMap is not part of this call).  Device inputs:
+ *   d_cur           host struct of device pointers; the left keypoint arrays and u_right are read,
+ *                   counts[0] is read on the device
+ *   d_cur_slots     n_max_cur entries, read and written (the slots lorb_track_motion_frames_dev left)
+ *   d_cur_slot_id   n_max_cur int32, read and written: the index into d_pts of the point slot j
+ *                   holds, or -1 for a point outside the table (points UpdateFrame created: always -1)
+ *   d_pose          6 doubles, (mRvec | mTvec); in the frame chain &d_motion_result->motion.pose[0]
+ *   d_src_status    nullable, one int32; in the frame chain &d_motion_result->status
+ *   d_pts           its in_frame MUST be NULL: the call derives the mask (LORB_E_INVALID otherwise)
+ *   ids             nullable.  NULL: d_cur_slot_id is taken as given.  Otherwise slot j's id on entry
+ *                   is computed from the motion stage's final code c = d_motion_assign[j] by the rule
+ *                   its tail applied to the slots: c >= 0 -> d_last_slot_id[c]; LORB_ASSIGN_NULL -> -1;
+ *                   LORB_ASSIGN_UNCHANGED -> the id already in d_cur_slot_id[j] when
+ *                   d_motion_result->motion.pass == 1 and cur_slots_given, else -1.
+ * On the device, in this order:
+ *   a. Status: counts[0] negative or above n_max_cur, or *d_src_status != 0, stores status = 1 in the
+ *      record and NOTHING else -- no slot, id, field, code or other part of the record is touched.
+ *   b. Pose hand-over: pose_in = (float) of the six doubles (the rounding of
+ *      BA::ProjectPoseOptimization's write-back, src/bundle_adjust.cpp:198-201); Tcw_in = the arithmetic
+ *      of lorb_pose_to_Tcw on pose_in; the camera centre from cv::Mat::inv() of Tcw_in.
+ *   c. The held-slot loop (src/visual_odometry.cpp:153-171): a non-EMPTY slot whose id >= 0 names a
+ *      point with is_bad set becomes EMPTY with id -1; every other non-EMPTY slot with id >= 0 marks its
+ *      point as already in the frame (mnLastFrameSeen).
+ *   d. a8 + a5 (:173-202) exactly as lorb_track_local_dev with that mask, Tcw_in and the slots of c.
+ *   e. The tail (:204-209) as lorb_track_local_dev from pose_in, then the codes applied to the slots
+ *      whether or not the gate passes (the reference keeps the matcher's writes): assign[j] = k >= 0
+ *      gives state = locked[k] ? LOCKED : FREE, pos = pts.pos[k], desc = pts.desc[k], id = k;
+ *      UNCHANGED slots stay as they are.
+ * What the device pose is equal to: the BA's pose agrees with the oracle to 1e-5, not bit for bit, and
+ * the device's double sin / cos is not libm's function, so Tcw_in is DEFINED as what the record
+ * reports; the matching is bit-exact given that Tcw_in (lorb_track_local_dev on the record's Tcw_in,
+ * pose_in, n_cur and the slots and mask of step c gives the same bits).
+ * Outputs as lorb_track_local_dev: d_in_view, d_track, d_level (d_pts->n entries each), d_assign
+ * (n_max_cur entries).  Nothing at or past counts[0] is written.  LORB_E_INVALID, before anything is
+ * enqueued: a null required argument, n_max_cur < 1, d_pts->n < 0, d_pts->n * n_max_cur > 8M (past
+ * that the candidate total would have to be read back), n_levels out of range, a negative
+ * min_matches, a non-NULL d_pts->in_frame.  Asynchronous on the ctx stream: no stream synchronise, no
+ * device-to-host read and no host-to-device copy.
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_track_local_id_source {
+  const int32_t* d_motion_assign;                  /* n_max_cur: lorb_track_motion_frames_dev's d_assign */
+  const lorb_track_frames_result* d_motion_result; /* its record (motion.pass is read) */
+  const int32_t* d_last_slot_id;                   /* n_max_last: the last frame's slot ids */
+  int32_t n_max_last;
+  int32_t cur_slots_given;                         /* as passed to lorb_track_motion_frames_dev */
+} lorb_track_local_id_source;
+
+typedef struct lorb_track_local_frames_result {
+  lorb_track_local_result local;  /* as lorb_track_local_dev */
+  float pose_in[6];               /* (float) of d_pose: the a12 start */
+  float Tcw_in[16];               /* the pose a8 projected with */
+  float Tcw[16];                  /* Frame::SetPose of local.pose rounded to float; ok == 0: Tcw_in */
+  int32_t n_cur;                  /* the count the call read */
+  int32_t n_held;                 /* slots non-EMPTY after step c */
+  int32_t n_in_frame;             /* points of d_pts the frame held after step c */
+  int32_t status;                 /* 0, or 1: nothing else was written */
+} lorb_track_local_frames_result;
+
+int lorb_track_local_frames_dev(lorb_ctx* ctx, const lorb_frame_params* frame, const lorb_frame_out* d_cur,
+                                int32_t n_max_cur, const lorb_frame_slots* d_cur_slots, int32_t* d_cur_slot_id,
+                                const double* d_pose, const int32_t* d_src_status,
+                                const lorb_track_local_id_source* ids, const lorb_map_points_dev* d_pts,
+                                const lorb_track_local_params* par, const lorb_lm_options* opt,
+                                uint8_t* d_in_view, float* d_track, int32_t* d_level, int32_t* d_assign,
+                                lorb_track_local_frames_result* d_result);
+
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.
  * obs_frame[k] >= 0 : optimised pose index (PoseMPCost, src/bundle_adjust.cpp:293-301)

@@ -214,6 +214,17 @@ class TrackFramesResult(C.Structure):  # lorb_track_frames_result
                 ("status", C.c_int32)]
 
 
+class TrackLocalIdSource(C.Structure):  # lorb_track_local_id_source (device addresses)
+    _fields_ = [("d_motion_assign", C.c_void_p), ("d_motion_result", C.c_void_p), ("d_last_slot_id", C.c_void_p),
+                ("n_max_last", C.c_int32), ("cur_slots_given", C.c_int32)]
+
+
+class TrackLocalFramesResult(C.Structure):  # lorb_track_local_frames_result
+    _fields_ = [("local", TrackLocalResult), ("pose_in", C.c_float * 6), ("Tcw_in", C.c_float * 16),
+                ("Tcw", C.c_float * 16), ("n_cur", C.c_int32), ("n_held", C.c_int32), ("n_in_frame", C.c_int32),
+                ("status", C.c_int32)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

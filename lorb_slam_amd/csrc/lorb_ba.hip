@@ -1500,7 +1500,8 @@ __global__ __launch_bounds__(kPoThreads) void k_track_frames_tail(lorb::TrackTai
 // call, src/visual_odometry.cpp:204-209), one workgroup: nToMatch counted from a8's flags (an
 // integer sum), the nMatches <= min_matches gate, and tail_run over the slots holding a map point
 // after a5 (a slot a5 left alone keeps the point stage 1 gave it).
-__global__ __launch_bounds__(kPoThreads) void k_local_tail(lorb::LocalTail a, LMOpt o) {
+// (the body, shared with k_local_frames_tail; pose_init: the a12 start, wherever it lives)
+__device__ __forceinline__ void local_tail_run(const lorb::LocalTail& a, const float* pose_init, const LMOpt& o) {
   __shared__ int wcnt[kPoW];
   const int nm = *a.nm;
   int c = 0;
@@ -1510,7 +1511,39 @@ __global__ __launch_bounds__(kPoThreads) void k_local_tail(lorb::LocalTail a, LM
   const bool ok = nm > a.min_matches;
   if (threadIdx.x == 0) { a.rec->ok = ok; a.rec->nmatches = nm; a.rec->n_in_view = n_in_view; }
   const TailSlots s = {a.nk, a.assign, true, a.slot_state, a.slot_pos, a.pt_pos, a.x, a.y, a.list, nullptr, a.assign_out};
-  tail_run(s, ok, a.fx, a.fy_eff, a.cx, a.cy, a.pose_init, o, &a.rec->n_residuals, a.rec->pose, &a.rec->summary);
+  tail_run(s, ok, a.fx, a.fy_eff, a.cx, a.cy, pose_init, o, &a.rec->n_residuals, a.rec->pose, &a.rec->summary);
+}
+__global__ __launch_bounds__(kPoThreads) void k_local_tail(lorb::LocalTail a, LMOpt o) { local_tail_run(a, a.pose_init, o); }
+
+// The tail of lorb_track_local_frames_dev: k_local_tail with both counts read from device memory
+// (a.nk / a.np are the bounds on entry) and the LM started from the pose k_local_head handed over;
+// then Frame::SetPose of the result rounded to float (the hand-over's own function: with ok == 0 the
+// pose is pose_in widened, so Tcw has the bits of Tcw_in), and a5's codes applied to the frame's
+// slots -- code k >= 0 gives the slot point k of the table (state from its lock flag, pos, desc, id);
+// UNCHANGED slots stay -- whether or not the gate passed (src/visual_odometry.cpp:204-205 keeps the
+// matcher's writes).  The apply runs after the LM for the reason k_track_frames_tail gives.
+__global__ __launch_bounds__(kPoThreads) void k_local_frames_tail(lorb::LocalTail a, lorb::LocalFramesTail f, LMOpt o) {
+  if (!lorb::frame_counts(f.dc, &a.np, &a.nk)) return;
+  local_tail_run(a, f.pose->pose_in, o);
+  __syncthreads();  // the record's pose is written, every read of the entry slots is done
+  if (threadIdx.x == 0) {
+    float p[6];
+    for (int k = 0; k < 6; ++k) p[k] = (float)a.rec->pose[k];
+    lorb::pose_to_Tcw(p, p + 3, f.rec->Tcw);
+  }
+  const uint4* pd = reinterpret_cast<const uint4*>(f.pt_desc);
+  uint4* cd = reinterpret_cast<uint4*>(f.cur.desc);
+  for (int j = threadIdx.x; j < a.nk; j += kPoThreads) {
+    const int c = a.assign[j];
+    if (c >= 0) {
+      f.cur.state[j] = f.pt_locked[c] ? LORB_SLOT_LOCKED : LORB_SLOT_FREE;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) f.cur.pos[3 * (size_t)j + k] = a.pt_pos[3 * (size_t)c + k];
+      cd[2 * (size_t)j] = pd[2 * (size_t)c];
+      cd[2 * (size_t)j + 1] = pd[2 * (size_t)c + 1];
+      f.slot_id[j] = c;
+    }
+  }
 }
 
 LMOpt to_dev_opt(const lorb_lm_options* o) {
@@ -1925,6 +1958,11 @@ int launch_local_tail(lorb_ctx* ctx, const LocalTail& t, const lorb_lm_options* 
   LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
 }
+int launch_local_frames_tail(lorb_ctx* ctx, const LocalTail& t, const LocalFramesTail& f, const lorb_lm_options* opt) {
+  hipLaunchKernelGGL(k_local_frames_tail, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, f, to_dev_opt(opt));
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
 int launch_track_tail(lorb_ctx* ctx, const TrackTail& t, const lorb_lm_options* opt) {
   hipLaunchKernelGGL(k_track_tail, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, to_dev_opt(opt));
   LORB_CHECK_LAUNCH(ctx);
@@ -2102,29 +2140,9 @@ int lorb_ba_pose_only_dev(lorb_ctx* ctx, const lorb_pose_problem_batch* d_prob, 
 }
 
 // cv::Rodrigues (vector -> matrix, double internally) + Frame::UpdatePoseMat write-back
-// (the file-scope contraction pragma must not reach this restatement: it rounds like the
-// reference's un-contracted host build whatever -march the library is built with)
-void lorb_pose_to_Tcw(const float rvec[3], const float tvec[3], float T[16]) {
-#pragma clang fp contract(off)
-  double rx = rvec[0], ry = rvec[1], rz = rvec[2];
-  const double theta = std::sqrt(rx * rx + ry * ry + rz * rz);
-  double R[9];
-  if (theta < 2.220446049250313e-16) {
-    for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
-  } else {
-    const double c = std::cos(theta), s = std::sin(theta), c1 = 1. - c;
-    const double it = theta ? 1. / theta : 0.;
-    rx *= it; ry *= it; rz *= it;
-    const double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz};
-    const double rxm[9] = {0, -rz, ry, rz, 0, -rx, -ry, rx, 0};
-    const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int k = 0; k < 9; ++k) R[k] = c * I[k] + c1 * rrt[k] + s * rxm[k];
-  }
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) T[4 * r + c] = (float)R[3 * r + c];
-    T[4 * r + 3] = tvec[r];
-  }
-  T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
-}
+// (lorb::pose_to_Tcw turns contraction off in its own body: the file-scope pragma must not reach this
+// restatement, which rounds like the reference's un-contracted host build whatever -march the
+// library is built with)
+void lorb_pose_to_Tcw(const float rvec[3], const float tvec[3], float T[16]) { lorb::pose_to_Tcw(rvec, tvec, T); }
 
 }  // extern "C"

@@ -381,8 +381,36 @@ __device__ __forceinline__ void unproject_point(float fx, float fy, float cx, fl
     out[r] = (float)s;
   }
 }
-// cv::Mat::inv() of a 4x4 CV_32F (hal::LU32f), host side (lorb_window.hip)
-bool inv4_lu32f(const float* A, float* out);
+// cv::Mat::inv() of a 4x4 CV_32F (hal::LU32f) (lorb_window.hip; float only, compiled
+// -ffp-contract=off: the device value has the bits of the host's).  Device code of lorb_window.hip only.
+__host__ __device__ bool inv4_lu32f(const float* A, float* out);
+
+// cv::Rodrigues (vector -> matrix, double internally) + Frame::UpdatePoseMat write-back: the body of
+// lorb_pose_to_Tcw, and on the device the pose hand-over of lorb_track_local_frames_dev.  Contraction
+// is off in the body whatever the including unit says (lorb_ba.hip contracts), so it rounds like the
+// reference's un-contracted host build; the device's double sin / cos are not libm's functions.
+__host__ __device__ inline void pose_to_Tcw(const float rvec[3], const float tvec[3], float T[16]) {
+#pragma clang fp contract(off)
+  double rx = rvec[0], ry = rvec[1], rz = rvec[2];
+  const double theta = sqrt(rx * rx + ry * ry + rz * rz);
+  double R[9];
+  if (theta < 2.220446049250313e-16) {
+    for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+  } else {
+    const double c = cos(theta), s = sin(theta), c1 = 1. - c;
+    const double it = theta ? 1. / theta : 0.;
+    rx *= it; ry *= it; rz *= it;
+    const double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz};
+    const double rxm[9] = {0, -rz, ry, rz, 0, -rx, -ry, rx, 0};
+    const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int k = 0; k < 9; ++k) R[k] = c * I[k] + c1 * rrt[k] + s * rxm[k];
+  }
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) T[4 * r + c] = (float)R[3 * r + c];
+    T[4 * r + 3] = tvec[r];
+  }
+  T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
+}
 
 // The tail of the motion-tracking chain (lorb_track_motion*, lorb_window.hip): one launch of
 // k_track_tail (lorb_ba.hip) after both a4 passes -- pass decision, final assign, residual
@@ -444,6 +472,28 @@ struct LocalTail {
   int* assign_out;               // non-null: the codes are also stored here (mapped block)
 };
 int launch_local_tail(lorb_ctx* ctx, const LocalTail& t, const lorb_lm_options* opt);
+
+// The device-count, device-pose form of the local-map chain (lorb_track_local_frames_dev).  Its first
+// kernel (k_local_head, lorb_window.hip) leaves this block in device memory; the candidate kernel and
+// the tail read the pose from it where the host-pose form reads FrustumIn::T / Ow and
+// LocalTail::pose_init out of its kernel arguments.  np is d_pts->n, or -1 when the call's status is
+// 1: as FrameCounts::last of the later kernels it makes every one of them return on that status.
+struct LocalPose {
+  float T[16], Ow[3], pose_in[6];
+  int np;
+};
+// What k_local_frames_tail (lorb_ba.hip) has beyond k_local_tail: nk / np are read through dc, the
+// LM starts from pose->pose_in, and after it the record's Tcw is written and the codes are applied to
+// the frame's slots and their ids.
+struct LocalFramesTail {
+  FrameCounts dc;
+  const LocalPose* pose;
+  lorb_frame_slots cur;
+  int* slot_id;
+  const uint8_t *pt_locked, *pt_desc;
+  lorb_track_local_frames_result* rec;
+};
+int launch_local_frames_tail(lorb_ctx* ctx, const LocalTail& t, const LocalFramesTail& f, const lorb_lm_options* opt);
 
 // Device memory owned by one object (not a ctx scratch slot): add() every array, commit() allocates
 // one block and sets the pointers (256-byte aligned, 16 spare bytes each as scratch_t gives).
@@ -574,9 +624,10 @@ inline constexpr SlotFamily
     S_TL = {64, 20, false},   // lorb_track_local_map's staging.  Alias: inside S_ORB's range, as above
     S_TM = {88, 3, false},    // motion chain: pass 2's codes + both counts, the residual list, the host form's codes
     S_TF = {91, 1, false},    // frames chain (which also uses S_TM 0 and 1): the last frame's mp_locked flags
-    S_TLC = {92, 6, false};   // local-map chain: match count, residual list; the host form's codes, in-view flags, fields, levels
+    S_TLC = {92, 6, false},   // local-map chain: match count, residual list; the host form's codes, in-view flags, fields, levels
+    S_TLF = {98, 2, false};   // its frames form (which also uses S_TLC 0 and 1): the LocalPose block, the in_frame mask
 inline constexpr SlotFamily kSlotPlan[] = {
-    {S_BF_Q, 14, false}, {S_W0, 10, false}, S_KP, S_WX, S_ST, S_ORB, S_TL, S_TM, S_TF, S_TLC,
+    {S_BF_Q, 14, false}, {S_W0, 10, false}, S_KP, S_WX, S_ST, S_ORB, S_TL, S_TM, S_TF, S_TLC, S_TLF,
     {S_BF_TKEY, 1, true}, {S_IO_IN, 1, true}, {S_IO_OUT, 1, true}, {S_BF_DONE, 1, true}, {S_TM_ZERO, 1, true}};
 
 // slot K of family F; an offset past the family's end does not compile

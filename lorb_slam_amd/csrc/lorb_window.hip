@@ -293,15 +293,16 @@ __device__ __forceinline__ int walk_candidates_wave(const KpDev& K, const lorb_f
 constexpr int kCandWaves = 4;  // queries (wavefronts) per 256-thread workgroup
 
 // (a5) candidates of each local map point, one wavefront per point
-template <bool WRITE, bool GRID = false>
-__global__ __launch_bounds__(64 * kCandWaves) void k_cand_local(KpDev K, WinParams P, int np,
-                                                    const uint8_t* __restrict__ in_view,
-                                                    const uint8_t* __restrict__ is_bad,
-                                                    const float* __restrict__ px, const float* __restrict__ py,
-                                                    const float* __restrict__ pxr, const int* __restrict__ plev,
-                                                    const float* __restrict__ vcos, const uint4* __restrict__ pdesc,
-                                                    int* __restrict__ cand_cnt, const int* __restrict__ cand_off,
-                                                    int2* __restrict__ cand, int stride = 0) {
+// (the body, shared with k_cand_local_dc)
+template <bool WRITE, bool GRID>
+__device__ __forceinline__ void cand_local_run(KpDev K, const WinParams& P, int np,
+                                               const uint8_t* __restrict__ in_view,
+                                               const uint8_t* __restrict__ is_bad,
+                                               const float* __restrict__ px, const float* __restrict__ py,
+                                               const float* __restrict__ pxr, const int* __restrict__ plev,
+                                               const float* __restrict__ vcos, const uint4* __restrict__ pdesc,
+                                               int* __restrict__ cand_cnt, const int* __restrict__ cand_off,
+                                               int2* __restrict__ cand, int stride) {
   const int m = blockIdx.x * kCandWaves + (threadIdx.x >> 6);
   // the query's scalars requested first (GRID: they arrive while the keypoints are staged)
   const int mq = min(m, np - 1);
@@ -322,6 +323,31 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_cand_local(KpDev K, WinPara
                                       WRITE ? cand + (stride > 0 ? (size_t)m * stride : (size_t)cand_off[m]) : nullptr);
   }
   if ((!WRITE || stride > 0) && (threadIdx.x & 63) == 0) cand_cnt[m] = cnt;
+}
+template <bool WRITE, bool GRID = false>
+__global__ __launch_bounds__(64 * kCandWaves) void k_cand_local(KpDev K, WinParams P, int np,
+                                                    const uint8_t* __restrict__ in_view,
+                                                    const uint8_t* __restrict__ is_bad,
+                                                    const float* __restrict__ px, const float* __restrict__ py,
+                                                    const float* __restrict__ pxr, const int* __restrict__ plev,
+                                                    const float* __restrict__ vcos, const uint4* __restrict__ pdesc,
+                                                    int* __restrict__ cand_cnt, const int* __restrict__ cand_off,
+                                                    int2* __restrict__ cand, int stride = 0) {
+  cand_local_run<WRITE, GRID>(K, P, np, in_view, is_bad, px, py, pxr, plev, vcos, pdesc, cand_cnt, cand_off, cand, stride);
+}
+// the device-count form of k_cand_local<true, false> (the local-map frames chain's write pass):
+// launched over the bound np = dc.max_last, the counts read first as k_cand_frame<., ., true> does
+__global__ __launch_bounds__(64 * kCandWaves) void k_cand_local_dc(KpDev K, WinParams P, int np,
+                                                    const uint8_t* __restrict__ in_view,
+                                                    const uint8_t* __restrict__ is_bad,
+                                                    const float* __restrict__ px, const float* __restrict__ py,
+                                                    const float* __restrict__ pxr, const int* __restrict__ plev,
+                                                    const float* __restrict__ vcos, const uint4* __restrict__ pdesc,
+                                                    int* __restrict__ cand_cnt, const int* __restrict__ cand_off,
+                                                    int2* __restrict__ cand, int stride, lorb::FrameCounts dc) {
+  if (!lorb::frame_counts(dc, &np, &K.n)) return;
+  if ((int)blockIdx.x * kCandWaves >= np) return;
+  cand_local_run<true, false>(K, P, np, in_view, is_bad, px, py, pxr, plev, vcos, pdesc, cand_cnt, cand_off, cand, stride);
 }
 
 // (a4) projection of last-frame map points + candidates, one wavefront per point
@@ -735,7 +761,8 @@ __global__ __launch_bounds__(256) void k_frustum(lorb_frame_params fp, const flo
 // straight from those registers.  WRITE: one strided pass (candidates at m * stride, counts in
 // cand_cnt); !WRITE: the count pass of the count / scan / write sequence, whose write pass is
 // k_cand_local<true> reading the fields stored here.
-struct FrustumIn {  // a8's inputs; the pose and the camera centre travel as kernel arguments
+struct FrustumIn {  // a8's inputs; the pose and the camera centre travel as kernel arguments (the
+                    // device-pose form reads them from a lorb::LocalPose block and leaves T / Ow unused)
   float T[16], Ow[3];
   const float *pos, *nrm, *maxd, *mind;
   const uint8_t *skip_a, *skip_b;
@@ -746,16 +773,17 @@ struct FieldsOut {
   float* track;      // 4 planes of np: x, y, xr, cos
   int* level;        // np
 };
-template <bool WRITE, bool GRID = false>
-__global__ __launch_bounds__(64 * kCandWaves) void k_cand_local_fr(KpDev K, WinParams P, int np, FrustumIn F,
-                                                                   FieldsOut o, FieldsOut mir,
-                                                                   const uint4* __restrict__ pdesc,
-                                                                   int* __restrict__ cand_cnt, int2* __restrict__ cand,
-                                                                   int stride) {
+// (the body, shared with k_cand_local_fr_dc; T, Ow: the pose and the camera centre, wherever they live)
+template <bool WRITE, bool GRID>
+__device__ __forceinline__ void cand_local_fr_run(KpDev K, const WinParams& P, int np, const FrustumIn& F,
+                                                  const float* __restrict__ T, const float* __restrict__ Ow,
+                                                  const FieldsOut& o, const FieldsOut& mir,
+                                                  const uint4* __restrict__ pdesc, int* __restrict__ cand_cnt,
+                                                  int2* __restrict__ cand, int stride) {
   const int m = blockIdx.x * kCandWaves + (threadIdx.x >> 6);
   // the query's fields first (GRID: its loads are in flight while the grid is staged)
   TrackFields f;
-  const bool act = frustum_point(P.fp, F.T, F.Ow, min(m, np - 1), F.pos, F.nrm, F.maxd, F.mind, F.cos_limit, F.skip_a,
+  const bool act = frustum_point(P.fp, T, Ow, min(m, np - 1), F.pos, F.nrm, F.maxd, F.mind, F.cos_limit, F.skip_a,
                                  F.skip_b, &f);
   if constexpr (GRID) {
     __shared__ KpLds L;
@@ -784,6 +812,30 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_cand_local_fr(KpDev K, WinP
                                       WRITE ? cand + (size_t)m * stride : nullptr);
   }
   if (lane0) cand_cnt[m] = cnt;
+}
+template <bool WRITE, bool GRID = false>
+__global__ __launch_bounds__(64 * kCandWaves) void k_cand_local_fr(KpDev K, WinParams P, int np, FrustumIn F,
+                                                                   FieldsOut o, FieldsOut mir,
+                                                                   const uint4* __restrict__ pdesc,
+                                                                   int* __restrict__ cand_cnt, int2* __restrict__ cand,
+                                                                   int stride) {
+  cand_local_fr_run<WRITE, GRID>(K, P, np, F, F.T, F.Ow, o, mir, pdesc, cand_cnt, cand, stride);
+}
+// The device-count, device-pose form (lorb_track_local_frames_dev): launched over the bound np =
+// dc.max_last with K.n = dc.max_cur (also the stride); the counts are read first, a workgroup wholly
+// past np leaves before it stages anything; the pose and the camera centre come from the block
+// k_local_head left (F.T / F.Ow are unused).
+template <bool WRITE, bool GRID = false>
+__global__ __launch_bounds__(64 * kCandWaves) void k_cand_local_fr_dc(KpDev K, WinParams P, int np, FrustumIn F,
+                                                                      FieldsOut o, const uint4* __restrict__ pdesc,
+                                                                      int* __restrict__ cand_cnt,
+                                                                      int2* __restrict__ cand, int stride,
+                                                                      const lorb::LocalPose* __restrict__ pose,
+                                                                      lorb::FrameCounts dc) {
+  if (!lorb::frame_counts(dc, &np, &K.n)) return;
+  if ((int)blockIdx.x * kCandWaves >= np) return;
+  cand_local_fr_run<WRITE, GRID>(K, P, np, F, pose->T, pose->Ow, o, FieldsOut{nullptr, nullptr, nullptr}, pdesc, cand_cnt,
+                                 cand, stride);
 }
 
 // (a20) Frame::UnprojectStereo of one keypoint: the origin where it has no depth (src/frame.cpp:352-355)
@@ -874,20 +926,23 @@ __global__ __launch_bounds__(1024) void k_slots_fill(SlotFill a, lorb::FrameCoun
 
 }  // namespace
 
-// cv::Mat::inv() for 4x4 CV_32F: hal::LU32f (partial pivoting, float), host side
-bool lorb::inv4_lu32f(const float* Ain, float* out) {
+// cv::Mat::inv() for 4x4 CV_32F: hal::LU32f (partial pivoting, float), host and device
+__host__ __device__ bool lorb::inv4_lu32f(const float* Ain, float* out) {
   float A[16], b[16];
-  memcpy(A, Ain, sizeof(A));
+  for (int i = 0; i < 16; i++) A[i] = Ain[i];
   for (int i = 0; i < 16; i++) b[i] = (i % 5 == 0) ? 1.0f : 0.0f;
   const float eps = 1.1920928955078125e-07f * 10;
   for (int i = 0; i < 4; i++) {
     int k = i;
     for (int j = i + 1; j < 4; j++)
-      if (std::fabs(A[j * 4 + i]) > std::fabs(A[k * 4 + i])) k = j;
-    if (std::fabs(A[k * 4 + i]) < eps) { memset(out, 0, 16 * sizeof(float)); return false; }
+      if (fabsf(A[j * 4 + i]) > fabsf(A[k * 4 + i])) k = j;
+    if (fabsf(A[k * 4 + i]) < eps) {
+      for (int j = 0; j < 16; j++) out[j] = 0.0f;
+      return false;
+    }
     if (k != i) {
-      for (int j = i; j < 4; j++) std::swap(A[i * 4 + j], A[k * 4 + j]);
-      for (int j = 0; j < 4; j++) std::swap(b[i * 4 + j], b[k * 4 + j]);
+      for (int j = i; j < 4; j++) { const float v = A[i * 4 + j]; A[i * 4 + j] = A[k * 4 + j]; A[k * 4 + j] = v; }
+      for (int j = 0; j < 4; j++) { const float v = b[i * 4 + j]; b[i * 4 + j] = b[k * 4 + j]; b[k * 4 + j] = v; }
     }
     const float dd = -1 / A[i * 4 + i];
     for (int j = i + 1; j < 4; j++) {
@@ -902,12 +957,90 @@ bool lorb::inv4_lu32f(const float* Ain, float* out) {
       for (int k = i + 1; k < 4; k++) s -= A[i * 4 + k] * b[k * 4 + j];
       b[i * 4 + j] = s / A[i * 4 + i];
     }
-  memcpy(out, b, sizeof(b));
+  for (int i = 0; i < 16; i++) out[i] = b[i];
   return true;
 }
 
 namespace {
 using lorb::inv4_lu32f;
+
+// The first launch of lorb_track_local_frames_dev, one 1024-thread workgroup (as k_slots_fill):
+//   a. the status: the count against its bound and the source's status; a failing one stores status 1
+//      and, in the chain's own block, np = -1, on which every later kernel returns (frame_counts);
+//   b. the pose hand-over, by thread 0 while the others walk the slots: the six doubles rounded to
+//      float, Tcw_in, the camera centre, into the LocalPose block and the record;
+//   c. the slots' ids (given, or derived from the motion stage's codes), then the held-slot loop of
+//      src/visual_odometry.cpp:153-171: a slot holding a bad point is emptied, every other held point
+//      of the table is flagged in the in_frame mask, which the kernel clears first.
+struct LocalHead {
+  const int* count;  // the frame's counts (entry 0)
+  int n_max, np;
+  const int* src_status;  // or null
+  const double* pose;     // 6
+  uint8_t* state;         // n_max: the frame's slot states
+  int* slot_id;           // n_max
+  const uint8_t* is_bad;  // np, or null
+  uint8_t* in_frame;      // np: the mask (scratch)
+  lorb::LocalPose* blk;
+  lorb_track_local_frames_result* rec;
+  // the id source (motion_assign null: none)
+  const int* motion_assign;
+  const lorb_track_frames_result* motion_rec;
+  const int* last_slot_id;
+  int n_max_last, given;
+};
+__global__ __launch_bounds__(1024) void k_local_head(LocalHead a) {
+  __shared__ int wsum[16];
+  const int t = threadIdx.x;
+  const int n = a.count[0];
+  const bool ok = n >= 0 && n <= a.n_max && !(a.src_status && *a.src_status != 0);
+  if (t == 0) {
+    a.rec->status = ok ? 0 : 1;
+    a.blk->np = ok ? a.np : -1;
+  }
+  if (!ok) return;
+  if (t == 0) {
+    float p[6], T[16], Twc[16];
+    for (int k = 0; k < 6; ++k) p[k] = (float)a.pose[k];  // src/bundle_adjust.cpp:198-201
+    lorb::pose_to_Tcw(p, p + 3, T);
+    inv4_lu32f(T, Twc);
+    for (int k = 0; k < 6; ++k) { a.blk->pose_in[k] = p[k]; a.rec->pose_in[k] = p[k]; }
+    for (int k = 0; k < 16; ++k) { a.blk->T[k] = T[k]; a.rec->Tcw_in[k] = T[k]; }
+    a.blk->Ow[0] = Twc[3]; a.blk->Ow[1] = Twc[7]; a.blk->Ow[2] = Twc[11];
+    a.rec->n_cur = n;
+  }
+  for (int m = t; m < a.np; m += 1024) a.in_frame[m] = 0;
+  const bool keep = a.motion_assign && a.given && a.motion_rec->motion.pass == 1;
+  __syncthreads();  // the mask is clear
+  int held = 0;
+  for (int j = t; j < n; j += 1024) {
+    int id = a.slot_id[j];
+    if (a.motion_assign) {
+      const int c = a.motion_assign[j];
+      if (c >= 0) id = c < a.n_max_last ? a.last_slot_id[c] : -1;
+      else if (c == LORB_ASSIGN_NULL || !keep) id = -1;
+    }
+    if ((unsigned)id >= (unsigned)a.np) id = -1;  // a point outside the table
+    const uint8_t st = a.state[j];
+    if (st != LORB_SLOT_EMPTY) {
+      if (id >= 0 && a.is_bad && a.is_bad[id]) {
+        a.state[j] = LORB_SLOT_EMPTY;
+        id = -1;
+      } else {
+        held++;
+        if (id >= 0) a.in_frame[id] = 1;
+      }
+    }
+    a.slot_id[j] = id;
+  }
+  int n_held;
+  lorb::block_excl_scan_1024(held, wsum, &n_held);  // its barriers: the mask is complete
+  int inf = 0;
+  for (int m = t; m < a.np; m += 1024) inf += a.in_frame[m];
+  int n_inf;
+  lorb::block_excl_scan_1024(inf, wsum, &n_inf);
+  if (t == 0) { a.rec->n_held = n_held; a.rec->n_in_frame = n_inf; }
+}
 
 // a frame's keypoints (Frame::mvKeysUn, mDescriptors, slot states) for the host-array entry points:
 // packed into their InPack (one pull for every input), then the device grid built
@@ -1026,10 +1159,12 @@ int empty_slots(lorb_ctx* ctx, int n, const uint8_t** out) {
 // the candidate lists of the nq queries (one strided pass up to kCandStrided entries, else count /
 // scan / write), the resolver.  What differs per search is `launch`: called as launch(CandPass<WRITE,
 // GRID>, workgroups, cnt, off, cand, stride), it launches that instantiation of its candidate kernel.
-// The working buffers (S_WX, S_W9) are the same for every search.  dc (the frames chain, MODE 1 only):
-// nq and K->n are the caller's bounds -- they size the grids, the stride, the LDS mode and every
-// buffer -- and each kernel reads the two counts from device memory (its kDevCount form); `launch`
-// passes *dc on to its candidate kernel.
+// The working buffers (S_WX, S_W9) are the same for every search.  dc (the frames chains): nq and
+// K->n are the caller's bounds -- they size the grids, the stride, the LDS mode and every buffer --
+// and each kernel reads the two counts from device memory (its kDevCount form); `launch` passes *dc
+// on to its candidate kernel.  MODE 1: dc->last is the last frame's count.  MODE 0
+// (lorb_track_local_frames_dev): the query count is a host value, so dc->last points at a device int
+// that the call's first kernel stores it into (or -1: every kernel then returns).
 template <bool WRITE, bool GRID>
 struct CandPass {
   static constexpr bool write = WRITE, grid = GRID;
@@ -1696,6 +1831,99 @@ int lorb_track_local(lorb_ctx* ctx, const lorb_frame_params* frame, const float 
     lorb_pose_to_Tcw(R, T, Tcw_out);
   }
   return LORB_OK;
+}
+
+// VisualOdometry::EstimatePoseLocal after UpdateLocalMap (src/visual_odometry.cpp:153-209) on a built
+// frame whose count, pose and slots stay in device memory: k_local_head (status, pose hand-over,
+// held-slot loop), then track_local_issue's launches in their device-count, device-pose forms over the
+// caller's bounds (np = d_pts->n is a host value: k_local_head stores it where FrameCounts::last
+// points, or -1 on a failing status), and the tail that also applies the codes to the slots.
+// Launches: head + candidates + resolver + tail while np * n_max_cur <= kCandStrided and n_max_cur <=
+// kStageKps; the grid build is added past kStageKps, the count / scan / write sequence replaces the
+// one candidate pass past kCandStrided.
+int lorb_track_local_frames_dev(lorb_ctx* ctx, const lorb_frame_params* frame, const lorb_frame_out* d_cur,
+                                int32_t n_max_cur, const lorb_frame_slots* d_cur_slots, int32_t* d_cur_slot_id,
+                                const double* d_pose, const int32_t* d_src_status,
+                                const lorb_track_local_id_source* ids, const lorb_map_points_dev* d_pts,
+                                const lorb_track_local_params* par, const lorb_lm_options* opt, uint8_t* d_in_view,
+                                float* d_track, int32_t* d_level, int32_t* d_assign,
+                                lorb_track_local_frames_result* d_result) {
+  if (!ctx || !frame || !d_cur || !d_cur_slots || !d_cur_slot_id || !d_pose || !d_pts || !par || !opt || !d_in_view ||
+      !d_track || !d_level || !d_assign || !d_result)
+    return LORB_E_INVALID;
+  const int nk = n_max_cur, np = d_pts->n;
+  if (nk < 1) return lorb::set_error(ctx, LORB_E_INVALID, "bound %d must be positive", nk);
+  if (np < 0) return lorb::set_error(ctx, LORB_E_INVALID, "negative sizes");
+  // a5's candidate list is allocated from the bounds: past this it would need the total read back
+  if ((int64_t)np * (int64_t)nk > (int64_t(8) << 20))
+    return lorb::set_error(ctx, LORB_E_INVALID, "%d points x bound %d exceed the asynchronous limit of 8M candidates", np,
+                           nk);
+  if (frame->n_levels < 1 || frame->n_levels > LORB_MAX_LEVELS)
+    return lorb::set_error(ctx, LORB_E_INVALID, "n_levels %d out of range", frame->n_levels);
+  if (par->min_matches < 0) return lorb::set_error(ctx, LORB_E_INVALID, "min_matches %d is negative", par->min_matches);
+  if (d_pts->in_frame) return lorb::set_error(ctx, LORB_E_INVALID, "d_pts->in_frame must be NULL: the call derives it");
+  if (!d_cur->counts || !d_cur->left.x || !d_cur->left.y || !d_cur->left.octave || !d_cur->left.angle ||
+      !d_cur->left.desc || !d_cur->u_right || !slots_ok(d_cur_slots) ||
+      (ids && (!ids->d_motion_assign || !ids->d_motion_result || !ids->d_last_slot_id || ids->n_max_last < 1)) ||
+      (np > 0 && (!d_pts->pos || !d_pts->normal || !d_pts->max_dist || !d_pts->min_dist || !d_pts->desc || !d_pts->locked)))
+    return lorb::set_error(ctx, LORB_E_INVALID, "null array");
+  int* nm;
+  float* list;
+  lorb::LocalPose* blk;
+  uint8_t* in_frame;
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLC, 0>(), 1, &nm));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLC, 1>(), (size_t)nk * 5, &list));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLF, 0>(), 1, &blk));
+  LORB_TRY(lorb::scratch_t(ctx, slot<S_TLF, 1>(), (size_t)std::max(np, 1), &in_frame));
+  LocalHead h{};
+  h.count = d_cur->counts; h.n_max = nk; h.np = np; h.src_status = d_src_status; h.pose = d_pose;
+  h.state = d_cur_slots->state; h.slot_id = d_cur_slot_id; h.is_bad = d_pts->is_bad; h.in_frame = in_frame;
+  h.blk = blk; h.rec = d_result;
+  if (ids) {
+    h.motion_assign = ids->d_motion_assign; h.motion_rec = ids->d_motion_result; h.last_slot_id = ids->d_last_slot_id;
+    h.n_max_last = ids->n_max_last; h.given = ids->cur_slots_given != 0;
+  }
+  hipLaunchKernelGGL(k_local_head, dim3(1), dim3(1024), 0, ctx->stream, h);
+  LORB_CHECK_LAUNCH(ctx);
+  const lorb::FrameCounts dc = {&blk->np, d_cur->counts, np, nk};
+  KpDev K;
+  K.x = d_cur->left.x; K.y = d_cur->left.y; K.angle = d_cur->left.angle; K.uR = d_cur->u_right;
+  K.octave = d_cur->left.octave; K.desc = reinterpret_cast<const uint4*>(d_cur->left.desc);
+  K.slot_state = d_cur_slots->state;
+  K.cell_off = nullptr; K.cell_idx = nullptr; K.n = nk;
+  FrustumIn F{};  // T and Ow stay zero: the device form reads them from blk
+  F.pos = d_pts->pos; F.nrm = d_pts->normal; F.maxd = d_pts->max_dist; F.mind = d_pts->min_dist;
+  F.skip_a = in_frame; F.skip_b = d_pts->is_bad;
+  F.cos_limit = par->viewing_cos_limit;
+  WinParams P{};
+  P.fp = *frame;
+  P.th = par->th;
+  const FieldsOut o = {d_in_view, d_track, d_level};
+  const uint4* pdesc = reinterpret_cast<const uint4*>(d_pts->desc);
+  const LocalDev Q = {np, d_in_view, d_pts->is_bad, d_pts->locked, d_track, d_track + np, d_track + 2 * np,
+                      d_track + 3 * np, d_level, pdesc};
+  LORB_TRY(search_issue<0>(
+      ctx, &K, P.fp, np, d_pts->locked, nullptr, {d_assign, nm, nullptr, nullptr, 0},
+      [&](auto pass, unsigned g, int* cnt, const int* off, int2* cand, int stride) {
+        using Pass = decltype(pass);
+        if (off)
+          hipLaunchKernelGGL(k_cand_local_dc, dim3(g), dim3(256), 0, ctx->stream, K, P, np, Q.iv, Q.bad, Q.px, Q.py,
+                             Q.pxr, Q.pl, Q.vc, Q.pd, cnt, off, cand, stride, dc);
+        else
+          hipLaunchKernelGGL((k_cand_local_fr_dc<Pass::write, Pass::grid>), dim3(g), dim3(256), 0, ctx->stream, K, P, np, F,
+                             o, pdesc, cnt, cand, stride, (const lorb::LocalPose*)blk, dc);
+      },
+      &dc));
+  lorb::LocalTail t{};
+  t.nk = nk; t.np = np; t.nm = nm; t.assign = d_assign; t.in_view = d_in_view;
+  t.slot_state = d_cur_slots->state; t.slot_pos = d_cur_slots->pos; t.pt_pos = d_pts->pos; t.x = K.x; t.y = K.y;
+  t.min_matches = par->min_matches;
+  t.fx = frame->fx; t.fy_eff = par->fy_eff; t.cx = frame->cx; t.cy = frame->cy;
+  t.list = list; t.rec = &d_result->local; t.assign_out = nullptr;
+  lorb::LocalFramesTail f{};
+  f.dc = dc; f.pose = blk; f.cur = *d_cur_slots; f.slot_id = d_cur_slot_id;
+  f.pt_locked = d_pts->locked; f.pt_desc = d_pts->desc; f.rec = d_result;
+  return lorb::launch_local_frames_tail(ctx, t, f, opt);
 }
 
 int lorb_unproject_stereo_dev(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16], int32_t n,

@@ -154,6 +154,109 @@ def track_motion_frames(ctx, fp, cur_Tcw, pose_init, cur, cur_slots, last_Tcw, l
             a.free()
 
 
+def enqueue_track_motion_frames(ctx, fp, cur_Tcw, pose_init, cur, cur_slots, last_Tcw, last, last_slots, assign, record,
+                                n_max_cur=None, n_max_last=None, cur_slots_given=False, last_outlier=None, th_first=15.0,
+                                th_retry=30.0, min_matches=20, fy_eff=None, opt=None):
+    """lorb_track_motion_frames_dev enqueued and nothing else: assign (n_max_cur int32) and record
+    (sizeof(A.TrackFramesResult) bytes) are the caller's DeviceArrays, last_outlier a DeviceArray or None.
+    Nothing is fetched and nothing waits, so lorb_track_local_frames_dev can be enqueued behind it."""
+    fps = A.make_frame_params(fp)
+    par = A.TrackMotionParams(th_first, th_retry, min_matches, fps.fx if fy_eff is None else fy_eff)
+    opt = opt or A.LMOptions.default()
+    T, TL, pi = A.f32(cur_Tcw).reshape(16), A.f32(last_Tcw).reshape(16), A.f32(pose_init).reshape(6)
+    nc = cur_slots.n_max if n_max_cur is None else int(n_max_cur)
+    nl = last_slots.n_max if n_max_last is None else int(n_max_last)
+    ctx.check(lib().lorb_track_motion_frames_dev(
+        ctx.handle, C.byref(fps), A.ptr(T, C.c_float), A.ptr(pi, C.c_float), C.byref(cur.out), C.c_int32(nc),
+        C.byref(cur_slots.c), C.c_int32(1 if cur_slots_given else 0), A.ptr(TL, C.c_float), C.byref(last.out),
+        C.c_int32(nl), C.byref(last_slots.c), last_outlier.ptr if last_outlier else None, C.byref(par), C.byref(opt),
+        assign.ptr, record.ptr), "lorb_track_motion_frames_dev")
+
+
+def motion_record_addresses(record):
+    """(address of motion.pose, address of status) inside a device A.TrackFramesResult: d_pose and
+    d_src_status of lorb_track_local_frames_dev in the frame chain."""
+    base = record.ptr.value
+    return (base + A.TrackFramesResult.motion.offset + A.TrackMotionResult.pose.offset,
+            base + A.TrackFramesResult.status.offset)
+
+
+class DevicePoints:
+    """lorb_map_points_dev in device memory, in_frame NULL (lorb_track_local_frames_dev derives it).
+    pts: dict(pos, normal, max_dist, min_dist, desc, locked, is_bad or None)."""
+
+    def __init__(self, ctx, pts):
+        self.n = len(pts["pos"])
+        conv = dict(pos=A.f32, normal=A.f32, max_dist=A.f32, min_dist=A.f32, desc=A.u8, locked=A.u8, is_bad=A.u8)
+        self.arrays = {k: ctx.to_device(f(pts[k])) for k, f in conv.items() if pts.get(k) is not None}
+        a = self.arrays
+        self.c = A.MapPointsDev(self.n, a["pos"].ptr, a["normal"].ptr, a["max_dist"].ptr, a["min_dist"].ptr, a["desc"].ptr,
+                                a["locked"].ptr, a["is_bad"].ptr if "is_bad" in a else None, None)
+
+    def free(self):
+        for a in self.arrays.values():
+            a.free()
+        self.arrays = {}
+
+
+class LocalFramesOut:
+    """The device outputs of lorb_track_local_frames_dev for n_points points and a bound of n_max_cur
+    keypoints: in_view, track (4 planes of n_points), level, assign and the record, each ORB_GUARD
+    entries longer than the call is told.  in_view / track / level / record start as ORB_SENTINEL bytes,
+    assign as assign_fill."""
+
+    def __init__(self, ctx, n_points, n_max_cur, assign_fill=-77):
+        def sent(n, dtype):
+            return ctx.to_device(np.full(n * np.dtype(dtype).itemsize, ORB_SENTINEL, np.uint8).view(dtype))
+
+        self.n_points, self.n_max_cur = int(n_points), int(n_max_cur)
+        self.in_view = sent(self.n_points + ORB_GUARD, np.uint8)
+        self.track = sent(4 * self.n_points + ORB_GUARD, np.float32)
+        self.level = sent(self.n_points + ORB_GUARD, np.int32)
+        self.assign = ctx.to_device(np.full(self.n_max_cur + ORB_GUARD, assign_fill, np.int32))
+        self.record = sent(C.sizeof(A.TrackLocalFramesResult) + ORB_GUARD, np.uint8)
+
+    def result(self):
+        """The record (waits for the stream): A.TrackLocalFramesResult."""
+        return A.TrackLocalFramesResult.from_buffer_copy(self.record.numpy().tobytes()[:C.sizeof(A.TrackLocalFramesResult)])
+
+    def free(self):
+        for a in (self.in_view, self.track, self.level, self.assign, self.record):
+            a.free()
+
+
+def track_local_frames(ctx, fp, cur, cur_slots, slot_id, d_pose, pts, out=None, n_max_cur=None, d_src_status=None,
+                       id_source=None, viewing_cos_limit=0.5, th=1.0, min_matches=20, fy_eff=None, opt=None, fetch=False):
+    """lorb_track_local_frames_dev on a DeviceFrame, its DeviceSlots and their ids: EstimatePoseLocal
+    after UpdateLocalMap with the count, the pose and the slots read on the device.  slot_id: DeviceArray
+    of n_max_cur int32; d_pose / d_src_status: device addresses (motion_record_addresses() in the frame
+    chain; d_src_status may be None); pts: DevicePoints; id_source: A.TrackLocalIdSource or None; out: a
+    LocalFramesOut (one is made when None: the caller frees it).  The call is only enqueued; returns
+    dict(out=..., in_view, track, level, assign, record: the device buffers) and, only with fetch=True
+    (which waits for the stream), result: the A.TrackLocalFramesResult."""
+    fps = A.make_frame_params(fp)
+    par = A.TrackLocalParams(viewing_cos_limit, th, min_matches, fps.fx if fy_eff is None else fy_eff)
+    opt = opt or A.LMOptions.default()
+    nc = cur_slots.n_max if n_max_cur is None else int(n_max_cur)
+    made = out is None
+    if made:
+        out = LocalFramesOut(ctx, pts.n, max(nc, 0))
+    try:
+        ctx.check(lib().lorb_track_local_frames_dev(
+            ctx.handle, C.byref(fps), C.byref(cur.out), C.c_int32(nc), C.byref(cur_slots.c), slot_id.ptr,
+            C.c_void_p(d_pose), C.c_void_p(d_src_status) if d_src_status else None,
+            C.byref(id_source) if id_source is not None else None, C.byref(pts.c), C.byref(par), C.byref(opt),
+            out.in_view.ptr, out.track.ptr, out.level.ptr, out.assign.ptr, out.record.ptr), "lorb_track_local_frames_dev")
+    except LorbError:
+        if made:
+            out.free()
+        raise
+    r = dict(out=out, in_view=out.in_view, track=out.track, level=out.level, assign=out.assign, record=out.record)
+    if fetch:
+        r["result"] = out.result()
+    return r
+
+
 class FrameBuilder:
     """lorb_frame_builder of one geometry.  fp: frame-params dict (n_levels, scale_factors, bf, b are
     read); n_desired: features per level (n_levels entries); pattern: the 256 test pairs (1024 ints)."""

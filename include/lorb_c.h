@@ -800,6 +800,121 @@ int lorb_track_local_frames_dev(lorb_ctx* ctx, const lorb_frame_params* frame, c
                                 uint8_t* d_in_view, float* d_track, int32_t* d_level, int32_t* d_assign,
                                 lorb_track_local_frames_result* d_result);
 
+/* ----------------------------------------------------------------------------------------
+ * VisualOdometry::UpdateLocalMap (src/visual_odometry.cpp:234-340) in the frame chain: the local map
+ * built on the device from the slots the motion stage has just written, so that a tracked frame with
+ * the reference's own local map is lorb_frame_build_dev, lorb_track_motion_frames_dev,
+ * lorb_local_map_update_dev, lorb_track_local_frames_dev, lorb_local_map_ids_back_dev and ONE wait.
+ *
+ * The map store is the caller's: a host struct of device arrays with host counts (the mapper changes
+ * the map from the host side).  Ordering convention: keyframe index order stands for the iteration
+ * order of std::map<Frame*, ...>, point index order for that of std::set<MapPoint*>; the adapters
+ * flatten sets the same way.
+ *   points          the n_points map points (points.n); points.in_frame MUST be NULL; points.desc is
+ *                   16-byte aligned
+ *   obs_off/obs_kf  MapPoint::GetObservations() as a CSR over the points: the keyframe indices of
+ *                   point p are obs_kf[obs_off[p] .. obs_off[p + 1]); only membership is read
+ *   kf_bad          Frame::IsBad() per keyframe
+ *   kf_slot_off / kf_slot_point   Frame::GetMapPoints() as a CSR over the keyframes: a global point
+ *                   index, or -1 for a NULL slot
+ *   cov_off/cov_kf  mvpOrderedKeyFrames as a CSR over the keyframes, in the reference's order;
+ *                   GetBestCovisibleFrames(10) reads at most the first 10 of a list (src/frame.cpp:735-741)
+ * n_obs, n_kf_slots and n_cov are the lengths of obs_kf, kf_slot_point and cov_kf: a CSR range is
+ * clipped to them, and an index outside its table (a keyframe outside [0, n_kf), a point outside
+ * [-1, n_points)) is skipped, so a damaged store cannot make the device write out of bounds.
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_map_store {
+  lorb_map_points_dev points;
+  const int32_t* obs_off;        /* n_points + 1 */
+  const int32_t* obs_kf;         /* n_obs */
+  const uint8_t* kf_bad;         /* n_kf */
+  const int32_t* kf_slot_off;    /* n_kf + 1 */
+  const int32_t* kf_slot_point;  /* n_kf_slots */
+  const int32_t* cov_off;        /* n_kf + 1 */
+  const int32_t* cov_kf;         /* n_cov */
+  int32_t n_kf, n_obs, n_kf_slots, n_cov;
+} lorb_map_store;
+
+/* The local map as a device object.  It owns the local table (the arrays of a lorb_map_points_dev of
+ * max_local rows), l2g[max_local] (local row -> global point), g2l[max_points] (global point -> local
+ * row, -1 elsewhere), kf_votes[max_kf] (step 1.1's frameCounter), local_kf[max_kf] (mpLocalKeyFrames in
+ * the reference's order) and its scratch.  create zero-fills every table column once and sets is_bad = 1
+ * in every row.  view returns those arrays; view->points has n = max_local and is handed to
+ * lorb_track_local_frames_dev as it stands: rows at or past the local count have is_bad = 1, and the
+ * local stage skips a bad point before it reads anything else of it.  That stage's candidate layout is
+ * sized by max_local * n_max_cur, which must stay <= 8M. */
+typedef struct lorb_local_map lorb_local_map;
+typedef struct lorb_local_map_arrays {
+  lorb_map_points_dev points;    /* n = max_local, in_frame NULL */
+  const int32_t* l2g;            /* max_local; rows < n_local are written */
+  const int32_t* g2l;            /* max_points; entries < n_points are written */
+  const int32_t* kf_votes;       /* max_kf; entries < n_kf are written */
+  const int32_t* local_kf;       /* max_kf; entries < n_local_kf are written */
+  int32_t max_local, max_kf, max_points;
+} lorb_local_map_arrays;
+typedef struct lorb_local_map_result {
+  int32_t status;      /* 0; 1: a bad count or source status, nothing else was written; 2: n_local > max_local */
+  int32_t n_cur;       /* the count the call read */
+  int32_t n_held;      /* slots non-EMPTY after step c */
+  int32_t n_nulled;    /* slots step c emptied (their point was bad) */
+  int32_t n_voted;     /* keyframes with a vote that are not bad: the list before the expansion */
+  int32_t n_local_kf;  /* the list after the expansion */
+  int32_t refer_kf;    /* pFMax, or -1 when mReferFrame stays */
+  int32_t n_local;     /* local points (the true count also under status 2) */
+} lorb_local_map_result;
+/* max_local, max_kf, max_points >= 1 (LORB_E_INVALID otherwise).  Allocates; waits for the stream. */
+int lorb_local_map_create(lorb_ctx* ctx, int32_t max_local, int32_t max_kf, int32_t max_points, lorb_local_map** out);
+int lorb_local_map_destroy(lorb_local_map* map);
+int lorb_local_map_view(const lorb_local_map* map, lorb_local_map_arrays* out);
+
+/* UpdateLocalMap (src/visual_odometry.cpp:234-340) on the slots of a built frame.  Host values: the
+ * store's counts and n_max_cur.  d_cur->counts[0] is read on the device; d_cur_slots (states read and
+ * written), d_cur_slot_gid (n_max_cur int32: the GLOBAL point index slot j holds, -1 for a point
+ * outside the store -- those UpdateFrame created), d_cur_slot_id (n_max_cur int32, written: the LOCAL
+ * row) and d_result are device memory; d_src_status is nullable (in the frame chain
+ * &d_motion_result->status); ids is nullable.  On the device, in this order:
+ *   a. Status: counts[0] negative or above n_max_cur, or *d_src_status != 0, stores status = 1 and
+ *      NOTHING else, as the two frame calls do.
+ *   b. Entry ids: ids == NULL takes d_cur_slot_gid as given; otherwise slot j's gid is computed from
+ *      the motion stage's codes by exactly the rule of lorb_track_local_id_source, with d_last_slot_id
+ *      and d_cur_slot_gid holding global indices.  An index outside [0, n_points) counts as -1.
+ *   c. Step 1.1 (:241-259), for every non-EMPTY slot j < n_cur with gid g >= 0: point g bad makes the
+ *      slot EMPTY and its gid -1; otherwise every keyframe of the point's observation list gets one
+ *      vote.  Slots with gid -1 vote for nothing (a created point has no observations).
+ *   d. Steps 1.2-1.3 (:263-312): the voted keyframes in ascending index, bad ones skipped, are the
+ *      list; pFMax is the first with the strictly largest vote (:274).  The expansion (:282-307) is an
+ *      INDEX loop over the growing list that stops as soon as the list holds more than 10 entries;
+ *      each visited entry appends the first non-bad frame among the first 10 of its covisible list
+ *      that is not in the list yet, and goes on to the next entry.  (The reference iterates by
+ *      iterator while it push_backs, which is undefined on reallocation: DESIGN section 7.)
+ *   e. Step 2 (:315-336): every non-bad point held in a slot of a local keyframe is local, once, in
+ *      ascending global index: l2g, g2l (-1 elsewhere) and the gathered table rows (pos, normal,
+ *      max_dist, min_dist, desc, locked, is_bad = 0); rows from n_local up to max_local get is_bad = 1.
+ *   f. Local ids: d_cur_slot_id[j] = g2l[gid] for non-EMPTY slots with gid >= 0, else -1.  The local
+ *      stage is then called with ids = NULL and d_src_status = &d_result->status.
+ * n_local > max_local is status 2: the effects of c and d stand, every table row has is_bad = 1,
+ * g2l is -1 throughout, l2g and d_cur_slot_id are untouched and n_local reports the true count.
+ * Nothing at or past a count is written (d_cur_slot_gid / d_cur_slot_id: counts[0]; kf_votes: n_kf;
+ * local_kf: n_local_kf; l2g and the gathered columns: n_local; g2l: n_points).
+ * LORB_E_INVALID, before anything is enqueued: a null required argument, a map of another ctx,
+ * n_max_cur < 1, a negative count, n_points above max_points, n_kf above max_kf, max_local *
+ * n_max_cur > 8M, a non-NULL points.in_frame, a points.desc that is not 16-byte aligned.
+ * Asynchronous on the ctx stream: 5 kernel launches (4 for a store without points), no stream
+ * synchronise, no device-to-host read and no host-to-device copy. */
+int lorb_local_map_update_dev(lorb_ctx* ctx, lorb_local_map* map, const lorb_map_store* store,
+                              const lorb_frame_out* d_cur, int32_t n_max_cur, const lorb_frame_slots* d_cur_slots,
+                              int32_t* d_cur_slot_gid, int32_t* d_cur_slot_id, const int32_t* d_src_status,
+                              const lorb_track_local_id_source* ids, lorb_local_map_result* d_result);
+
+/* After the local stage: the slots' local rows back into the global index space (one launch).  For
+ * each slot j < counts[0]: d_cur_slot_id[j] = lid >= 0 gives d_cur_slot_gid[j] = l2g[lid]; an EMPTY
+ * slot gives -1; any other slot keeps its gid (a held point outside the local map, or a created one).
+ * A count out of range or *d_local_status != 0 (nullable; in the chain the local stage's
+ * &d_result->status) writes nothing.  The gids are the next frame's d_last_slot_id. */
+int lorb_local_map_ids_back_dev(lorb_ctx* ctx, const lorb_local_map* map, const lorb_frame_out* d_cur,
+                                int32_t n_max_cur, const lorb_frame_slots* d_cur_slots, const int32_t* d_cur_slot_id,
+                                const int32_t* d_local_status, int32_t* d_cur_slot_gid);
+
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.
  * obs_frame[k] >= 0 : optimised pose index (PoseMPCost, src/bundle_adjust.cpp:293-301)

@@ -225,6 +225,23 @@ class TrackLocalFramesResult(C.Structure):  # lorb_track_local_frames_result
                 ("status", C.c_int32)]
 
 
+class MapStore(C.Structure):  # lorb_map_store (device addresses, host counts)
+    _fields_ = [("points", MapPointsDev), ("obs_off", C.c_void_p), ("obs_kf", C.c_void_p), ("kf_bad", C.c_void_p),
+                ("kf_slot_off", C.c_void_p), ("kf_slot_point", C.c_void_p), ("cov_off", C.c_void_p),
+                ("cov_kf", C.c_void_p), ("n_kf", C.c_int32), ("n_obs", C.c_int32), ("n_kf_slots", C.c_int32),
+                ("n_cov", C.c_int32)]
+
+
+class LocalMapArrays(C.Structure):  # lorb_local_map_arrays
+    _fields_ = [("points", MapPointsDev), ("l2g", C.c_void_p), ("g2l", C.c_void_p), ("kf_votes", C.c_void_p),
+                ("local_kf", C.c_void_p), ("max_local", C.c_int32), ("max_kf", C.c_int32), ("max_points", C.c_int32)]
+
+
+class LocalMapResult(C.Structure):  # lorb_local_map_result
+    _fields_ = [("status", C.c_int32), ("n_cur", C.c_int32), ("n_held", C.c_int32), ("n_nulled", C.c_int32),
+                ("n_voted", C.c_int32), ("n_local_kf", C.c_int32), ("refer_kf", C.c_int32), ("n_local", C.c_int32)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
-from .runtime import LorbError, lib
+from .runtime import DeviceArray, LorbError, lib
 from .window import ORB_GUARD, ORB_SENTINEL
 
 SIDE_KEYS = ("x", "y", "octave", "size", "angle", "response", "desc")
@@ -255,6 +255,158 @@ def track_local_frames(ctx, fp, cur, cur_slots, slot_id, d_pose, pts, out=None, 
     if fetch:
         r["result"] = out.result()
     return r
+
+
+def _sentinel(ctx, n, dtype):
+    return ctx.to_device(np.full(n * np.dtype(dtype).itemsize, ORB_SENTINEL, np.uint8).view(dtype))
+
+
+def _guarded(ctx, a, dtype, width=1):
+    """Host array a in a device buffer ORB_GUARD entries longer, the guard band ORB_SENTINEL bytes."""
+    a = np.ascontiguousarray(a, dtype).reshape(-1)
+    h = np.full((len(a) + ORB_GUARD * width) * np.dtype(dtype).itemsize, ORB_SENTINEL, np.uint8).view(dtype)
+    h[:len(a)] = a
+    return ctx.to_device(h)
+
+
+class DeviceMapStore:
+    """lorb_map_store in device memory: the map as lorb_local_map_update_dev reads it.
+    pts: dict(pos, normal, max_dist, min_dist, desc, locked, is_bad or None) of n_points rows;
+    obs: per point the list of observing keyframe indices (MapPoint::GetObservations);
+    kf_bad: Frame::IsBad per keyframe; kf_slots: per keyframe its slots' global point indices, -1 for a
+    NULL slot (Frame::GetMapPoints); cov: per keyframe its ordered covisible keyframes
+    (mvpOrderedKeyFrames).  Every array is ORB_GUARD entries longer than its count."""
+
+    def __init__(self, ctx, pts, obs, kf_bad, kf_slots, cov):
+        self.ctx, self.n_points, self.n_kf = ctx, len(pts["pos"]), len(kf_bad)
+        if not (len(obs) == self.n_points and len(kf_slots) == len(cov) == self.n_kf):
+            raise LorbError("store lists disagree with the point / keyframe counts")
+
+        def csr(lists):
+            off = np.zeros(len(lists) + 1, np.int32)
+            off[1:] = np.cumsum([len(x) for x in lists])
+            flat = np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in lists]) if len(lists) else np.zeros(0, np.int32)
+            return off, flat.astype(np.int32)
+
+        (oo, ok), (so, sp), (co, ck) = csr(obs), csr(kf_slots), csr(cov)
+        self.host = dict(obs_off=oo, obs_kf=ok, kf_slot_off=so, kf_slot_point=sp, cov_off=co, cov_kf=ck)
+        conv = dict(pos=(np.float32, 3), normal=(np.float32, 3), max_dist=(np.float32, 1), min_dist=(np.float32, 1),
+                    desc=(np.uint8, 32), locked=(np.uint8, 1), is_bad=(np.uint8, 1))
+        a = self.arrays = {k: _guarded(ctx, pts[k], dt, w) for k, (dt, w) in conv.items() if pts.get(k) is not None}
+        for k, v in self.host.items():
+            a[k] = _guarded(ctx, v, np.int32)
+        a["kf_bad"] = _guarded(ctx, kf_bad, np.uint8)
+        self.c = A.MapStore(
+            A.MapPointsDev(self.n_points, a["pos"].ptr, a["normal"].ptr, a["max_dist"].ptr, a["min_dist"].ptr, a["desc"].ptr,
+                           a["locked"].ptr, a["is_bad"].ptr if "is_bad" in a else None, None),
+            a["obs_off"].ptr, a["obs_kf"].ptr, a["kf_bad"].ptr, a["kf_slot_off"].ptr, a["kf_slot_point"].ptr,
+            a["cov_off"].ptr, a["cov_kf"].ptr, self.n_kf, len(ok), len(sp), len(ck))
+
+    def free(self):
+        for a in self.arrays.values():
+            a.free()
+        self.arrays = {}
+
+
+class DeviceArrayView(DeviceArray):
+    """A DeviceArray over memory somebody else owns: free() leaves it alone."""
+
+    def __init__(self, ctx, addr, shape, dtype):
+        super().__init__(ctx, C.c_void_p(addr), shape, dtype)
+
+    def free(self):
+        pass
+
+
+class LocalMap:
+    """lorb_local_map: the device object lorb_local_map_update_dev fills.  points: the A.MapPointsDev
+    (n = max_local) that track_local_frames takes as pts (through .c and .n, like DevicePoints); l2g,
+    g2l, kf_votes, local_kf and the table columns are DeviceArray views of the object's own memory (not
+    to be freed; the object gives them no guard band beyond their capacity)."""
+    _COLS = dict(pos=(np.float32, 3), normal=(np.float32, 3), max_dist=(np.float32, 1), min_dist=(np.float32, 1),
+                 desc=(np.uint8, 32), locked=(np.uint8, 1), is_bad=(np.uint8, 1))
+
+    def __init__(self, ctx, max_local, max_kf, max_points):
+        self.ctx = ctx
+        self._p = C.c_void_p()
+        ctx.check(lib().lorb_local_map_create(ctx.handle, C.c_int32(max_local), C.c_int32(max_kf), C.c_int32(max_points),
+                                              C.byref(self._p)), "lorb_local_map_create")
+        v = self.view = A.LocalMapArrays()
+        ctx.check(lib().lorb_local_map_view(self._p, C.byref(v)), "lorb_local_map_view")
+        self.max_local, self.max_kf, self.max_points = v.max_local, v.max_kf, v.max_points
+        self.c, self.n = v.points, v.points.n
+
+        def arr(addr, shape, dt):
+            return DeviceArrayView(ctx, addr, shape, dt)
+
+        self.l2g, self.g2l = arr(v.l2g, (self.max_local,), np.int32), arr(v.g2l, (self.max_points,), np.int32)
+        self.kf_votes, self.local_kf = arr(v.kf_votes, (self.max_kf,), np.int32), arr(v.local_kf, (self.max_kf,), np.int32)
+        self.table = {k: arr(getattr(v.points, k), (self.max_local, w) if w > 1 else (self.max_local,), dt)
+                      for k, (dt, w) in self._COLS.items()}
+
+    def fill(self, value=ORB_SENTINEL, table=True):
+        """Every index array (and, with table, every table column but is_bad) set to `value` bytes:
+        what a test does before a call to see afterwards what the call wrote."""
+        arrays = [self.l2g, self.g2l, self.kf_votes, self.local_kf]
+        arrays += [a for k, a in self.table.items() if k != "is_bad"] if table else []
+        for a in arrays:
+            self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, a.ptr, C.c_int(value), C.c_size_t(a.nbytes)), "memset")
+
+    def numpy(self):
+        """dict of every array of the object as it stands (waits for the stream)."""
+        out = dict(l2g=self.l2g.numpy(), g2l=self.g2l.numpy(), kf_votes=self.kf_votes.numpy(), local_kf=self.local_kf.numpy())
+        out.update({k: a.numpy() for k, a in self.table.items()})
+        return out
+
+    def free(self):
+        if self._p:
+            lib().lorb_local_map_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def local_map_buffers(ctx, n_max_cur, gid=None, fill=-77):
+    """(slot gids, slot local ids, record) for local_map_update: DeviceArrays of n_max_cur + ORB_GUARD
+    int32 each -- gids start as `gid` (then `fill`), local ids as `fill` -- and a record of ORB_SENTINEL
+    bytes with ORB_GUARD bytes behind it."""
+    g = np.full(n_max_cur + ORB_GUARD, fill, np.int32)
+    if gid is not None:
+        g[:len(gid)] = np.asarray(gid, np.int32)
+    return (ctx.to_device(g), ctx.to_device(np.full(n_max_cur + ORB_GUARD, fill, np.int32)),
+            _sentinel(ctx, C.sizeof(A.LocalMapResult) + ORB_GUARD, np.uint8))
+
+
+def local_map_result(record):
+    """The A.LocalMapResult in a device record buffer (waits for the stream)."""
+    return A.LocalMapResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.LocalMapResult)])
+
+
+def local_map_update(ctx, lmap, store, cur, cur_slots, slot_gid, slot_id, record, n_max_cur=None, d_src_status=None,
+                     id_source=None):
+    """lorb_local_map_update_dev: UpdateLocalMap on a DeviceFrame's slots, enqueued and nothing else.
+    lmap: LocalMap; store: DeviceMapStore; slot_gid / slot_id / record: DeviceArrays (local_map_buffers);
+    d_src_status: a device address or None; id_source: A.TrackLocalIdSource over GLOBAL ids or None.
+    Returns the device address of the record's status: d_src_status of track_local_frames."""
+    nc = cur_slots.n_max if n_max_cur is None else int(n_max_cur)
+    ctx.check(lib().lorb_local_map_update_dev(
+        ctx.handle, lmap._p, C.byref(store.c), C.byref(cur.out), C.c_int32(nc), C.byref(cur_slots.c), slot_gid.ptr,
+        slot_id.ptr, C.c_void_p(d_src_status) if d_src_status else None,
+        C.byref(id_source) if id_source is not None else None, record.ptr), "lorb_local_map_update_dev")
+    return record.ptr.value + A.LocalMapResult.status.offset
+
+
+def local_map_ids_back(ctx, lmap, cur, cur_slots, slot_id, slot_gid, n_max_cur=None, d_local_status=None):
+    """lorb_local_map_ids_back_dev: the slots' local rows back to global ids after the local stage
+    (enqueued and nothing else).  d_local_status: a device address or None."""
+    nc = cur_slots.n_max if n_max_cur is None else int(n_max_cur)
+    ctx.check(lib().lorb_local_map_ids_back_dev(
+        ctx.handle, lmap._p, C.byref(cur.out), C.c_int32(nc), C.byref(cur_slots.c), slot_id.ptr,
+        C.c_void_p(d_local_status) if d_local_status else None, slot_gid.ptr), "lorb_local_map_ids_back_dev")
 
 
 class FrameBuilder:

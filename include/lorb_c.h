@@ -915,6 +915,51 @@ int lorb_local_map_ids_back_dev(lorb_ctx* ctx, const lorb_local_map* map, const 
                                 int32_t n_max_cur, const lorb_frame_slots* d_cur_slots, const int32_t* d_cur_slot_id,
                                 const int32_t* d_local_status, int32_t* d_cur_slot_gid);
 
+/* ----------------------------------------------------------------------------------------
+ * The pose hand-over between frames as device objects: VisualOdometry::Run's motion model
+ * (src/visual_odometry.cpp:65-66, :119) and Frame::SetPose(Tcw) (src/frame.cpp:570-575) with no host
+ * value in between, so that any number of frames can be enqueued behind one another and waited for once.
+ * Both blocks are plain device memory; the first frame's are uploaded with lorb_memcpy_h2d (the
+ * identity from lorb_frame_pose_from_Tcw, mTcc = I: src/visual_odometry.cpp:84,112).
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_frame_pose {   /* one per frame; a caller keeps two and swaps them with the frames */
+  float Tcw[16];     /* Frame::GetPose()    */
+  float Twc[16];     /* Frame::GetInvPose(): cv::Mat::inv() of Tcw (LU32f) */
+  float pose[6];     /* mRvec | mTvec       */
+  int32_t status;    /* 0; 1: nothing in the block is valid */
+} lorb_frame_pose;
+typedef struct lorb_motion_model { float Tcc[16]; int32_t status; } lorb_motion_model;   /* mTcc */
+
+/* lorb_track_motion_frames_dev with the three poses in device memory.  Every other argument is that
+ * call's.  On the device, in the chain's first launch and before anything else:
+ *   Status: a count negative or above its bound, d_last_pose->status != 0, or d_model given with
+ *     status != 0, stores status = 1 in the record and in d_cur_pose and NOTHING else.
+ *   Prediction, only when d_model is given (:119, then SetPose(Tcw)): d_cur_pose->Tcw = last.Tcw * Tcc
+ *     as cv::gemm on CV_32F (float operands, double accumulation in k order, one rounding to float), Twc
+ *     = cv::Mat::inv() of it, pose = the vector of lorb_Tcw_to_pose, status = 0.  With d_model == NULL
+ *     d_cur_pose is read as given.
+ * The rest of the stage reads both blocks: the fill's Twc is d_last_pose->Twc, a4's motion direction
+ * comes from d_cur_pose->Tcw and d_last_pose->Tcw, the LM starts from d_cur_pose->pose.  Given the same
+ * poses every output has the bits of lorb_track_motion_frames_dev (which computes Twc from last_Tcw).
+ * Asynchronous on the ctx stream: the same launches, no stream synchronise, no copy. */
+int lorb_track_motion_frames_pose_dev(lorb_ctx* ctx, const lorb_frame_params* cur, lorb_frame_pose* d_cur_pose,
+                                      const lorb_frame_out* d_cur, int32_t n_max_cur,
+                                      const lorb_frame_slots* d_cur_slots, int32_t cur_slots_given,
+                                      const lorb_frame_pose* d_last_pose, const lorb_motion_model* d_model,
+                                      const lorb_frame_out* d_last, int32_t n_max_last,
+                                      const lorb_frame_slots* d_last_slots, const uint8_t* d_last_outlier,
+                                      const lorb_track_motion_params* par, const lorb_lm_options* opt,
+                                      int32_t* d_assign, lorb_track_frames_result* d_result);
+
+/* After the local stage (:65-66), one launch.  d_local_result->status == 0: cur.Tcw = the record's Tcw,
+ * cur.pose = (float) of local.pose when local.ok, else pose_in; cur.Twc = cv::Mat::inv() of cur.Tcw;
+ * cur.status = 0; model.Tcc = last.Twc * cur.Tcw (the gemm convention above), model.status = 0.  A
+ * non-zero status stores cur.status = 1 and leaves the model untouched: the next frame's motion stage
+ * then has status 1 too, and so has every frame behind it.  All five arguments are required. */
+int lorb_frame_pose_finish_dev(lorb_ctx* ctx, const lorb_track_local_frames_result* d_local_result,
+                               const lorb_frame_pose* d_last_pose, lorb_frame_pose* d_cur_pose,
+                               lorb_motion_model* d_model);
+
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.
  * obs_frame[k] >= 0 : optimised pose index (PoseMPCost, src/bundle_adjust.cpp:293-301)
@@ -1215,6 +1260,15 @@ int lorb_compute_descriptor_dev(lorb_ctx* ctx, int32_t n_points, const int32_t* 
 
 /* Rodrigues vector -> Tcw (float), cv::Rodrigues semantics (double internally). */
 void lorb_pose_to_Tcw(const float rvec[3], const float tvec[3], float Tcw[16]);
+/* Tcw -> Rodrigues vector | translation: cv::Rodrigues matrix -> vector (OpenCV 3.x cvRodrigues2's
+ * 3 x 3 branch, double internally, the result rounded to float) and column 3
+ * (Frame::UpdatePoseVector, src/frame.cpp:590-605).  The orthogonalisation R <- U * V^T is the
+ * library's own one-sided Jacobi iteration, not OpenCV's.  LORB_E_INVALID on a null
+ * argument. */
+int lorb_Tcw_to_pose(const float Tcw[16], float R[3], float T[3]);
+/* Frame::SetPose(Tcw) (src/frame.cpp:570-575): the matrix as given, the vector of it, Twc =
+ * cv::Mat::inv() (LU32f), status 0.  LORB_E_INVALID on a null argument. */
+int lorb_frame_pose_from_Tcw(const float Tcw[16], lorb_frame_pose* out);
 
 #ifdef __cplusplus
 }

@@ -242,6 +242,14 @@ class LocalMapResult(C.Structure):  # lorb_local_map_result
                 ("n_voted", C.c_int32), ("n_local_kf", C.c_int32), ("refer_kf", C.c_int32), ("n_local", C.c_int32)]
 
 
+class FramePose(C.Structure):  # lorb_frame_pose
+    _fields_ = [("Tcw", C.c_float * 16), ("Twc", C.c_float * 16), ("pose", C.c_float * 6), ("status", C.c_int32)]
+
+
+class MotionModel(C.Structure):  # lorb_motion_model
+    _fields_ = [("Tcc", C.c_float * 16), ("status", C.c_int32)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

@@ -1474,7 +1474,8 @@ __global__ __launch_bounds__(kPoThreads) void k_track_tail(lorb::TrackTail a, LM
 // emptied slots, src/visual_odometry.cpp:128; slots not given are all EMPTY whatever the array holds).
 // The apply runs after the LM: the solve has read slot_pos (the kept slots' points) by then, and the
 // few dozen bytes per slot are not worth a launch of their own.
-__global__ __launch_bounds__(kPoThreads) void k_track_frames_tail(lorb::TrackTail a, lorb::FramesTail f, LMOpt o) {
+// (the body, shared with k_track_frames_tail_pose)
+__device__ __forceinline__ void track_frames_tail_run(lorb::TrackTail& a, const lorb::FramesTail& f, const LMOpt& o) {
   int n_last;
   if (!lorb::frame_counts(f.dc, &n_last, &a.nk)) return;
   const bool retry = track_tail_run(a, o);
@@ -1494,6 +1495,17 @@ __global__ __launch_bounds__(kPoThreads) void k_track_frames_tail(lorb::TrackTai
       f.cur.state[j] = LORB_SLOT_EMPTY;
     }
   }
+}
+__global__ __launch_bounds__(kPoThreads) void k_track_frames_tail(lorb::TrackTail a, lorb::FramesTail f, LMOpt o) {
+  track_frames_tail_run(a, f, o);
+}
+// The tail of lorb_track_motion_frames_pose_dev: the LM starts from the pose the chain's first kernel
+// left in its MotionPose block (f.dc.last is that block's n_last: -1 on status 1, and the kernel returns).
+__global__ __launch_bounds__(kPoThreads) void k_track_frames_tail_pose(lorb::TrackTail a, lorb::FramesTail f,
+                                                                       const lorb::MotionPose* __restrict__ pose, LMOpt o) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) a.pose_init[k] = pose->pose_init[k];
+  track_frames_tail_run(a, f, o);
 }
 
 // The tail of the local-map tracking chain (VisualOdometry::EstimatePoseLocal after its matcher
@@ -1973,6 +1985,12 @@ int launch_track_frames_tail(lorb_ctx* ctx, const TrackTail& t, const FramesTail
   LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
 }
+int launch_track_frames_tail_pose(lorb_ctx* ctx, const TrackTail& t, const FramesTail& f, const MotionPose* pose,
+                                  const lorb_lm_options* opt) {
+  hipLaunchKernelGGL(k_track_frames_tail_pose, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, f, pose, to_dev_opt(opt));
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
 }  // namespace lorb
 
 extern "C" {
@@ -2144,5 +2162,26 @@ int lorb_ba_pose_only_dev(lorb_ctx* ctx, const lorb_pose_problem_batch* d_prob, 
 // restatement, which rounds like the reference's un-contracted host build whatever -march the
 // library is built with)
 void lorb_pose_to_Tcw(const float rvec[3], const float tvec[3], float T[16]) { lorb::pose_to_Tcw(rvec, tvec, T); }
+
+// cv::Rodrigues (matrix -> vector) + Frame::UpdatePoseVector's translation (lorb::Tcw_to_rvec, which
+// turns contraction off in its own body for the same reason)
+int lorb_Tcw_to_pose(const float Tcw[16], float R[3], float T[3]) {
+  if (!Tcw || !R || !T) return LORB_E_INVALID;
+  lorb::Tcw_to_rvec(Tcw, R);
+  T[0] = Tcw[3]; T[1] = Tcw[7]; T[2] = Tcw[11];
+  return LORB_OK;
+}
+
+// Frame::SetPose(Tcw): the host's way to make a frame's first block (lorb::inv4_lu32f is float only and
+// lives in lorb_window.hip, compiled -ffp-contract=off)
+int lorb_frame_pose_from_Tcw(const float Tcw[16], lorb_frame_pose* out) {
+  if (!Tcw || !out) return LORB_E_INVALID;
+  memcpy(out->Tcw, Tcw, sizeof(out->Tcw));
+  lorb::inv4_lu32f(Tcw, out->Twc);
+  lorb::Tcw_to_rvec(Tcw, out->pose);
+  out->pose[3] = Tcw[3]; out->pose[4] = Tcw[7]; out->pose[5] = Tcw[11];
+  out->status = 0;
+  return LORB_OK;
+}
 
 }  // extern "C"

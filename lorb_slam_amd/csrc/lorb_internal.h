@@ -412,6 +412,141 @@ __host__ __device__ inline void pose_to_Tcw(const float rvec[3], const float tve
   T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
 }
 
+// R <- U * V^T of the SVD of a 3 x 3 double matrix (row-major, in place): the orthogonal polar factor,
+// which is unique for a non-singular R whatever the order and the signs of the singular vectors, so no
+// sorting.  One-sided Jacobi (Hestenes): plane rotations from the right make the columns of A = R * V
+// orthogonal, then U = A * diag(1 / |a_j|).  A column of norm zero (a singular R: no rotation) stays
+// zero where OpenCV's JacobiSVD completes U with a vector of its own.  Every index is a compile-time
+// constant after unrolling: the matrices stay in registers on the device.
+__host__ __device__ inline void polar_uvt3(double R[9]) {
+#pragma clang fp contract(off)
+  double A[9], V[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) { A[k] = R[k]; V[k] = (k % 4 == 0) ? 1.0 : 0.0; }
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    bool changed = false;
+#pragma unroll
+    for (int pq = 0; pq < 3; ++pq) {
+      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+      const double al = A[p] * A[p] + A[3 + p] * A[3 + p] + A[6 + p] * A[6 + p];
+      const double be = A[q] * A[q] + A[3 + q] * A[3 + q] + A[6 + q] * A[6 + q];
+      const double ga = A[p] * A[q] + A[3 + p] * A[3 + q] + A[6 + p] * A[6 + q];
+      if (fabs(ga) <= 2.220446049250313e-16 * sqrt(al * be)) continue;  // also a zero column
+      changed = true;
+      const double zeta = (be - al) / (2.0 * ga);
+      const double t = (zeta < 0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double x = A[3 * i + p], y = A[3 * i + q];
+        A[3 * i + p] = c * x - s * y;
+        A[3 * i + q] = s * x + c * y;
+        const double vx = V[3 * i + p], vy = V[3 * i + q];
+        V[3 * i + p] = c * vx - s * vy;
+        V[3 * i + q] = s * vx + c * vy;
+      }
+    }
+    if (!changed) break;
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double n = sqrt(A[j] * A[j] + A[3 + j] * A[3 + j] + A[6 + j] * A[6 + j]);
+    const double inv = n > 0 ? 1.0 / n : 0.0;
+    A[j] *= inv; A[3 + j] *= inv; A[6 + j] *= inv;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) R[3 * i + k] = A[3 * i] * V[3 * k] + A[3 * i + 1] * V[3 * k + 1] + A[3 * i + 2] * V[3 * k + 2];
+}
+
+// cv::Rodrigues (matrix -> vector) of the rotation block of a 4 x 4 float pose: OpenCV 3.x
+// cvRodrigues2's 3 x 3 branch, all arithmetic in double, the vector rounded to float; the counterpart of
+// pose_to_Tcw, the body of lorb_Tcw_to_pose, and on the device the motion-model prediction's
+// Frame::UpdatePoseVector.  Contraction is off in the body as there; the orthogonalisation is
+// polar_uvt3, and the device's double acos is not libm's function.
+__host__ __device__ inline void Tcw_to_rvec(const float T[16], float rvec[3]) {
+#pragma clang fp contract(off)
+  double R[9];
+  bool in_range = true;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    R[k] = (double)T[4 * (k / 3) + k % 3];
+    in_range = in_range && R[k] >= -100.0 && R[k] < 100.0;  // cv::checkRange: false on NaN / inf too
+  }
+  double rx = 0, ry = 0, rz = 0;
+  if (in_range) {
+    polar_uvt3(R);
+    rx = R[7] - R[5]; ry = R[2] - R[6]; rz = R[3] - R[1];
+    const double s = sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
+    double c = (R[0] + R[4] + R[8] - 1) * 0.5;
+    c = c > 1. ? 1. : c < -1. ? -1. : c;
+    double theta = acos(c);
+    if (s < 1e-5) {
+      if (c > 0) {
+        rx = 0; ry = 0; rz = 0;
+      } else {
+        double t = (R[0] + 1) * 0.5;
+        rx = sqrt(t > 0. ? t : 0.);
+        t = (R[4] + 1) * 0.5;
+        ry = sqrt(t > 0. ? t : 0.) * (R[1] < 0 ? -1. : 1.);
+        t = (R[8] + 1) * 0.5;
+        rz = sqrt(t > 0. ? t : 0.) * (R[2] < 0 ? -1. : 1.);
+        if (fabs(rx) < fabs(ry) && fabs(rx) < fabs(rz) && (R[5] > 0) != (ry * rz > 0)) rz = -rz;
+        theta /= sqrt(rx * rx + ry * ry + rz * rz);
+        rx *= theta; ry *= theta; rz *= theta;
+      }
+    } else {
+      double vth = 1 / (2 * s);
+      vth *= theta;
+      rx *= vth; ry *= vth; rz *= vth;
+    }
+  }
+  rvec[0] = (float)rx; rvec[1] = (float)ry; rvec[2] = (float)rz;
+}
+
+// C = A * B for 4 x 4 CV_32F through cv::gemm: float operands, double accumulation in k order, one
+// rounding to float (the convention of the oracle's gemv3_row).  C may alias neither operand.
+__host__ __device__ inline void gemm4_f32(const float* A, const float* B, float* C) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      double s = (double)A[4 * i] * (double)B[j];
+#pragma unroll
+      for (int k = 1; k < 4; ++k) s += (double)A[4 * i + k] * (double)B[4 * k + j];
+      C[4 * i + j] = (float)s;
+    }
+}
+
+// a4's motion direction (src/matcher.cpp:74-87) from the two poses: Rcw / tcw of the current frame,
+// twc = -Rcw^T * tcw, tlc = Rlw * twc + tlw (cv::gemm: double accumulation), its z against the
+// baseline.  One definition for the host-pose calls (frame_params_a4) and the device-pose chain's
+// first kernel (lorb_window.hip, compiled -ffp-contract=off; the pragma keeps it so anywhere else).
+__host__ __device__ inline void a4_motion_direction(const float* cur_Tcw, const float* last_Tcw, float b, float Rcw[9],
+                                                    float tcw[3], int* mode_forward, int* mode_backward) {
+#pragma clang fp contract(off)
+  const float* T = cur_Tcw;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Rcw[3 * r + c] = T[4 * r + c];
+    tcw[r] = T[4 * r + 3];
+  }
+  float twc[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const double s = (double)Rcw[i] * tcw[0] + (double)Rcw[3 + i] * tcw[1] + (double)Rcw[6 + i] * tcw[2];
+    twc[i] = (float)(-s);
+  }
+  const float* L = last_Tcw;
+  const double s2 = (double)L[8] * twc[0] + (double)L[9] * twc[1] + (double)L[10] * twc[2];
+  const float tlc2 = (float)(s2 + (double)L[11]);
+  *mode_forward = tlc2 > b;
+  *mode_backward = -tlc2 > b;
+}
+
 // The tail of the motion-tracking chain (lorb_track_motion*, lorb_window.hip): one launch of
 // k_track_tail (lorb_ba.hip) after both a4 passes -- pass decision, final assign, residual
 // compaction, pose-only LM, result record.  All pointers are device pointers.
@@ -454,6 +589,19 @@ struct FramesTail {
   int given;  // 0: the current slots are all EMPTY on entry, whatever the arrays hold
 };
 int launch_track_frames_tail(lorb_ctx* ctx, const TrackTail& t, const FramesTail& f, const lorb_lm_options* opt);
+
+// The device-pose form of that chain (lorb_track_motion_frames_pose_dev).  Its first kernel
+// (k_slots_fill's POSE form, lorb_window.hip) leaves this block in device memory; the candidate kernel
+// and the tail read from it what the host-pose form bakes into their kernel arguments (WinParams::Rcw /
+// tcw / mode_*, TrackTail::pose_init).  n_last is the last frame's count, or -1 when the call's status
+// is 1: as FrameCounts::last of the later kernels it makes every one of them return on that status.
+struct MotionPose {
+  float Rcw[9], tcw[3], pose_init[6];
+  int mode_forward, mode_backward, n_last;
+};
+// k_track_frames_tail_pose (lorb_ba.hip): k_track_frames_tail started from pose->pose_init
+int launch_track_frames_tail_pose(lorb_ctx* ctx, const TrackTail& t, const FramesTail& f, const MotionPose* pose,
+                                  const lorb_lm_options* opt);
 
 // The tail of the local-map tracking chain (lorb_track_local*, lorb_window.hip): one launch of
 // k_local_tail (lorb_ba.hip) after a8 + a5 -- the in-view count, the nmatches > min_matches gate,
@@ -625,9 +773,10 @@ inline constexpr SlotFamily
     S_TM = {88, 3, false},    // motion chain: pass 2's codes + both counts, the residual list, the host form's codes
     S_TF = {91, 1, false},    // frames chain (which also uses S_TM 0 and 1): the last frame's mp_locked flags
     S_TLC = {92, 6, false},   // local-map chain: match count, residual list; the host form's codes, in-view flags, fields, levels
-    S_TLF = {98, 2, false};   // its frames form (which also uses S_TLC 0 and 1): the LocalPose block, the in_frame mask
+    S_TLF = {98, 2, false},   // its frames form (which also uses S_TLC 0 and 1): the LocalPose block, the in_frame mask
+    S_TP = {100, 1, false};   // the frames chain's device-pose form (which also uses S_TM 0 and 1 and S_TF): the MotionPose block
 inline constexpr SlotFamily kSlotPlan[] = {
-    {S_BF_Q, 14, false}, {S_W0, 10, false}, S_KP, S_WX, S_ST, S_ORB, S_TL, S_TM, S_TF, S_TLC, S_TLF,
+    {S_BF_Q, 14, false}, {S_W0, 10, false}, S_KP, S_WX, S_ST, S_ORB, S_TL, S_TM, S_TF, S_TLC, S_TLF, S_TP,
     {S_BF_TKEY, 1, true}, {S_IO_IN, 1, true}, {S_IO_OUT, 1, true}, {S_BF_DONE, 1, true}, {S_TM_ZERO, 1, true}};
 
 // slot K of family F; an offset past the family's end does not compile

@@ -372,15 +372,19 @@ __device__ __forceinline__ FrameQuery frame_query(int i, const uint8_t* __restri
   q.o = loct[i];
   return q;
 }
-template <bool WRITE>
+// (kDevPose: Rcw, tcw and the two modes are the MotionPose block's, not P's -- P stays the kernel
+// argument it is either way: scale_factors is indexed by the octave)
+template <bool WRITE, bool kDevPose = false>
 __device__ __forceinline__ int cand_frame_one(const KpDev& K, const WinParams& P, const FrameQuery& q,
-                                              const uint4* qdesc, int2* out) {
+                                              const uint4* qdesc, int2* out, const lorb::MotionPose* mp = nullptr) {
   int cnt = 0;
   if (q.act) {
     const float X = q.X, Y = q.Y, Z = q.Z;
-    const float xc = gemv3(P.Rcw + 0, X, Y, Z, P.tcw[0]);
-    const float yc = gemv3(P.Rcw + 3, X, Y, Z, P.tcw[1]);
-    const float zc = gemv3(P.Rcw + 6, X, Y, Z, P.tcw[2]);
+    const float* Rcw = kDevPose ? mp->Rcw : P.Rcw;
+    const float* tcw = kDevPose ? mp->tcw : P.tcw;
+    const float xc = gemv3(Rcw + 0, X, Y, Z, tcw[0]);
+    const float yc = gemv3(Rcw + 3, X, Y, Z, tcw[1]);
+    const float zc = gemv3(Rcw + 6, X, Y, Z, tcw[2]);
     const float invzc = (float)(1.0 / (double)zc);
     if (!(invzc < 0)) {
       const float u = P.fp.fx * xc * invzc + P.fp.cx;
@@ -389,8 +393,8 @@ __device__ __forceinline__ int cand_frame_one(const KpDev& K, const WinParams& P
         const int o = q.o;
         const float radius = P.th * P.fp.scale_factors[o];
         int mn, mx;
-        if (P.mode_forward) { mn = o; mx = -1; }
-        else if (P.mode_backward) { mn = 0; mx = o; }
+        if (kDevPose ? mp->mode_forward : P.mode_forward) { mn = o; mx = -1; }
+        else if (kDevPose ? mp->mode_backward : P.mode_backward) { mn = 0; mx = o; }
         else { mn = o - 1; mx = o + 1; }
         const float ur = u - P.fp.bf * invzc;
         cnt = walk_candidates_wave<WRITE>(K, P.fp, u, v, radius, mn, mx, ur, radius, qdesc, out);
@@ -402,7 +406,9 @@ __device__ __forceinline__ int cand_frame_one(const KpDev& K, const WinParams& P
 // kDevCount (the frames chain): launched over the bounds (nl = dc.max_last, K.n = dc.max_cur, which
 // is also the stride); the counts are read first, a workgroup wholly past n_last leaves before it
 // stages anything, a wave past it loads no query
-template <bool WRITE, bool GRID = false, bool kDevCount = false>
+// kDevPose (that chain's device-pose form): P's pose part -- Rcw, tcw, the two modes -- is read from the
+// block the chain's first kernel left, and dc.last points at that block's n_last
+template <bool WRITE, bool GRID = false, bool kDevCount = false, bool kDevPose = false>
 __global__ __launch_bounds__(64 * kCandWaves) void k_cand_frame(KpDev K, WinParams P, int nl,
                                                     const uint8_t* __restrict__ has_mp,
                                                     const uint8_t* __restrict__ outlier,
@@ -412,7 +418,8 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_cand_frame(KpDev K, WinPara
                                                     int* __restrict__ cand_cnt, const int* __restrict__ cand_off,
                                                     int2* __restrict__ cand, int stride = 0,
                                                     const int* __restrict__ skip_unless = nullptr, int skip_max = 0,
-                                                    lorb::FrameCounts dc = {}) {
+                                                    lorb::FrameCounts dc = {},
+                                                    const lorb::MotionPose* __restrict__ mp = nullptr) {
   if (kDevCount) {
     if (!lorb::frame_counts(dc, &nl, &K.n)) return;
     if ((int)blockIdx.x * kCandWaves >= nl) return;
@@ -429,9 +436,9 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_cand_frame(KpDev K, WinPara
     K = stage_grid<64 * kCandWaves>(K, P.fp, L);
   }
   if (i >= nl) return;
-  const int cnt = cand_frame_one<WRITE>(
+  const int cnt = cand_frame_one<WRITE, kDevPose>(
       K, P, q, ldesc + 2 * (size_t)i,
-      WRITE ? cand + (stride > 0 ? (size_t)i * stride : (size_t)cand_off[i]) : nullptr);
+      WRITE ? cand + (stride > 0 ? (size_t)i * stride : (size_t)cand_off[i]) : nullptr, mp);
   if ((!WRITE || stride > 0) && (threadIdx.x & 63) == 0) cand_cnt[i] = cnt;
 }
 
@@ -865,6 +872,49 @@ __global__ __launch_bounds__(256) void k_unproject(lorb_frame_params fp, lorb::M
 //   MODE LORB_SLOTS_INITIALIZE (:86-99): depth >= 0 -> LOCKED with the same; depth < 0 -> EMPTY.
 // CHAIN (the frames chain): both counts are checked and the record's status, counts and n_created
 // written here, the chain's first kernel; `locked` receives state == LOCKED (a4's mp_locked).
+// POSE (that chain's device-pose form, lorb_track_motion_frames_pose_dev): the status also covers the
+// two blocks' status words; thread 0 -- beside the slot walk, as in k_local_head -- runs the
+// motion-model prediction (src/visual_odometry.cpp:119, then Frame::SetPose(Tcw)) into the current
+// frame's block when a model is given, and leaves a4's motion direction and the LM's start in the
+// MotionPose block for the kernels behind it; the fill's Twc is the last frame's block's.
+struct PoseChain {
+  lorb_frame_pose* cur;
+  const lorb_frame_pose* last;
+  const lorb_motion_model* model;  // or null: *cur as given
+  lorb::MotionPose* blk;
+};
+// (one thread) the prediction where a model is given, then what the chain reads of the two poses
+__device__ __forceinline__ void motion_predict(const PoseChain& pc, float baseline) {
+  float Tcw[16], pose[6];
+  if (pc.model) {
+    float Twc[16];
+    lorb::gemm4_f32(pc.last->Tcw, pc.model->Tcc, Tcw);  // pF->GetPose() * mTcc
+    lorb::inv4_lu32f(Tcw, Twc);
+    lorb::Tcw_to_rvec(Tcw, pose);
+    pose[3] = Tcw[3]; pose[4] = Tcw[7]; pose[5] = Tcw[11];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { pc.cur->Tcw[k] = Tcw[k]; pc.cur->Twc[k] = Twc[k]; }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) pc.cur->pose[k] = pose[k];
+    pc.cur->status = 0;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) Tcw[k] = pc.cur->Tcw[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) pose[k] = pc.cur->pose[k];
+  }
+  float Rcw[9], tcw[3];
+  int fwd, bwd;
+  lorb::a4_motion_direction(Tcw, pc.last->Tcw, baseline, Rcw, tcw, &fwd, &bwd);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) pc.blk->Rcw[k] = Rcw[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pc.blk->tcw[k] = tcw[k];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) pc.blk->pose_init[k] = pose[k];
+  pc.blk->mode_forward = fwd;
+  pc.blk->mode_backward = bwd;
+}
 struct SlotFill {
   lorb_frame_params fp;
   lorb::Mat4f Twc;
@@ -878,13 +928,26 @@ struct SlotFill {
   uint8_t* locked;  // or null
   int* n_created;   // or null
 };
-template <int MODE, bool CHAIN>
+template <int MODE, bool CHAIN, bool POSE = false>
 __global__ __launch_bounds__(1024) void k_slots_fill(SlotFill a, lorb::FrameCounts dc,
-                                                     lorb_track_frames_result* __restrict__ rec) {
+                                                     lorb_track_frames_result* __restrict__ rec, PoseChain pc = {}) {
   __shared__ int wsum[16];
   const int t = threadIdx.x;
   int n, n_cur = 0;
-  if (CHAIN) {
+  lorb::Mat4f twc_blk;  // POSE only
+  if constexpr (POSE) {
+    static_assert(CHAIN, "the device-pose form is a form of the chain");
+    const bool ok = lorb::frame_counts(dc, &n, &n_cur) && pc.last->status == 0 && !(pc.model && pc.model->status != 0);
+    if (t == 0) {
+      rec->status = ok ? 0 : 1;
+      pc.blk->n_last = ok ? n : -1;
+      if (!ok) pc.cur->status = 1;
+    }
+    if (!ok) return;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) twc_blk.v[k] = pc.last->Twc[k];
+    if (t == 0) motion_predict(pc, a.fp.b);
+  } else if (CHAIN) {
     const bool ok = lorb::frame_counts(dc, &n, &n_cur);
     if (t == 0) rec->status = ok ? 0 : 1;
     if (!ok) return;
@@ -908,7 +971,7 @@ __global__ __launch_bounds__(1024) void k_slots_fill(SlotFill a, lorb::FrameCoun
       st = fill ? LORB_SLOT_LOCKED : LORB_SLOT_EMPTY;
     }
     if (fill) {
-      unproject_kp(a.fp, a.Twc, a.x[i], a.y[i], a.depth[i], a.pos + 3 * (size_t)i);
+      unproject_kp(a.fp, POSE ? twc_blk : a.Twc, a.x[i], a.y[i], a.depth[i], a.pos + 3 * (size_t)i);
       a.sdesc[2 * (size_t)i] = a.desc[2 * (size_t)i];
       a.sdesc[2 * (size_t)i + 1] = a.desc[2 * (size_t)i + 1];
       made++;
@@ -1042,6 +1105,34 @@ __global__ __launch_bounds__(1024) void k_local_head(LocalHead a) {
   if (t == 0) { a.rec->n_held = n_held; a.rec->n_in_frame = n_inf; }
 }
 
+// VisualOdometry::Run :65-66 after the local stage, one thread: the frame's block from the local
+// record (Frame::SetPose of the optimised pose) and mTcc = last.Twc * cur.Tcw
+struct PoseFinish {
+  const lorb_track_local_frames_result* rec;
+  const lorb_frame_pose* last;
+  lorb_frame_pose* cur;
+  lorb_motion_model* model;
+};
+__global__ __launch_bounds__(64) void k_pose_finish(PoseFinish a) {
+  if (threadIdx.x != 0) return;
+  if (a.rec->status != 0) {
+    a.cur->status = 1;
+    return;
+  }
+  float Tcw[16], Twc[16], Tcc[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) Tcw[k] = a.rec->Tcw[k];
+  inv4_lu32f(Tcw, Twc);
+  lorb::gemm4_f32(a.last->Twc, Tcw, Tcc);
+  const bool ok = a.rec->local.ok != 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) a.cur->pose[k] = ok ? (float)a.rec->local.pose[k] : a.rec->pose_in[k];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) { a.cur->Tcw[k] = Tcw[k]; a.cur->Twc[k] = Twc[k]; a.model->Tcc[k] = Tcc[k]; }
+  a.cur->status = 0;
+  a.model->status = 0;
+}
+
 // a frame's keypoints (Frame::mvKeysUn, mDescriptors, slot states) for the host-array entry points:
 // packed into their InPack (one pull for every input), then the device grid built
 struct KpParts {
@@ -1094,21 +1185,8 @@ WinParams frame_params_a4(const lorb_frame_params* cur, const float* cur_Tcw, co
   P.fp = *cur;
   P.th = th;
   P.oct_limit = std::min(std::max(oct_limit, 0), LORB_MAX_LEVELS);
-  const float* T = cur_Tcw;
-  const float Rcw[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-  const float tcw[3] = {T[3], T[7], T[11]};
-  memcpy(P.Rcw, Rcw, sizeof(Rcw));
-  memcpy(P.tcw, tcw, sizeof(tcw));
-  float twc[3];
-  for (int i = 0; i < 3; i++) {
-    const double s = (double)Rcw[i] * tcw[0] + (double)Rcw[3 + i] * tcw[1] + (double)Rcw[6 + i] * tcw[2];
-    twc[i] = (float)(-s);
-  }
-  const float* L = last_Tcw;
-  const double s2 = (double)L[8] * twc[0] + (double)L[9] * twc[1] + (double)L[10] * twc[2];
-  const float tlc2 = (float)(s2 + (double)L[11]);
-  P.mode_forward = tlc2 > cur->b;
-  P.mode_backward = -tlc2 > cur->b;
+  // (null poses: the chain's device-pose form, whose candidate kernel reads this part from its block)
+  if (cur_Tcw) lorb::a4_motion_direction(cur_Tcw, last_Tcw, cur->b, P.Rcw, P.tcw, &P.mode_forward, &P.mode_backward);
   return P;
 }
 
@@ -1232,12 +1310,16 @@ int search_issue(lorb_ctx* ctx, KpDev* K, const lorb_frame_params& fp, int nq, c
 // a4 on device-resident inputs, for the host-array call, the device-pointer call and the motion
 // chain (whose second pass over the same *K is predicated on the first's count)
 int a4_issue(lorb_ctx* ctx, KpDev* K, const WinParams& P, const LastDev& L, int* dassign, int* dnm, int* out,
-             const int* skip_unless = nullptr, int skip_max = 0, const lorb::FrameCounts* dc = nullptr) {
+             const int* skip_unless = nullptr, int skip_max = 0, const lorb::FrameCounts* dc = nullptr,
+             const lorb::MotionPose* mp = nullptr) {  // mp (with dc): P's pose part lives in that block
   return search_issue<1>(
       ctx, K, P.fp, L.n, L.lk, L.la, {dassign, dnm, out, skip_unless, skip_max},
       [&](auto pass, unsigned g, int* cnt, const int* off, int2* cand, int stride) {
         using Pass = decltype(pass);
-        if (dc)
+        if (dc && mp)
+          hipLaunchKernelGGL((k_cand_frame<Pass::write, Pass::grid, true, true>), dim3(g), dim3(256), 0, ctx->stream, *K, P,
+                             L.n, L.hm, L.ol, L.pos, L.lo, L.ld, cnt, off, cand, stride, skip_unless, skip_max, *dc, mp);
+        else if (dc)
           hipLaunchKernelGGL((k_cand_frame<Pass::write, Pass::grid, true>), dim3(g), dim3(256), 0, ctx->stream, *K, P, L.n,
                              L.hm, L.ol, L.pos, L.lo, L.ld, cnt, off, cand, stride, skip_unless, skip_max, *dc);
         else
@@ -1372,12 +1454,14 @@ int lorb_search_by_projection_frame_dev(lorb_ctx* ctx, const lorb_frame_params* 
 // pass reuses the first's keypoint grid and working buffers (the stream orders them).
 // fr (lorb_track_motion_frames_dev): K.n and L.n are the caller's bounds (both >= 1), every kernel
 // reads the counts of fr->dc, and the tail is k_track_frames_tail, which also applies the codes to
-// the current frame's slots.
+// the current frame's slots.  mp (with fr: lorb_track_motion_frames_pose_dev): cur_Tcw, pose_init and
+// last_Tcw are null, the candidate kernels and the tail read the MotionPose block *mp instead.
 static int track_motion_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const float* cur_Tcw,
                               const float* pose_init, KpDev K, const float* slot_pos, const LastDev& L,
                               const float* last_Tcw, const lorb_track_motion_params* par,
                               const lorb_lm_options* opt, int* d_assign, lorb_track_motion_result* rec,
-                              int* assign_out, const lorb::FramesTail* fr = nullptr) {
+                              int* assign_out, const lorb::FramesTail* fr = nullptr,
+                              const lorb::MotionPose* mp = nullptr) {
   const int nk = K.n;
   const lorb::FrameCounts* dc = fr ? &fr->dc : nullptr;
   int* tm;  // pass 2's codes (nk) | its count | pass 1's count
@@ -1393,18 +1477,19 @@ static int track_motion_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const
     LORB_TRY(empty_slots(ctx, nk, &z));
     if (!given) K.slot_state = z;
     LORB_TRY(a4_issue(ctx, &K, frame_params_a4(cur, cur_Tcw, last_Tcw, par->th_first, cur->n_levels), L, d_assign, nm1,
-                      nullptr, nullptr, 0, dc));
+                      nullptr, nullptr, 0, dc, mp));
     K.slot_state = z;  // src/visual_odometry.cpp:128: the retry starts from emptied slots
     LORB_TRY(a4_issue(ctx, &K, frame_params_a4(cur, cur_Tcw, last_Tcw, par->th_retry, cur->n_levels), L, tm, nm2, nullptr,
-                      nm1, par->min_matches, dc));
+                      nm1, par->min_matches, dc, mp));
   }
   lorb::TrackTail t{};
   t.nk = nk; t.nm1 = nm1; t.nm2 = nm2; t.assign2 = tm; t.assign = d_assign;
   t.slot_state = given; t.slot_pos = slot_pos; t.last_pos = L.pos; t.x = K.x; t.y = K.y;
   t.min_matches = par->min_matches;
   t.fx = cur->fx; t.fy_eff = par->fy_eff; t.cx = cur->cx; t.cy = cur->cy;
-  memcpy(t.pose_init, pose_init, sizeof(t.pose_init));
+  if (pose_init) memcpy(t.pose_init, pose_init, sizeof(t.pose_init));
   t.list = list; t.rec = rec; t.assign_out = assign_out;
+  if (fr && mp) return lorb::launch_track_frames_tail_pose(ctx, t, *fr, mp, opt);
   if (fr) return lorb::launch_track_frames_tail(ctx, t, *fr, opt);
   return lorb::launch_track_tail(ctx, t, opt);
 }
@@ -1466,20 +1551,26 @@ int lorb_track_motion(lorb_ctx* ctx, const lorb_frame_params* cur, const float c
   return LORB_OK;
 }
 
-// the fill launch of lorb_frame_slots_fill_dev and of the frames chain (dc / rec given)
+// the fill launch of lorb_frame_slots_fill_dev and of the frames chain (dc / rec given; pc: its
+// device-pose form, Tcw null)
 static int slots_fill_issue(lorb_ctx* ctx, const lorb_frame_params* frame, const float* Tcw, const lorb_frame_out* f,
                             int n_max, int mode, const lorb_frame_slots* s, uint8_t* locked, int* n_created,
-                            const lorb::FrameCounts* dc, lorb_track_frames_result* rec) {
+                            const lorb::FrameCounts* dc, lorb_track_frames_result* rec, const PoseChain* pc = nullptr) {
   SlotFill a{};
   a.fp = *frame;
-  float Twc[16];
-  inv4_lu32f(Tcw, Twc);
-  memcpy(a.Twc.v, Twc, sizeof(a.Twc.v));
+  if (Tcw) {
+    float Twc[16];
+    inv4_lu32f(Tcw, Twc);
+    memcpy(a.Twc.v, Twc, sizeof(a.Twc.v));
+  }
   a.count = f->counts; a.n_max = n_max;
   a.x = f->left.x; a.y = f->left.y; a.depth = f->depth; a.desc = reinterpret_cast<const uint4*>(f->left.desc);
   a.state = s->state; a.pos = s->pos; a.sdesc = reinterpret_cast<uint4*>(s->desc);
   a.locked = locked; a.n_created = n_created;
-  if (dc)
+  if (dc && pc)
+    hipLaunchKernelGGL((k_slots_fill<LORB_SLOTS_UPDATE_FRAME, true, true>), dim3(1), dim3(1024), 0, ctx->stream, a, *dc, rec,
+                       *pc);
+  else if (dc)
     hipLaunchKernelGGL((k_slots_fill<LORB_SLOTS_UPDATE_FRAME, true>), dim3(1), dim3(1024), 0, ctx->stream, a, *dc, rec);
   else if (mode == LORB_SLOTS_UPDATE_FRAME)
     hipLaunchKernelGGL((k_slots_fill<LORB_SLOTS_UPDATE_FRAME, false>), dim3(1), dim3(1024), 0, ctx->stream, a,
@@ -1510,16 +1601,13 @@ int lorb_frame_slots_fill_dev(lorb_ctx* ctx, const lorb_frame_params* frame, con
 // built frames whose counts stay in device memory: the UpdateFrame fill of the last frame's slots
 // (which also checks the counts and writes the record's status), the motion chain in its device-count
 // form over the caller's bounds, and the tail that applies the codes to the current frame's slots.
-int lorb_track_motion_frames_dev(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16],
-                                 const float pose_init[6], const lorb_frame_out* d_cur, int32_t n_max_cur,
-                                 const lorb_frame_slots* d_cur_slots, int32_t cur_slots_given,
-                                 const float last_Tcw[16], const lorb_frame_out* d_last, int32_t n_max_last,
-                                 const lorb_frame_slots* d_last_slots, const uint8_t* d_last_outlier,
-                                 const lorb_track_motion_params* par, const lorb_lm_options* opt,
-                                 int32_t* d_assign, lorb_track_frames_result* d_result) {
-  if (!ctx || !cur || !cur_Tcw || !pose_init || !d_cur || !d_cur_slots || !last_Tcw || !d_last || !d_last_slots || !par ||
-      !opt || !d_assign || !d_result)
-    return LORB_E_INVALID;
+// (both forms: the host poses, or pose -- cur, last and model of the device-pose form, blk unset)
+static int track_frames_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const float* cur_Tcw, const float* pose_init,
+                              const float* last_Tcw, const PoseChain* pose, const lorb_frame_out* d_cur, int32_t n_max_cur,
+                              const lorb_frame_slots* d_cur_slots, int32_t cur_slots_given, const lorb_frame_out* d_last,
+                              int32_t n_max_last, const lorb_frame_slots* d_last_slots, const uint8_t* d_last_outlier,
+                              const lorb_track_motion_params* par, const lorb_lm_options* opt, int32_t* d_assign,
+                              lorb_track_frames_result* d_result) {
   if (n_max_cur < 1 || n_max_last < 1)
     return lorb::set_error(ctx, LORB_E_INVALID, "bounds %d / %d must be positive", n_max_last, n_max_cur);
   // a4's candidate list is allocated from the bounds: past this it would need the total read back
@@ -1537,8 +1625,14 @@ int lorb_track_motion_frames_dev(lorb_ctx* ctx, const lorb_frame_params* cur, co
   fr.cur = *d_cur_slots; fr.last = *d_last_slots; fr.given = cur_slots_given != 0;
   uint8_t* lk;
   LORB_TRY(lorb::scratch_t(ctx, slot<S_TF, 0>(), (size_t)n_max_last, &lk));
+  PoseChain pc{};
+  if (pose) {  // the fill reads the last frame's own count; the kernels behind it the copy in the block (-1: status 1)
+    pc = *pose;
+    LORB_TRY(lorb::scratch_t(ctx, slot<S_TP, 0>(), 1, &pc.blk));
+  }
   LORB_TRY(slots_fill_issue(ctx, cur, last_Tcw, d_last, n_max_last, LORB_SLOTS_UPDATE_FRAME, d_last_slots, lk, nullptr,
-                            &fr.dc, d_result));
+                            &fr.dc, d_result, pose ? &pc : nullptr));
+  if (pose) fr.dc.last = &pc.blk->n_last;
   KpDev K;
   K.x = d_cur->left.x; K.y = d_cur->left.y; K.angle = d_cur->left.angle; K.uR = d_cur->u_right;
   K.octave = d_cur->left.octave; K.desc = reinterpret_cast<const uint4*>(d_cur->left.desc);
@@ -1549,7 +1643,50 @@ int lorb_track_motion_frames_dev(lorb_ctx* ctx, const lorb_frame_params* cur, co
   const LastDev L = {n_max_last, d_last_slots->state, d_last_outlier, lk, d_last_slots->pos, d_last->left.angle,
                      d_last->left.octave, reinterpret_cast<const uint4*>(d_last_slots->desc)};
   return track_motion_issue(ctx, cur, cur_Tcw, pose_init, K, d_cur_slots->pos, L, last_Tcw, par, opt, d_assign,
-                            &d_result->motion, nullptr, &fr);
+                            &d_result->motion, nullptr, &fr, pc.blk);
+}
+
+int lorb_track_motion_frames_dev(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16],
+                                 const float pose_init[6], const lorb_frame_out* d_cur, int32_t n_max_cur,
+                                 const lorb_frame_slots* d_cur_slots, int32_t cur_slots_given,
+                                 const float last_Tcw[16], const lorb_frame_out* d_last, int32_t n_max_last,
+                                 const lorb_frame_slots* d_last_slots, const uint8_t* d_last_outlier,
+                                 const lorb_track_motion_params* par, const lorb_lm_options* opt,
+                                 int32_t* d_assign, lorb_track_frames_result* d_result) {
+  if (!ctx || !cur || !cur_Tcw || !pose_init || !d_cur || !d_cur_slots || !last_Tcw || !d_last || !d_last_slots || !par ||
+      !opt || !d_assign || !d_result)
+    return LORB_E_INVALID;
+  return track_frames_issue(ctx, cur, cur_Tcw, pose_init, last_Tcw, nullptr, d_cur, n_max_cur, d_cur_slots, cur_slots_given,
+                            d_last, n_max_last, d_last_slots, d_last_outlier, par, opt, d_assign, d_result);
+}
+
+// The same chain with the three poses in device memory (VisualOdometry::Run's hand-over between
+// frames): the first launch is k_slots_fill's POSE form -- status over the counts and the blocks, the
+// motion-model prediction on thread 0, the MotionPose block -- and the candidate kernels and the tail
+// are the forms that read that block.  The same number of launches as the host-pose call.
+int lorb_track_motion_frames_pose_dev(lorb_ctx* ctx, const lorb_frame_params* cur, lorb_frame_pose* d_cur_pose,
+                                      const lorb_frame_out* d_cur, int32_t n_max_cur,
+                                      const lorb_frame_slots* d_cur_slots, int32_t cur_slots_given,
+                                      const lorb_frame_pose* d_last_pose, const lorb_motion_model* d_model,
+                                      const lorb_frame_out* d_last, int32_t n_max_last,
+                                      const lorb_frame_slots* d_last_slots, const uint8_t* d_last_outlier,
+                                      const lorb_track_motion_params* par, const lorb_lm_options* opt,
+                                      int32_t* d_assign, lorb_track_frames_result* d_result) {
+  if (!ctx || !cur || !d_cur_pose || !d_cur || !d_cur_slots || !d_last_pose || !d_last || !d_last_slots || !par || !opt ||
+      !d_assign || !d_result)
+    return LORB_E_INVALID;
+  const PoseChain pose = {d_cur_pose, d_last_pose, d_model, nullptr};
+  return track_frames_issue(ctx, cur, nullptr, nullptr, nullptr, &pose, d_cur, n_max_cur, d_cur_slots, cur_slots_given,
+                            d_last, n_max_last, d_last_slots, d_last_outlier, par, opt, d_assign, d_result);
+}
+
+int lorb_frame_pose_finish_dev(lorb_ctx* ctx, const lorb_track_local_frames_result* d_local_result,
+                               const lorb_frame_pose* d_last_pose, lorb_frame_pose* d_cur_pose,
+                               lorb_motion_model* d_model) {
+  if (!ctx || !d_local_result || !d_last_pose || !d_cur_pose || !d_model) return LORB_E_INVALID;
+  hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(64), 0, ctx->stream, PoseFinish{d_local_result, d_last_pose, d_cur_pose, d_model});
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
 }
 
 int lorb_is_in_frustum(lorb_ctx* ctx, const lorb_frame_params* frame, const float Tcw[16],

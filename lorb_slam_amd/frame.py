@@ -409,6 +409,92 @@ def local_map_ids_back(ctx, lmap, cur, cur_slots, slot_id, slot_gid, n_max_cur=N
         C.c_void_p(d_local_status) if d_local_status else None, slot_gid.ptr), "lorb_local_map_ids_back_dev")
 
 
+def Tcw_to_pose(Tcw):
+    """lorb_Tcw_to_pose: (rvec, tvec) float32 of a 4 x 4 pose (cv::Rodrigues matrix -> vector; host)."""
+    T, r, t = A.f32(Tcw).reshape(16), np.zeros(3, np.float32), np.zeros(3, np.float32)
+    if lib().lorb_Tcw_to_pose(A.ptr(T, C.c_float), A.ptr(r, C.c_float), A.ptr(t, C.c_float)) != 0:
+        raise LorbError("lorb_Tcw_to_pose failed")
+    return r, t
+
+
+def frame_pose_from_Tcw(Tcw):
+    """lorb_frame_pose_from_Tcw: Frame::SetPose(Tcw) as an A.FramePose (host)."""
+    T, out = A.f32(Tcw).reshape(16), A.FramePose()
+    if lib().lorb_frame_pose_from_Tcw(A.ptr(T, C.c_float), C.byref(out)) != 0:
+        raise LorbError("lorb_frame_pose_from_Tcw failed")
+    return out
+
+
+class DeviceBlock:
+    """One ctypes struct in device memory (an A.FramePose or an A.MotionModel of the frame loop) with
+    ORB_GUARD bytes behind it.  value: the struct to upload; None leaves the whole buffer ORB_SENTINEL
+    bytes."""
+
+    def __init__(self, ctx, ctype, value=None):
+        self.ctx, self.ctype, self.size = ctx, ctype, C.sizeof(ctype)
+        h = np.full(self.size + ORB_GUARD, ORB_SENTINEL, np.uint8)
+        if value is not None:
+            h[:self.size] = np.frombuffer(bytes(value), np.uint8)
+        self.array = ctx.to_device(h)
+        self.ptr = self.array.ptr
+
+    def upload(self, value):
+        """lorb_memcpy_h2d of a struct (synchronous)."""
+        b = np.frombuffer(bytes(value), np.uint8).copy()
+        self.ctx.check(lib().lorb_memcpy_h2d(self.ctx.handle, self.ptr, b.ctypes.data_as(C.c_void_p), C.c_size_t(self.size)),
+                       "h2d")
+
+    def numpy(self):
+        """The whole guarded buffer as bytes (waits for the stream)."""
+        return self.array.numpy()
+
+    def read(self):
+        """The struct as it stands (waits for the stream)."""
+        return self.ctype.from_buffer_copy(self.numpy().tobytes()[:self.size])
+
+    def free(self):
+        self.array.free()
+
+
+def pose_block(ctx, Tcw=None):
+    """A device lorb_frame_pose: Frame::SetPose(Tcw), or sentinel bytes (a block the chain will write)."""
+    return DeviceBlock(ctx, A.FramePose, None if Tcw is None else frame_pose_from_Tcw(Tcw))
+
+
+def model_block(ctx, Tcc=None):
+    """A device lorb_motion_model: mTcc = Tcc with status 0, or sentinel bytes."""
+    if Tcc is None:
+        return DeviceBlock(ctx, A.MotionModel)
+    m = A.MotionModel()
+    m.Tcc[:] = [float(v) for v in A.f32(Tcc).reshape(16)]
+    return DeviceBlock(ctx, A.MotionModel, m)
+
+
+def enqueue_track_motion_frames_pose(ctx, fp, cur_pose, cur, cur_slots, last_pose, model, last, last_slots, assign, record,
+                                     n_max_cur=None, n_max_last=None, cur_slots_given=False, last_outlier=None,
+                                     th_first=15.0, th_retry=30.0, min_matches=20, fy_eff=None, opt=None):
+    """lorb_track_motion_frames_pose_dev enqueued and nothing else: enqueue_track_motion_frames with the
+    three poses in device memory.  cur_pose / last_pose: DeviceBlocks of A.FramePose; model: a DeviceBlock
+    of A.MotionModel (the prediction runs on the device and writes cur_pose) or None (cur_pose as given)."""
+    fps = A.make_frame_params(fp)
+    par = A.TrackMotionParams(th_first, th_retry, min_matches, fps.fx if fy_eff is None else fy_eff)
+    opt = opt or A.LMOptions.default()
+    nc = cur_slots.n_max if n_max_cur is None else int(n_max_cur)
+    nl = last_slots.n_max if n_max_last is None else int(n_max_last)
+    ctx.check(lib().lorb_track_motion_frames_pose_dev(
+        ctx.handle, C.byref(fps), cur_pose.ptr, C.byref(cur.out), C.c_int32(nc), C.byref(cur_slots.c),
+        C.c_int32(1 if cur_slots_given else 0), last_pose.ptr, model.ptr if model is not None else None, C.byref(last.out),
+        C.c_int32(nl), C.byref(last_slots.c), last_outlier.ptr if last_outlier else None, C.byref(par), C.byref(opt),
+        assign.ptr, record.ptr), "lorb_track_motion_frames_pose_dev")
+
+
+def frame_pose_finish(ctx, local_record, last_pose, cur_pose, model):
+    """lorb_frame_pose_finish_dev (enqueued and nothing else): the frame's pose block and mTcc from the
+    local stage's record.  local_record: the DeviceArray holding the A.TrackLocalFramesResult."""
+    ctx.check(lib().lorb_frame_pose_finish_dev(ctx.handle, local_record.ptr, last_pose.ptr, cur_pose.ptr, model.ptr),
+              "lorb_frame_pose_finish_dev")
+
+
 class FrameBuilder:
     """lorb_frame_builder of one geometry.  fp: frame-params dict (n_levels, scale_factors, bf, b are
     read); n_desired: features per level (n_levels entries); pattern: the 256 test pairs (1024 ints)."""

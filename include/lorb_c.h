@@ -951,6 +951,64 @@ int lorb_track_motion_frames_pose_dev(lorb_ctx* ctx, const lorb_frame_params* cu
                                       const lorb_track_motion_params* par, const lorb_lm_options* opt,
                                       int32_t* d_assign, lorb_track_frames_result* d_result);
 
+/* The second motion attempt of VisualOdometry::Run, on the reference keyframe, decided on the device
+ * (src/visual_odometry.cpp:50-54,117-138):
+ *     bool tag = EstimatePoseMotion(mPrevFrame);  if(tag == false) tag = EstimatePoseMotion(mReferFrame);
+ * Enqueued directly behind lorb_track_motion_frames_pose_dev with that call's d_assign, d_result,
+ * d_cur_pose, d_cur_slots and d_model (required here); the refer objects are the frame the caller
+ * believes is mReferFrame.  Two optional groups, each given whole or not at all:
+ *   gids   d_last_slot_gid (n_max_last), d_refer_slot_gid (n_max_refer), d_cur_slot_gid (n_max_cur, read
+ *          and written): the global point index each slot holds.  NULL: no id bookkeeping.
+ *   guard  d_refer_kf (one device int32, read and written: the keyframe index of mReferFrame, initialised
+ *          once by the caller) and d_prev_update (the PREVIOUS frame's lorb_local_map_update_dev record);
+ *          refer_kf is the index of the frame passed as d_refer.  NULL: no guard.
+ * On the device, in the chain's first launch and before anything else, in this order:
+ *   a. The first attempt's record has status != 0: due = ran = stale = 0 (and both figures 0) is stored in
+ *      d_refer_result and NOTHING else is written; the record keeps its status 1.
+ *   b. The reference-frame word (:311-312): d_prev_update->status == 0 with refer_kf >= 0 stores that
+ *      index in *d_refer_kf -- the previous frame's UpdateLocalMap is the last thing that can have moved
+ *      mReferFrame.  Enqueued every frame, the word follows mReferFrame exactly.
+ *   c. Entry ids (gids given): d_cur_slot_gid[j], j < n_cur, from the first attempt's codes by exactly the
+ *      rule of lorb_track_local_id_source, with d_last_slot_gid and first_slots_given (cur_slots_given as
+ *      passed to the first attempt); an index outside its table counts as -1.  Always done, due or not:
+ *      behind this call lorb_local_map_update_dev is given ids = NULL.
+ *   d. due = (motion.pass == 0); stale = due and the guard is given and *d_refer_kf != refer_kf.  Not due,
+ *      or stale: d_refer_result is stored and NOTHING else is written -- d_assign, d_result, both slot
+ *      sets, d_cur_pose, d_model and the refer frame's slots stay as they are, every later kernel of the
+ *      call returns at once, and the refer frame's count, pose status and bounds are not examined.
+ *   e. Due and not stale (ran = 1): the stage is exactly lorb_track_motion_frames_pose_dev with the refer
+ *      objects as d_last*, d_model given and cur_slots_given = 1 -- both a4 passes start from the slots the
+ *      failed first attempt left (:128-131 leaves its <= 20 matches in mvpMapPoints) -- into the same
+ *      d_assign and d_result: the status (the refer count, d_refer_pose->status; status 1 in the record
+ *      and in d_cur_pose and nothing else), the prediction d_cur_pose = SetPose(refer.Tcw * Tcc), the
+ *      UPDATE_FRAME fill of d_refer_slots with refer.Twc, the tail and its slot write-back.
+ *      first_nmatches_first / _retry keep the first attempt's figures.  With gids given the tail applies
+ *      the final codes to d_cur_slot_gid: c >= 0 -> d_refer_slot_gid[c] (outside the table: -1);
+ *      LORB_ASSIGN_NULL -> -1; LORB_ASSIGN_UNCHANGED -> the id step c left when pass 1 stood, else -1.
+ * A stale reference frame is reported, not followed: the caller sees stale = 1 and a
+ * record with pass 0.  Downstream nothing changes: &d_result->status, &d_result->motion.pose[0] and
+ * lorb_frame_pose_finish_dev (mTcc is still formed against the previous frame's block, :65) as before.
+ * LORB_E_INVALID as lorb_track_motion_frames_pose_dev (bounds n_max_refer and n_max_cur), and for a null
+ * d_model or d_refer_result, a partially given gid group (or n_max_last < 1 with it) and a partially
+ * given guard pair.  Asynchronous on the ctx stream: the launches of lorb_track_motion_frames_pose_dev
+ * for the same bounds and no more, no stream synchronise, no copy. */
+typedef struct lorb_track_refer_result {
+  int32_t due;    /* 1: the first attempt's record had status 0 and motion.pass == 0 */
+  int32_t ran;    /* 1: the second attempt ran (due, and not stale) */
+  int32_t stale;  /* 1: due, but *d_refer_kf != refer_kf: not run */
+  int32_t first_nmatches_first, first_nmatches_retry;  /* the first attempt's (0 under a), kept for the caller when ran */
+} lorb_track_refer_result;
+int lorb_track_motion_refer_pose_dev(lorb_ctx* ctx, const lorb_frame_params* cur, lorb_frame_pose* d_cur_pose,
+                                     const lorb_frame_out* d_cur, int32_t n_max_cur, const lorb_frame_slots* d_cur_slots,
+                                     int32_t first_slots_given, const lorb_frame_pose* d_refer_pose,
+                                     const lorb_motion_model* d_model, const lorb_frame_out* d_refer, int32_t n_max_refer,
+                                     const lorb_frame_slots* d_refer_slots, const uint8_t* d_refer_outlier,
+                                     const int32_t* d_last_slot_gid, int32_t n_max_last, const int32_t* d_refer_slot_gid,
+                                     int32_t* d_cur_slot_gid, int32_t refer_kf, int32_t* d_refer_kf,
+                                     const lorb_local_map_result* d_prev_update, const lorb_track_motion_params* par,
+                                     const lorb_lm_options* opt, int32_t* d_assign, lorb_track_frames_result* d_result,
+                                     lorb_track_refer_result* d_refer_result);
+
 /* After the local stage (:65-66), one launch.  d_local_result->status == 0: cur.Tcw = the record's Tcw,
  * cur.pose = (float) of local.pose when local.ok, else pose_in; cur.Twc = cv::Mat::inv() of cur.Tcw;
  * cur.status = 0; model.Tcc = last.Twc * cur.Tcw (the gemm convention above), model.status = 0.  A

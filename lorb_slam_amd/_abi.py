@@ -250,6 +250,11 @@ class MotionModel(C.Structure):  # lorb_motion_model
     _fields_ = [("Tcc", C.c_float * 16), ("status", C.c_int32)]
 
 
+class TrackReferResult(C.Structure):  # lorb_track_refer_result
+    _fields_ = [("due", C.c_int32), ("ran", C.c_int32), ("stale", C.c_int32), ("first_nmatches_first", C.c_int32),
+                ("first_nmatches_retry", C.c_int32)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

@@ -1474,8 +1474,11 @@ __global__ __launch_bounds__(kPoThreads) void k_track_tail(lorb::TrackTail a, LM
 // emptied slots, src/visual_odometry.cpp:128; slots not given are all EMPTY whatever the array holds).
 // The apply runs after the LM: the solve has read slot_pos (the kept slots' points) by then, and the
 // few dozen bytes per slot are not worth a launch of their own.
-// (the body, shared with k_track_frames_tail_pose)
-__device__ __forceinline__ void track_frames_tail_run(lorb::TrackTail& a, const lorb::FramesTail& f, const LMOpt& o) {
+// (the body, shared with k_track_frames_tail_pose and k_track_frames_tail_refer; kGids: the latter's,
+// which writes each slot's id beside the slot)
+template <bool kGids = false>
+__device__ __forceinline__ void track_frames_tail_run(lorb::TrackTail& a, const lorb::FramesTail& f, const LMOpt& o,
+                                                      const lorb::ReferGids* g = nullptr) {
   int n_last;
   if (!lorb::frame_counts(f.dc, &n_last, &a.nk)) return;
   const bool retry = track_tail_run(a, o);
@@ -1494,6 +1497,9 @@ __device__ __forceinline__ void track_frames_tail_run(lorb::TrackTail& a, const 
     } else if (c == LORB_ASSIGN_NULL || !keep) {
       f.cur.state[j] = LORB_SLOT_EMPTY;
     }
+    if constexpr (kGids) {
+      if (g->cur_gid) g->cur_gid[j] = lorb::motion_entry_id(g->cur_gid[j], c, keep, g->refer_gid, g->n_max_refer);
+    }
   }
 }
 __global__ __launch_bounds__(kPoThreads) void k_track_frames_tail(lorb::TrackTail a, lorb::FramesTail f, LMOpt o) {
@@ -1506,6 +1512,17 @@ __global__ __launch_bounds__(kPoThreads) void k_track_frames_tail_pose(lorb::Tra
 #pragma unroll
   for (int k = 0; k < 6; ++k) a.pose_init[k] = pose->pose_init[k];
   track_frames_tail_run(a, f, o);
+}
+// The tail of lorb_track_motion_refer_pose_dev (the "last" frame is the refer frame): the same, and the
+// codes that count applied to the slots' ids as they are to the slots -- motion_entry_id with the refer
+// frame's ids as the source, an UNCHANGED slot keeping the id the call's first kernel left when pass 1
+// stood.  A skipped attempt returns with the body (n_last = -1) and writes no id.
+__global__ __launch_bounds__(kPoThreads) void k_track_frames_tail_refer(lorb::TrackTail a, lorb::FramesTail f,
+                                                                        const lorb::MotionPose* __restrict__ pose,
+                                                                        lorb::ReferGids g, LMOpt o) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) a.pose_init[k] = pose->pose_init[k];
+  track_frames_tail_run<true>(a, f, o, &g);
 }
 
 // The tail of the local-map tracking chain (VisualOdometry::EstimatePoseLocal after its matcher
@@ -1988,6 +2005,12 @@ int launch_track_frames_tail(lorb_ctx* ctx, const TrackTail& t, const FramesTail
 int launch_track_frames_tail_pose(lorb_ctx* ctx, const TrackTail& t, const FramesTail& f, const MotionPose* pose,
                                   const lorb_lm_options* opt) {
   hipLaunchKernelGGL(k_track_frames_tail_pose, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, f, pose, to_dev_opt(opt));
+  LORB_CHECK_LAUNCH(ctx);
+  return LORB_OK;
+}
+int launch_track_frames_tail_refer(lorb_ctx* ctx, const TrackTail& t, const FramesTail& f, const MotionPose* pose,
+                                   const ReferGids& g, const lorb_lm_options* opt) {
+  hipLaunchKernelGGL(k_track_frames_tail_refer, dim3(1), dim3(kPoThreads), 0, ctx->stream, t, f, pose, g, to_dev_opt(opt));
   LORB_CHECK_LAUNCH(ctx);
   return LORB_OK;
 }

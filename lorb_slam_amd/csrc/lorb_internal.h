@@ -603,6 +603,29 @@ struct MotionPose {
 int launch_track_frames_tail_pose(lorb_ctx* ctx, const TrackTail& t, const FramesTail& f, const MotionPose* pose,
                                   const lorb_lm_options* opt);
 
+// The id a current-frame slot holds after a motion stage, from that stage's final code for the slot:
+// the rule of lorb_track_local_id_source, which is the rule the stage's tail applied to the slot itself.
+// code >= 0: the id of source slot `code` (an index outside the table counts as -1); LORB_ASSIGN_NULL:
+// -1; LORB_ASSIGN_UNCHANGED: the id the slot had (`id`) when `keep` -- pass 1 stood and the slots were
+// given -- else -1.  One definition for k_local_head, k_lm_vote and both kernels of
+// lorb_track_motion_refer_pose_dev.
+__device__ __forceinline__ int motion_entry_id(int id, int code, bool keep, const int* src_id, int n_max_src) {
+  if (code >= 0) return code < n_max_src ? src_id[code] : -1;
+  if (code == LORB_ASSIGN_NULL || !keep) return -1;
+  return id;
+}
+
+// The second motion attempt (lorb_track_motion_refer_pose_dev): what its tail has beyond
+// k_track_frames_tail_pose -- the final codes applied to the current frame's slot ids with the refer
+// frame's ids as the source.  cur_gid null: no id bookkeeping.
+struct ReferGids {
+  const int* refer_gid;
+  int n_max_refer;
+  int* cur_gid;
+};
+int launch_track_frames_tail_refer(lorb_ctx* ctx, const TrackTail& t, const FramesTail& f, const MotionPose* pose,
+                                   const ReferGids& g, const lorb_lm_options* opt);
+
 // The tail of the local-map tracking chain (lorb_track_local*, lorb_window.hip): one launch of
 // k_local_tail (lorb_ba.hip) after a8 + a5 -- the in-view count, the nmatches > min_matches gate,
 // residual compaction, pose-only LM, result record.  All pointers are device pointers.

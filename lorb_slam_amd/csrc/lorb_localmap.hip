@@ -104,11 +104,7 @@ __global__ __launch_bounds__(1024) void k_lm_vote(VoteArgs a) {
   lorb::I4 c = {{0, 0, 0, 0}};
   for (int j = t; j < n; j += 1024) {
     int g = a.gid[j];
-    if (a.motion_assign) {
-      const int code = a.motion_assign[j];
-      if (code >= 0) g = code < a.n_max_last ? a.last_gid[code] : -1;
-      else if (code == LORB_ASSIGN_NULL || !keep) g = -1;
-    }
+    if (a.motion_assign) g = lorb::motion_entry_id(g, a.motion_assign[j], keep, a.last_gid, a.n_max_last);
     if ((unsigned)g >= (unsigned)a.n_points) g = -1;  // a point outside the store
     if (a.state[j] != LORB_SLOT_EMPTY) {
       if (g >= 0 && a.pt_bad && a.pt_bad[g]) {

@@ -928,13 +928,65 @@ struct SlotFill {
   uint8_t* locked;  // or null
   int* n_created;   // or null
 };
-template <int MODE, bool CHAIN, bool POSE = false>
+// REFER (the second motion attempt, lorb_track_motion_refer_pose_dev: src/visual_odometry.cpp:50-54): the
+// POSE form on the refer frame behind a head that decides, from the first attempt's record in device
+// memory, whether the attempt runs at all.  In this order: (a) a first attempt with status != 0 zeroes
+// the refer record and ends the call; (b) the reference-frame word follows the previous frame's
+// UpdateLocalMap (:311-312); (c) the current slots' ids by the first attempt's codes (motion_entry_id);
+// (d) due = the first attempt's pass == 0, stale = due and the word is not the caller's refer frame.
+// Not due, or stale, ends the call: n_last = -1 in the MotionPose block, on which every kernel behind
+// this one returns, and nothing of the refer frame is examined.  Every thread reads the first attempt's
+// record before the barrier; thread 0 overwrites its status only behind it.
+struct ReferHead {
+  const int* assign;  // the first attempt's final codes
+  int first_given;    // cur_slots_given of the first attempt
+  const int* last_gid;  // the gid group (cur_gid null: none)
+  int n_max_last;
+  int* cur_gid;
+  int refer_kf;  // the guard pair (kf_word null: none)
+  int* kf_word;
+  const lorb_local_map_result* prev_update;
+  lorb_track_refer_result* out;
+};
+template <int MODE, bool CHAIN, bool POSE = false, bool REFER = false>
 __global__ __launch_bounds__(1024) void k_slots_fill(SlotFill a, lorb::FrameCounts dc,
-                                                     lorb_track_frames_result* __restrict__ rec, PoseChain pc = {}) {
+                                                     lorb_track_frames_result* __restrict__ rec, PoseChain pc = {},
+                                                     ReferHead rh = {}) {
   __shared__ int wsum[16];
   const int t = threadIdx.x;
   int n, n_cur = 0;
   lorb::Mat4f twc_blk;  // POSE only
+  if constexpr (REFER) {
+    static_assert(POSE, "the second attempt is a form of the device-pose chain");
+    const bool first_ok = rec->status == 0;
+    const int first_pass = rec->motion.pass, nm_first = rec->motion.nmatches_first, nm_retry = rec->motion.nmatches_retry;
+    int kf = 0;
+    if (rh.kf_word) {
+      kf = *rh.kf_word;
+      if (rh.prev_update->status == 0 && rh.prev_update->refer_kf >= 0) kf = rh.prev_update->refer_kf;
+    }
+    __syncthreads();
+    if (!first_ok) {  // a
+      if (t == 0) {
+        *rh.out = lorb_track_refer_result{0, 0, 0, 0, 0};
+        pc.blk->n_last = -1;
+      }
+      return;
+    }
+    if (t == 0 && rh.kf_word) *rh.kf_word = kf;  // b
+    if (rh.cur_gid) {                            // c
+      const int nc = min(dc.cur[0], dc.max_cur);
+      const bool keep = rh.first_given && first_pass == 1;
+      for (int j = t; j < nc; j += 1024)
+        rh.cur_gid[j] = lorb::motion_entry_id(rh.cur_gid[j], rh.assign[j], keep, rh.last_gid, rh.n_max_last);
+    }
+    const bool due = first_pass == 0, stale = due && rh.kf_word && kf != rh.refer_kf;  // d
+    if (t == 0) *rh.out = lorb_track_refer_result{due, due && !stale, stale, nm_first, nm_retry};
+    if (!due || stale) {
+      if (t == 0) pc.blk->n_last = -1;
+      return;
+    }
+  }
   if constexpr (POSE) {
     static_assert(CHAIN, "the device-pose form is a form of the chain");
     const bool ok = lorb::frame_counts(dc, &n, &n_cur) && pc.last->status == 0 && !(pc.model && pc.model->status != 0);
@@ -1078,11 +1130,7 @@ __global__ __launch_bounds__(1024) void k_local_head(LocalHead a) {
   int held = 0;
   for (int j = t; j < n; j += 1024) {
     int id = a.slot_id[j];
-    if (a.motion_assign) {
-      const int c = a.motion_assign[j];
-      if (c >= 0) id = c < a.n_max_last ? a.last_slot_id[c] : -1;
-      else if (c == LORB_ASSIGN_NULL || !keep) id = -1;
-    }
+    if (a.motion_assign) id = lorb::motion_entry_id(id, a.motion_assign[j], keep, a.last_slot_id, a.n_max_last);
     if ((unsigned)id >= (unsigned)a.np) id = -1;  // a point outside the table
     const uint8_t st = a.state[j];
     if (st != LORB_SLOT_EMPTY) {
@@ -1455,13 +1503,14 @@ int lorb_search_by_projection_frame_dev(lorb_ctx* ctx, const lorb_frame_params* 
 // fr (lorb_track_motion_frames_dev): K.n and L.n are the caller's bounds (both >= 1), every kernel
 // reads the counts of fr->dc, and the tail is k_track_frames_tail, which also applies the codes to
 // the current frame's slots.  mp (with fr: lorb_track_motion_frames_pose_dev): cur_Tcw, pose_init and
-// last_Tcw are null, the candidate kernels and the tail read the MotionPose block *mp instead.
+// last_Tcw are null, the candidate kernels and the tail read the MotionPose block *mp instead.  rg (with
+// mp: lorb_track_motion_refer_pose_dev): the tail is the form that also writes the slots' ids.
 static int track_motion_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const float* cur_Tcw,
                               const float* pose_init, KpDev K, const float* slot_pos, const LastDev& L,
                               const float* last_Tcw, const lorb_track_motion_params* par,
                               const lorb_lm_options* opt, int* d_assign, lorb_track_motion_result* rec,
                               int* assign_out, const lorb::FramesTail* fr = nullptr,
-                              const lorb::MotionPose* mp = nullptr) {
+                              const lorb::MotionPose* mp = nullptr, const lorb::ReferGids* rg = nullptr) {
   const int nk = K.n;
   const lorb::FrameCounts* dc = fr ? &fr->dc : nullptr;
   int* tm;  // pass 2's codes (nk) | its count | pass 1's count
@@ -1489,6 +1538,7 @@ static int track_motion_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const
   t.fx = cur->fx; t.fy_eff = par->fy_eff; t.cx = cur->cx; t.cy = cur->cy;
   if (pose_init) memcpy(t.pose_init, pose_init, sizeof(t.pose_init));
   t.list = list; t.rec = rec; t.assign_out = assign_out;
+  if (fr && mp && rg) return lorb::launch_track_frames_tail_refer(ctx, t, *fr, mp, *rg, opt);
   if (fr && mp) return lorb::launch_track_frames_tail_pose(ctx, t, *fr, mp, opt);
   if (fr) return lorb::launch_track_frames_tail(ctx, t, *fr, opt);
   return lorb::launch_track_tail(ctx, t, opt);
@@ -1555,7 +1605,8 @@ int lorb_track_motion(lorb_ctx* ctx, const lorb_frame_params* cur, const float c
 // device-pose form, Tcw null)
 static int slots_fill_issue(lorb_ctx* ctx, const lorb_frame_params* frame, const float* Tcw, const lorb_frame_out* f,
                             int n_max, int mode, const lorb_frame_slots* s, uint8_t* locked, int* n_created,
-                            const lorb::FrameCounts* dc, lorb_track_frames_result* rec, const PoseChain* pc = nullptr) {
+                            const lorb::FrameCounts* dc, lorb_track_frames_result* rec, const PoseChain* pc = nullptr,
+                            const ReferHead* rh = nullptr) {  // rh (with pc): the second attempt's head
   SlotFill a{};
   a.fp = *frame;
   if (Tcw) {
@@ -1567,7 +1618,10 @@ static int slots_fill_issue(lorb_ctx* ctx, const lorb_frame_params* frame, const
   a.x = f->left.x; a.y = f->left.y; a.depth = f->depth; a.desc = reinterpret_cast<const uint4*>(f->left.desc);
   a.state = s->state; a.pos = s->pos; a.sdesc = reinterpret_cast<uint4*>(s->desc);
   a.locked = locked; a.n_created = n_created;
-  if (dc && pc)
+  if (dc && pc && rh)
+    hipLaunchKernelGGL((k_slots_fill<LORB_SLOTS_UPDATE_FRAME, true, true, true>), dim3(1), dim3(1024), 0, ctx->stream, a, *dc,
+                       rec, *pc, *rh);
+  else if (dc && pc)
     hipLaunchKernelGGL((k_slots_fill<LORB_SLOTS_UPDATE_FRAME, true, true>), dim3(1), dim3(1024), 0, ctx->stream, a, *dc, rec,
                        *pc);
   else if (dc)
@@ -1601,13 +1655,15 @@ int lorb_frame_slots_fill_dev(lorb_ctx* ctx, const lorb_frame_params* frame, con
 // built frames whose counts stay in device memory: the UpdateFrame fill of the last frame's slots
 // (which also checks the counts and writes the record's status), the motion chain in its device-count
 // form over the caller's bounds, and the tail that applies the codes to the current frame's slots.
-// (both forms: the host poses, or pose -- cur, last and model of the device-pose form, blk unset)
+// (both forms: the host poses, or pose -- cur, last and model of the device-pose form, blk unset; rh and
+// rg with pose: the second attempt, whose "last" objects are the refer frame's)
 static int track_frames_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const float* cur_Tcw, const float* pose_init,
                               const float* last_Tcw, const PoseChain* pose, const lorb_frame_out* d_cur, int32_t n_max_cur,
                               const lorb_frame_slots* d_cur_slots, int32_t cur_slots_given, const lorb_frame_out* d_last,
                               int32_t n_max_last, const lorb_frame_slots* d_last_slots, const uint8_t* d_last_outlier,
                               const lorb_track_motion_params* par, const lorb_lm_options* opt, int32_t* d_assign,
-                              lorb_track_frames_result* d_result) {
+                              lorb_track_frames_result* d_result, const ReferHead* rh = nullptr,
+                              const lorb::ReferGids* rg = nullptr) {
   if (n_max_cur < 1 || n_max_last < 1)
     return lorb::set_error(ctx, LORB_E_INVALID, "bounds %d / %d must be positive", n_max_last, n_max_cur);
   // a4's candidate list is allocated from the bounds: past this it would need the total read back
@@ -1631,7 +1687,7 @@ static int track_frames_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const
     LORB_TRY(lorb::scratch_t(ctx, slot<S_TP, 0>(), 1, &pc.blk));
   }
   LORB_TRY(slots_fill_issue(ctx, cur, last_Tcw, d_last, n_max_last, LORB_SLOTS_UPDATE_FRAME, d_last_slots, lk, nullptr,
-                            &fr.dc, d_result, pose ? &pc : nullptr));
+                            &fr.dc, d_result, pose ? &pc : nullptr, rh));
   if (pose) fr.dc.last = &pc.blk->n_last;
   KpDev K;
   K.x = d_cur->left.x; K.y = d_cur->left.y; K.angle = d_cur->left.angle; K.uR = d_cur->u_right;
@@ -1643,7 +1699,7 @@ static int track_frames_issue(lorb_ctx* ctx, const lorb_frame_params* cur, const
   const LastDev L = {n_max_last, d_last_slots->state, d_last_outlier, lk, d_last_slots->pos, d_last->left.angle,
                      d_last->left.octave, reinterpret_cast<const uint4*>(d_last_slots->desc)};
   return track_motion_issue(ctx, cur, cur_Tcw, pose_init, K, d_cur_slots->pos, L, last_Tcw, par, opt, d_assign,
-                            &d_result->motion, nullptr, &fr, pc.blk);
+                            &d_result->motion, nullptr, &fr, pc.blk, rg);
 }
 
 int lorb_track_motion_frames_dev(lorb_ctx* ctx, const lorb_frame_params* cur, const float cur_Tcw[16],
@@ -1678,6 +1734,38 @@ int lorb_track_motion_frames_pose_dev(lorb_ctx* ctx, const lorb_frame_params* cu
   const PoseChain pose = {d_cur_pose, d_last_pose, d_model, nullptr};
   return track_frames_issue(ctx, cur, nullptr, nullptr, nullptr, &pose, d_cur, n_max_cur, d_cur_slots, cur_slots_given,
                             d_last, n_max_last, d_last_slots, d_last_outlier, par, opt, d_assign, d_result);
+}
+
+// VisualOdometry::Run :50-54, the second attempt on the reference keyframe, decided on the device: the
+// device-pose chain with the refer frame's objects as the last frame's, the current slots given, and
+// k_slots_fill's REFER form in front, which ends the call -- every later kernel returns at once -- unless
+// the first attempt's record says pass 0 and the reference-frame word is the caller's refer frame.  The
+// tail is the form that also applies the final codes to the slots' global ids.  The same launches as
+// lorb_track_motion_frames_pose_dev for the same bounds.
+int lorb_track_motion_refer_pose_dev(lorb_ctx* ctx, const lorb_frame_params* cur, lorb_frame_pose* d_cur_pose,
+                                     const lorb_frame_out* d_cur, int32_t n_max_cur, const lorb_frame_slots* d_cur_slots,
+                                     int32_t first_slots_given, const lorb_frame_pose* d_refer_pose,
+                                     const lorb_motion_model* d_model, const lorb_frame_out* d_refer, int32_t n_max_refer,
+                                     const lorb_frame_slots* d_refer_slots, const uint8_t* d_refer_outlier,
+                                     const int32_t* d_last_slot_gid, int32_t n_max_last, const int32_t* d_refer_slot_gid,
+                                     int32_t* d_cur_slot_gid, int32_t refer_kf, int32_t* d_refer_kf,
+                                     const lorb_local_map_result* d_prev_update, const lorb_track_motion_params* par,
+                                     const lorb_lm_options* opt, int32_t* d_assign, lorb_track_frames_result* d_result,
+                                     lorb_track_refer_result* d_refer_result) {
+  if (!ctx || !cur || !d_cur_pose || !d_cur || !d_cur_slots || !d_refer_pose || !d_model || !d_refer || !d_refer_slots ||
+      !par || !opt || !d_assign || !d_result || !d_refer_result)
+    return LORB_E_INVALID;
+  // the two optional groups are given whole or not at all (checked before the context is touched)
+  const int n_gid = (d_last_slot_gid != nullptr) + (d_refer_slot_gid != nullptr) + (d_cur_slot_gid != nullptr);
+  if (n_gid != 0 && n_gid != 3) return LORB_E_INVALID;
+  if ((d_refer_kf != nullptr) != (d_prev_update != nullptr)) return LORB_E_INVALID;
+  if (n_gid && n_max_last < 1) return lorb::set_error(ctx, LORB_E_INVALID, "bound %d must be positive", n_max_last);
+  const PoseChain pose = {d_cur_pose, d_refer_pose, d_model, nullptr};
+  const ReferHead rh = {d_assign, first_slots_given != 0, d_last_slot_gid, n_max_last,    d_cur_slot_gid,
+                        refer_kf, d_refer_kf,             d_prev_update,   d_refer_result};
+  const lorb::ReferGids rg = {d_refer_slot_gid, n_max_refer, d_cur_slot_gid};
+  return track_frames_issue(ctx, cur, nullptr, nullptr, nullptr, &pose, d_cur, n_max_cur, d_cur_slots, 1, d_refer,
+                            n_max_refer, d_refer_slots, d_refer_outlier, par, opt, d_assign, d_result, &rh, &rg);
 }
 
 int lorb_frame_pose_finish_dev(lorb_ctx* ctx, const lorb_track_local_frames_result* d_local_result,

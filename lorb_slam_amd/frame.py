@@ -488,6 +488,37 @@ def enqueue_track_motion_frames_pose(ctx, fp, cur_pose, cur, cur_slots, last_pos
         assign.ptr, record.ptr), "lorb_track_motion_frames_pose_dev")
 
 
+def refer_kf_word(ctx, refer_kf):
+    """The one-word device buffer behind d_refer_kf: a DeviceBlock of one int32 holding the keyframe index
+    of mReferFrame, which the caller initialises once and lorb_track_motion_refer_pose_dev keeps current."""
+    return DeviceBlock(ctx, C.c_int32, C.c_int32(int(refer_kf)))
+
+
+def enqueue_track_motion_refer_pose(ctx, fp, cur_pose, cur, cur_slots, refer_pose, model, refer, refer_slots, assign, record,
+                                    refer_record, first_slots_given=False, n_max_cur=None, n_max_refer=None,
+                                    refer_outlier=None, last_gid=None, n_max_last=None, refer_gid=None, cur_gid=None,
+                                    refer_kf=-1, kf_word=None, prev_update=None, th_first=15.0, th_retry=30.0, min_matches=20,
+                                    fy_eff=None, opt=None):
+    """lorb_track_motion_refer_pose_dev enqueued and nothing else: the second motion attempt on the refer
+    frame, decided on the device, directly behind enqueue_track_motion_frames_pose with that call's
+    cur_pose, cur_slots, model, assign and record.  refer_record: a DeviceBlock of A.TrackReferResult.
+    last_gid / refer_gid / cur_gid: DeviceArrays of int32 (all three or none); kf_word (refer_kf_word) /
+    prev_update (the previous frame's local-map record, a DeviceArray): both or none."""
+    fps = A.make_frame_params(fp)
+    par = A.TrackMotionParams(th_first, th_retry, min_matches, fps.fx if fy_eff is None else fy_eff)
+    opt = opt or A.LMOptions.default()
+    nc = cur_slots.n_max if n_max_cur is None else int(n_max_cur)
+    nr = refer_slots.n_max if n_max_refer is None else int(n_max_refer)
+    nl = nr if n_max_last is None else int(n_max_last)
+    p = lambda h: h.ptr if h is not None else None  # noqa: E731
+    ctx.check(lib().lorb_track_motion_refer_pose_dev(
+        ctx.handle, C.byref(fps), cur_pose.ptr, C.byref(cur.out), C.c_int32(nc), C.byref(cur_slots.c),
+        C.c_int32(1 if first_slots_given else 0), refer_pose.ptr, p(model), C.byref(refer.out), C.c_int32(nr),
+        C.byref(refer_slots.c), p(refer_outlier), p(last_gid), C.c_int32(nl), p(refer_gid), p(cur_gid), C.c_int32(int(refer_kf)),
+        p(kf_word), p(prev_update), C.byref(par), C.byref(opt), assign.ptr, record.ptr, refer_record.ptr),
+        "lorb_track_motion_refer_pose_dev")
+
+
 def frame_pose_finish(ctx, local_record, last_pose, cur_pose, model):
     """lorb_frame_pose_finish_dev (enqueued and nothing else): the frame's pose block and mTcc from the
     local stage's record.  local_record: the DeviceArray holding the A.TrackLocalFramesResult."""

@@ -1783,8 +1783,9 @@ int plan_solve(lorb_ba_plan* P, const lorb_lm_options* opt) {
   P->fold = fold_of(P);
   // per-kernel events cannot live inside a graph, and neither can a host-transport exchange
   const bool timing = ctx->ktime || no_graph() || (P->comm && !P->comm->rccl);
-  if (timing) return enqueue_solve(P, o);
   const lorb_ba_plan::GraphKey key = graph_key(P);
+  P->skey = key;
+  if (timing) return enqueue_solve(P, o);
   const bool same = key == P->gkey && same_opt(P->graph_opt, o);
   return P->cache.replay_or_capture(ctx, same, [&] { return enqueue_solve(P, o); },
                                     [&] { P->gkey = key; P->graph_opt = o; });
@@ -1826,6 +1827,17 @@ int plan_read(lorb_ba_plan* P, double* const* pose_out, double* const* point_out
 }
 
 }  // namespace
+
+namespace lorb {
+// plan_solve's host-side choices on the plan's fields as they are now against the last solve's
+bool ba_plan_solve_key_same(lorb_ba_plan* P) {
+  const bool fold_was = P->fold;
+  P->fold = fold_of(P);
+  const bool same = graph_key(P) == P->skey;
+  P->fold = fold_was;
+  return same;
+}
+}  // namespace lorb
 
 // A plan group (lorb_ba_group_*): member plans (not owned) on one context, solved by one set of
 // launches (k_ba_*_g) captured in one graph.  The graph holds the members' BaDev and launch shapes:

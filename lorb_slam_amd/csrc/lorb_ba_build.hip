@@ -36,15 +36,27 @@ struct lorb_ba_devbuild {
   bool dirty = true;  // the build scratch needs a clearing fill (first build, or after a failed one)
   bool sorted_hint = false;  // the caller's slots are sorted by point: try k_db_sorted first
   std::vector<double> h_red;                     // sharded: the build's host all-reduce
-  // per-build structure uploaded in one copy: [BaWin | live (2) | perm (C) | gcam (C) | bp (up_bp_cap)]
+  // per-build structure uploaded in one copy: [BaWin | live (3) | perm (C) | gcam (C) | adj (C * C bytes) |
+  // bp (up_bp_cap)]
   unsigned char* up_dev = nullptr; unsigned char* up_host = nullptr; int up_bp_cap = 0;
   const unsigned char* up_host_dev = nullptr;  // up_host as the device reads it (pinned, mapped)
-  size_t off_live = 0, off_perm = 0, off_gcam = 0, off_bp = 0, up_bytes = 0;
+  size_t off_live = 0, off_perm = 0, off_gcam = 0, off_adj = 0, off_bp = 0, up_bytes = 0;
+  // Speculation on the plan's structure (dev_spec_issue / dev_spec_verify): a completed build keeps
+  // what its host phase derived from the adjacency pattern -- last_adj and last_map (below), the
+  // (ch, cl) block list (last_bps), the band (hwin[0].bw) and the groups per partial run (spec_sf) --
+  // and the upload block keeps the parts that do not depend on counts (perm, the block list's
+  // (ch, cl), BaWin's band and layout constants, the adjacency as bytes).  spec_ok: all of that
+  // describes the plan as the device holds it.  spec_pending: a speculative gather is queued and
+  // not yet verified.  spec_out: the words k_db_spec leaves for k_db_gather<true> (see DbSpec).
+  bool spec_ok = false, spec_pending = false;
+  int spec_sf = 1;
+  int* spec_out = nullptr;
   // camera_order is a function of the adjacency pattern alone: a build whose pattern equals the
   // previous one's (a sliding window usually keeps its banded pattern) reuses that order
   std::vector<char> last_adj;
   std::vector<int> h_copy;  // host copy of the build's readback
   std::vector<int> last_map;
+  std::vector<lorb::ba::BlockPair> last_bps;  // the last completed build's block list
   // a build issued (dev_build_issue: phase 1 and the readback queued) and not yet finished
   hipEvent_t rb_ev = nullptr;
   bool rb_pending = false, rb_sorted = false, rb_fuse = false;
@@ -910,9 +922,96 @@ __device__ __forceinline__ void group_bounds(const int* __restrict__ off, int P,
   s0 = __shfl(lo, 0, 64);
   s1 = __shfl(lo, 32, 64);
 }
+// The speculative build (dev_spec_issue): the host has not seen phase 1's readback yet and assumes the
+// last build's adjacency pattern, hence its camera order, (ch, cl) block list, band and groups per
+// partial run.  One workgroup, queued behind the readback copy, takes the counts from the scratch
+// where phase 1 left them, checks that a plan built on the assumption stays inside the buffers as
+// allocated, and writes the count-dependent words of the upload block (the rest of it is the last
+// build's): BaWin's n_points / n_obs / n_obs_all / n_pblk / n_sg, live[], every block's pair count and
+// offset, the cameras' activity.  out[0] is the validity word: no error or out-of-order bit, the counts
+// within the capacities, every point within a point group, the point groups, their partials and the
+// partial-run factor as allocated / assumed, and the adjacency pattern of cov / cam_cnt equal to the
+// assumed one (cov holds the lower triangle: k_db_sorted<true>).  When it is 0 the plan left behind is
+// empty -- no points, observations, groups, blocks or runs -- so k_ba_init marks the window done and
+// every kernel of the LM graph exits: nothing is indexed with an unchecked count.  The word protects
+// the speculative solve only; the host decides hit or miss from the readback (dev_spec_verify).
+struct DbSpec {
+  int C, P_cap, K_cap, pblk_cap, nbp, sf, sg_force, part_stride;  // sg_force: LORB_SG_F (0: sg_factor's rule)
+  long long gpart_cap;
+  const int* hdr; const int* cov; const int* cam_cnt;
+  const unsigned char* adj;  // the assumed pattern, C x C
+  BaWin* win; int* live; BlockPair* bp; int* cam_active;
+  int* out;  // [0] valid, [1] K, [2] points, [3] point groups, [4] S (group size bound), [5] partial runs
+};
+__global__ __launch_bounds__(1024) void k_db_spec(DbSpec s, DbCams cams) {
+  __shared__ int s_inv[kPmSpan];
+  __shared__ int s_sum[1024];
+  __shared__ int s_bad;
+  const int t = threadIdx.x, C = s.C;
+  if (t == 0) s_bad = 0;
+  if (t < C) s_inv[cams.perm[t]] = t;
+  __syncthreads();
+  int K = s.hdr[0], Pn = s.hdr[3];
+  const int maxk = s.hdr[1], err = s.hdr[2];
+  bool ok = err == 0 && K >= 0 && K <= s.K_cap && Pn >= 0 && Pn <= s.P_cap && maxk >= 0 && maxk <= kGB - 1;
+  int S = 1, G = 0, NSG = 0;
+  if (ok) {  // db_layout's point groups and partial runs
+    S = kGB - maxk;
+    G = Pn > 0 ? (int)(((long long)K + Pn - 1) / S) + 1 : 0;
+    const int SF = s.sg_force ? (G > 1 ? s.sg_force : 1) : (G > 512 ? (G + 479) / 480 : 1);
+    NSG = G > 0 ? (G + SF - 1) / SF : 0;
+    ok = G <= s.pblk_cap && SF == s.sf && (long long)NSG * s.part_stride <= s.gpart_cap;
+  }
+  bool bad = false;
+  for (int k = t; k < C * C; k += 1024) {
+    const int i = k / C, j = k - i * C;
+    if (j <= i) bad |= ((i == j ? s.cam_cnt[i] : s.cov[k]) > 0) != (s.adj[k] != 0);
+  }
+  if (bad) s_bad = 1;
+  __syncthreads();
+  ok = ok && !s_bad;
+  if (!ok) { K = 0; Pn = 0; G = 0; NSG = 0; S = 1; }
+  if (t == 0) {
+    s.out[0] = ok; s.out[1] = K; s.out[2] = Pn; s.out[3] = G; s.out[4] = S; s.out[5] = NSG;
+    s.win->n_points = Pn; s.win->n_obs = K; s.win->n_obs_all = K; s.win->n_pblk = G; s.win->n_sg = NSG;
+    s.live[0] = G; s.live[1] = ok ? s.nbp : 0; s.live[2] = NSG;
+  }
+  if (!ok) return;
+  if (t < C) s.cam_active[cams.perm[t]] = s.cam_cnt[t] > 0;
+  // every block's pairs (db_blocks) and their running offset: thread t takes `per` consecutive blocks
+  const int per = (s.nbp + 1023) / 1024, b0 = min(t * per, s.nbp), b1 = min(b0 + per, s.nbp);
+  int sum = 0;
+  for (int k = b0; k < b1; ++k) {
+    const int a = s_inv[s.bp[k].ch], b = s_inv[s.bp[k].cl];
+    sum += a == b ? s.cam_cnt[a] : s.cov[max(a, b) * C + min(a, b)];
+  }
+  s_sum[t] = sum;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {  // inclusive scan of the threads' sums
+    const int v = t >= o ? s_sum[t - o] : 0;
+    __syncthreads();
+    s_sum[t] += v;
+    __syncthreads();
+  }
+  int off = s_sum[t] - sum;
+  for (int k = b0; k < b1; ++k) {
+    const int a = s_inv[s.bp[k].ch], b = s_inv[s.bp[k].cl];
+    const int cnt = a == b ? s.cam_cnt[a] : s.cov[max(a, b) * C + min(a, b)];
+    s.bp[k].off = off; s.bp[k].cnt = cnt;
+    off += cnt;
+  }
+}
+
+// SPEC: the speculative build's gather, behind k_db_spec: the counts come from `spec` (DbSpec::out,
+// zeros when the assumption failed), nothing is uploaded (the upload block holds the last build's
+// structure and k_db_spec's words) and the cameras' activity is k_db_spec's.  Every loop is
+// grid-stride, so the launch grid (predicted from the last counts) only bounds the parallelism.
+template <bool SPEC>
 __global__ __launch_bounds__(256) void k_db_gather(lorb_ba_window_dev w, BaDev d, int K, const int* __restrict__ key,
-                                                   const int* __restrict__ val, DbFused f, DbCams cams) {
+                                                   const int* __restrict__ val, DbFused f, DbCams cams,
+                                                   const int* __restrict__ spec) {
   const int gt = blockIdx.x * 256 + threadIdx.x, gs = gridDim.x * 256;
+  if (SPEC) { K = spec[1]; f.P = spec[2]; f.G = spec[3]; f.S = spec[4]; f.nsg = spec[5]; }
   // the upload, from the mapped staging (PCIe reads, no copy launch before this kernel)
   for (int i = gt; i < f.up_words; i += gs) f.up_dst[i] = f.up_src[i];
   const int* __restrict__ perm = cams.perm;
@@ -923,7 +1022,7 @@ __global__ __launch_bounds__(256) void k_db_gather(lorb_ba_window_dev w, BaDev d
       if (i < 6 * f.C) {
         const int c = i / 6, q = i - 6 * c;
         d.x_init_pose[6 * perm[c] + q] = (double)w.d_pose_init[i];
-        if (q == 0) const_cast<int*>(d.cam_active)[perm[c]] = gcam[c] > 0;
+        if (!SPEC && q == 0) const_cast<int*>(d.cam_active)[perm[c]] = gcam[c] > 0;
       }
       if (i < 6 * f.F) const_cast<double*>(d.fixed_pose)[i] = (double)w.d_fixed_pose[i];
       if (i < 3 * f.P) d.x_init_pt[i] = (double)w.d_point_init[i];
@@ -1066,8 +1165,11 @@ int up_alloc(lorb_ba_plan* P, int bp_need) {
   b.off_live = al(sizeof(BaWin));
   b.off_perm = b.off_live + 256;
   b.off_gcam = b.off_perm + al(4 * C);
-  b.off_bp = b.off_gcam + al(4 * C);
+  b.off_adj = b.off_gcam + al(4 * C);
+  b.off_bp = b.off_adj + al(C * C);
   b.up_bytes = b.off_bp + sizeof(BlockPair) * (size_t)cap;
+  b.spec_ok = false;  // the upload block moves: nothing of the last build is in the new one
+  if (!b.spec_out) LORB_TRY(dalloc(P, (size_t)8, &b.spec_out));
   if (b.up_dev) {
     LORB_TRY(dfree(P, b.up_dev));
     (void)hipHostFree(b.up_host);
@@ -1266,8 +1368,8 @@ int db_land(lorb_ctx* ctx, const lorb_ba_window_dev* w, lorb_ba_plan* P, int ler
 
 // Step 2: the camera order (input camera -> plan camera), from the global structure.  It depends
 // only on the adjacency pattern: compared in place against the last build's (no allocation on the
-// step's host phase), recomputed when it changed.
-void db_camera_order(lorb_ba_devbuild& b, const DbBuild& r) {
+// step's host phase), recomputed when it changed.  Returns whether the pattern was the last build's.
+bool db_camera_order(lorb_ba_devbuild& b, const DbBuild& r) {
   const int C = b.C;
   bool same_adj = b.last_adj.size() == (size_t)C * C;
   for (int i = 0; i < C && same_adj; ++i) {
@@ -1283,6 +1385,7 @@ void db_camera_order(lorb_ba_devbuild& b, const DbBuild& r) {
     b.last_map = camera_order(C, adj);
     b.last_adj.swap(adj);
   }
+  return same_adj;
 }
 
 // Step 3: the (camera, camera) block list from this rank's observations, in the std::map order of
@@ -1365,6 +1468,7 @@ void db_stage_and_gather(lorb_ctx* ctx, const lorb_ba_window_dev* w, lorb_ba_pla
   memcpy(h + b.off_live, live, sizeof(live));
   memcpy(h + b.off_perm, map.data(), sizeof(int) * C);
   memcpy(h + b.off_gcam, r.gcam, sizeof(int) * C);
+  if (!b.last_adj.empty()) memcpy(h + b.off_adj, b.last_adj.data(), b.last_adj.size());  // (what a speculative build assumes)
   if (!bps.empty()) memcpy(h + b.off_bp, bps.data(), sizeof(BlockPair) * bps.size());
   const int up_words = (int)((b.off_bp + sizeof(BlockPair) * bps.size() + 3) / 4);
   hp.mark(4);
@@ -1376,15 +1480,91 @@ void db_stage_and_gather(lorb_ctx* ctx, const lorb_ba_window_dev* w, lorb_ba_pla
   DbCams cams;
   for (int c = 0; c < C; ++c) { cams.perm[c] = map[c]; cams.gcam[c] = r.gcam[c]; }
   const int NB = lorb::ceil_div(r.K, 256);
-  hipLaunchKernelGGL(k_db_gather, dim3(std::max(NB, 1)), dim3(256), 0, ctx->stream, *w, P->dev, r.K, b.key_out, b.val_out,
-                     f, cams);
+  hipLaunchKernelGGL(k_db_gather<false>, dim3(std::max(NB, 1)), dim3(256), 0, ctx->stream, *w, P->dev, r.K, b.key_out,
+                     b.val_out, f, cams, (const int*)nullptr);
   b.dirty = false;
   hp.mark(5);
+}
+
+// LORB_SPEC_SPOIL=1 (tests; read at every build): flips one entry of the kept adjacency pattern on
+// the host, so the next speculative build's verification finds a changed pattern and falls back
+void spec_spoil(lorb_ba_devbuild& b) {
+  if (env_flag("LORB_SPEC_SPOIL") && b.last_adj.size() > 1) b.last_adj[1] ^= 1;
+}
+
+// A build may speculate when the plan is unsharded, its last build completed (and the upload block
+// has not moved since), its slots take the sorted phase 1 and the context is not timing kernels;
+// LORB_NO_SPEC=1 (read at every build) turns it off.
+bool spec_allowed(const lorb_ctx* ctx, const lorb_ba_plan* P) {
+  const lorb_ba_devbuild& b = *P->devb;
+  return !P->comm && b.spec_ok && b.sorted_hint && b.C > 0 && !ctx->ktime && !env_flag("LORB_NO_SPEC");
+}
+
+// The speculative half of a build, behind an issued phase 1 (sorted and fused) and its readback copy,
+// without waiting for it: k_db_spec, then the gather at a grid predicted from obs_hint (the caller's
+// bound on the live observations).  The host's own plan fields stay the last build's until
+// dev_spec_verify commits the new ones, so a solve enqueued in between makes its choices (fold_of,
+// red_threads, graph_key) from the last build's values.
+int dev_spec_issue(lorb_ctx* ctx, const lorb_ba_window_dev* w, lorb_ba_plan* P, int obs_hint) {
+  lorb_ba_devbuild& b = *P->devb;
+  const int C = b.C;
+  DbCams cams;
+  for (int c = 0; c < C; ++c) { cams.perm[c] = b.last_map[c]; cams.gcam[c] = 0; }
+  const char* e = getenv("LORB_SG_F");
+  const BaWin& hw = P->hwin[0];
+  DbSpec s{C, w->max_points, w->max_obs, b.pblk_cap, (int)b.last_bps.size(), b.spec_sf, e && atoi(e) >= 1 ? atoi(e) : 0,
+           hw.part_stride, (long long)b.gpart_cap, b.hdr, b.cov, b.cam_cnt, b.up_dev + b.off_adj,
+           reinterpret_cast<BaWin*>(b.up_dev), reinterpret_cast<int*>(b.up_dev + b.off_live),
+           reinterpret_cast<BlockPair*>(b.up_dev + b.off_bp), const_cast<int*>(P->dev.cam_active), b.spec_out};
+  hipLaunchKernelGGL(k_db_spec, dim3(1), dim3(1024), 0, ctx->stream, s, cams);
+  DbFused f{C, b.F, 0, 0, 1, P->env_total, C * b.Wd, 1, b.bits, b.hdr, b.cov, C * C + C, nullptr, nullptr, 0};
+  f.sgf = b.spec_sf; f.nsg = 0; f.sgrp = const_cast<int4*>(P->dev.sgrp);
+  const int NB = lorb::ceil_div(std::min(std::max(obs_hint, 1), std::max(w->max_obs, 1)), 256);
+  hipLaunchKernelGGL(k_db_gather<true>, dim3(NB), dim3(256), 0, ctx->stream, *w, P->dev, 0, b.key_out, b.val_out, f, cams,
+                     (const int*)b.spec_out);
+  LORB_CHECK_LAUNCH(ctx);
+  b.spec_pending = true;
+  return LORB_OK;
+}
+
+// The other half, after the solve is enqueued: waits for the readback (the spin stays) and runs the
+// host phase on it as dev_build_finish does (db_land to db_layout, and db_buffers' growth test without
+// reallocating).  *hit: every product equals the assumption -- the adjacency pattern (hence the
+// order), the block list, the band, the partial-run factor, no buffer has to grow, and the solve's
+// launch shape (ba_plan_solve_key_same, on the new plan fields) is the one it ran with -- and the new
+// host-side plan fields are committed.  An error of db_land / db_layout is returned as
+// dev_build_finish returns it.  Otherwise (*hit false) the caller builds again by dev_build.
+int dev_spec_verify(lorb_ctx* ctx, const lorb_ba_window_dev* w, lorb_ba_plan* P, bool* hit) {
+  lorb_ba_devbuild& b = *P->devb;
+  *hit = false;
+  b.spec_pending = false;
+  b.spec_ok = false;
+  b.rb_pending = false;
+  LORB_HIP(ctx, lorb::spin_wait(b.rb_ev));
+  if (b.pinned[2] & 16) return LORB_OK;  // slots out of order: dev_build reruns the general phase
+  const int bw_was = P->hwin[0].bw;
+  DbBuild r;
+  LORB_TRY(db_land(ctx, w, P, 0, LORB_OK, r));
+  if (!db_camera_order(b, r)) return LORB_OK;
+  db_blocks(b, r);
+  bool same = r.bw == bw_was && r.bps.size() == b.last_bps.size();
+  for (size_t i = 0; same && i < r.bps.size(); ++i) same = r.bps[i].ch == b.last_bps[i].ch && r.bps[i].cl == b.last_bps[i].cl;
+  if (!same) return LORB_OK;
+  LORB_TRY(db_layout(ctx, w, P, r));
+  if (r.SF != b.spec_sf || r.G > b.pblk_cap || (size_t)std::max(r.part_total, 1ll) > b.gpart_cap ||
+      (int)r.bps.size() > b.up_bp_cap || !lorb::ba_plan_solve_key_same(P))
+    return LORB_OK;
+  b.last_bps.swap(r.bps);
+  b.dirty = false;  // the speculative gather left the scratch clear
+  b.spec_ok = true;
+  *hit = true;
+  return LORB_OK;
 }
 
 // The second half of a build: wait for the readback, then the host phase: steps 1 to 6 above.
 int dev_build_finish(lorb_ctx* ctx, const lorb_ba_window_dev* w, lorb_ba_plan* P, int lerr) {
   lorb_ba_devbuild& b = *P->devb;
+  b.spec_ok = b.spec_pending = false;
   const int phase_rc = (lerr || !b.rb_pending) ? LORB_OK : db_phase1_wait(ctx, w, P);
   static const bool hp_log = env_flag("LORB_HOST_PHASE");
   HostPhase hp{P, hp_log};
@@ -1401,6 +1581,10 @@ int dev_build_finish(lorb_ctx* ctx, const lorb_ba_window_dev* w, lorb_ba_plan* P
   hp.mark(3);
   db_stage_and_gather(ctx, w, P, r, hp);
   LORB_CHECK_LAUNCH(ctx);
+  // what a speculative next build assumes (see lorb_ba_devbuild)
+  b.last_bps.swap(r.bps);
+  b.spec_sf = r.SF;
+  b.spec_ok = !P->comm;
   return LORB_OK;
 }
 
@@ -1469,6 +1653,24 @@ int ba_plan_update_dev_issue(lorb_ba_plan* P, const lorb_ba_window_dev* w) {
 int ba_plan_update_dev_finish(lorb_ba_plan* P, const lorb_ba_window_dev* w) {
   if (!P || !w || !P->devb || P->comm) return LORB_E_INVALID;
   return dev_build_finish(P->ctx, w, P, 0);
+}
+int ba_plan_update_dev_spec(lorb_ba_plan* P, const lorb_ba_window_dev* w, int obs_hint, bool* speculated) {
+  if (!P || !w || !P->devb || !speculated) return LORB_E_INVALID;
+  *speculated = false;
+  lorb_ctx* ctx = P->ctx;
+  lorb_ba_devbuild& b = *P->devb;
+  if (!spec_allowed(ctx, P)) return dev_build(ctx, w, P);
+  spec_spoil(b);
+  int lerr = 0;
+  LORB_TRY(dev_build_issue(ctx, w, P, &lerr));
+  if (!(b.rb_sorted && b.rb_fuse)) return dev_build_finish(ctx, w, P, lerr);
+  LORB_TRY(dev_spec_issue(ctx, w, P, obs_hint));
+  *speculated = true;
+  return LORB_OK;
+}
+int ba_plan_update_dev_verify(lorb_ba_plan* P, const lorb_ba_window_dev* w, bool* hit) {
+  if (!P || !w || !P->devb || !hit || !P->devb->spec_pending) return LORB_E_INVALID;
+  return dev_spec_verify(P->ctx, w, P, hit);
 }
 void ba_plan_sorted_hint(lorb_ba_plan* P, bool sorted) {
   if (P && P->devb) P->devb->sorted_hint = sorted;

@@ -113,6 +113,7 @@ struct lorb_ba_plan {
     int fold = 0;  // the folded iteration tail (lorb_ba_plan::fold)
     bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) == 0; }
   } gkey;
+  GraphKey skey;  // the launch shape of the last solve, captured or not (a speculative build's verification)
   int grid_pblk = 0, grid_bp = 0;  // launch grids of the point-group and block-pair kernels
   int grid_sg = 0;                 // k_ba_ls_sup's grid (partial runs)
   bool has_super = false;          // some window's partial runs hold more than one point group

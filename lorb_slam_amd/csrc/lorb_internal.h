@@ -124,6 +124,17 @@ void ba_plan_sorted_hint(lorb_ba_plan* P, bool sorted);
 // build.  Work for other plans may be queued in between (lorb_map_group builds its maps this way).
 int ba_plan_update_dev_issue(lorb_ba_plan* P, const lorb_ba_window_dev* w);
 int ba_plan_update_dev_finish(lorb_ba_plan* P, const lorb_ba_window_dev* w);
+// lorb_ba_plan_update_dev that speculates on the plan's structure where it may (lorb_ba_build.hip,
+// dev_spec_issue): *speculated -- phase 1, its readback and a gather that assumes the last build's
+// adjacency pattern are queued and the host has not waited; the caller enqueues the solve and then
+// calls ..._verify, which waits for the readback and runs the host phase on it: *hit -- the assumption
+// held and the plan is the one lorb_ba_plan_update_dev would have built; an error is the build's; else
+// the caller builds again (lorb_ba_plan_update_dev) and solves again.  Not speculated: the build is
+// complete (or failed) as lorb_ba_plan_update_dev leaves it.  obs_hint: a bound on the live observations.
+int ba_plan_update_dev_spec(lorb_ba_plan* P, const lorb_ba_window_dev* w, int obs_hint, bool* speculated);
+int ba_plan_update_dev_verify(lorb_ba_plan* P, const lorb_ba_window_dev* w, bool* hit);
+// the launch shape (graph key, fold) the plan's fields give now equals the last solve's (lorb_ba.hip)
+bool ba_plan_solve_key_same(lorb_ba_plan* P);
 // the window's live point / observation counts as the last lorb_ba_plan_update_dev read them
 void ba_plan_window_counts(const lorb_ba_plan* P, int* n_points, int* n_obs);
 // the last device build's per-point observation offsets (point-sorted slots), device pointer

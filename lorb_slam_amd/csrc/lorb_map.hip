@@ -344,6 +344,10 @@ struct lorb_map {
   hipEvent_t ev_built = nullptr, ev_app = nullptr;
   bool built = false;  // ev_built recorded by the previous step
   int n_overlapped = 0;  // steps whose match + append ran on the side stream
+  // lorb_map_step_dev speculates on the plan's structure (lorb::ba_plan_update_dev_spec): the gather and
+  // the solve are enqueued before the plan readback lands, the host phase verifies afterwards
+  bool spec = false;     // this step's build is speculative and not yet verified
+  int n_spec = 0, n_fallback = 0;  // speculated builds; those whose assumption failed (built and solved again)
   std::vector<void*> allocs;
   ~lorb_map() {
     if (prof && prof_n)
@@ -544,21 +548,29 @@ int map_build_fail(lorb_map* M, int rc) {
   return rc;
 }
 
-int map_build_done(lorb_map* M) {
+// the plan build's gather is queued: it has read the map, so the next step's match and append may
+// start behind it (see `side`)
+int map_built_event(lorb_map* M) {
   lorb_ctx* ctx = M->ctx;
-  M->plan_ok = true;
-  // the plan build has read the map: the next step's match and append may start (see `side`)
   if (!M->ev_built) LORB_HIP(ctx, hipEventCreateWithFlags(&M->ev_built, hipEventDisableTiming));
   LORB_HIP(ctx, hipEventRecord(M->ev_built, ctx->stream));
   M->built = true;
+  return LORB_OK;
+}
+
+int map_build_done(lorb_map* M) {
+  M->plan_ok = true;
+  LORB_TRY(map_built_event(M));
   LORB_TRY(map_mark(M, 4));
   lorb::ba_plan_window_counts(M->plan, &M->h_P, &M->h_K);
   return LORB_OK;
 }
 
-// steps 1-5 of lorb_map_step_dev: everything before the BA solve
+// steps 1-5 of lorb_map_step_dev: everything before the BA solve.  may_spec (lorb_map_step_dev): the
+// plan build may speculate; M->spec then says it did, and the caller verifies it after the solve.
 int map_prepare(lorb_map* M, const lorb_frame_params* frame, const float pose[6], const float Tcw[16], int32_t n,
-                const uint8_t* d_desc, const float* d_x, const float* d_y, const float* d_depth, bool split = false) {
+                const uint8_t* d_desc, const float* d_x, const float* d_y, const float* d_depth, bool split = false,
+                bool may_spec = false) {
   if (!M || !frame || !pose || !Tcw || n < 0) return LORB_E_INVALID;
   lorb_ctx* ctx = M->ctx;
   if (n > M->n_cap) return lorb::set_error(ctx, LORB_E_INVALID, "%d keypoints > the map's max_keypoints %d", n, M->n_cap);
@@ -641,8 +653,45 @@ int map_prepare(lorb_map* M, const lorb_frame_params* frame, const float pose[6]
     if (const int rc = lorb::ba_plan_update_dev_issue(M->plan, &w); rc != LORB_OK) return map_build_fail(M, rc);
     return LORB_OK;
   }
+  // (a map's first step, and the one after a failed build, build in full: the assumption is the
+  // previous step's window)
+  if (may_spec && M->built && !M->prof) {
+    const int obs_hint = std::min(M->h_K + n, m.K_cap);  // the last build's observations and the append's
+    if (const int rc = lorb::ba_plan_update_dev_spec(M->plan, &w, obs_hint, &M->spec); rc != LORB_OK) {
+      M->spec = false;
+      return map_build_fail(M, rc);
+    }
+    if (M->spec) {  // counts, plan_ok: after the verification
+      M->n_spec++;
+      return map_built_event(M);
+    }
+    return map_build_done(M);
+  }
   if (const int rc = lorb_ba_plan_update_dev(M->plan, &w); rc != LORB_OK) return map_build_fail(M, rc);
   return map_build_done(M);
+}
+
+// A speculative build after its solve is enqueued: the host's verification.  The assumption held:
+// the plan is built (map_build_done's host-side part).  It failed: the whole build again, waiting for
+// its readback, in stream order behind the speculative solve (a no-op when the device saw the failure
+// too), ev_built recorded anew behind the gather that counts, and the solve again.  A build error is
+// the step's, as from map_prepare.
+int map_spec_verify(lorb_map* M, const lorb_lm_options* opt) {
+  M->spec = false;
+  const lorb_ba_window_dev w = window_of(M);
+  bool hit = false;
+  if (const int rc = lorb::ba_plan_update_dev_verify(M->plan, &w, &hit); rc != LORB_OK) return map_build_fail(M, rc);
+  if (!hit) {
+    M->n_fallback++;
+    if (const int rc = lorb_ba_plan_update_dev(M->plan, &w); rc != LORB_OK) return map_build_fail(M, rc);
+  }
+  M->plan_ok = true;
+  lorb::ba_plan_window_counts(M->plan, &M->h_P, &M->h_K);
+  if (!hit) {
+    LORB_TRY(map_built_event(M));
+    LORB_TRY(lorb_ba_plan_solve(M->plan, opt));
+  }
+  return LORB_OK;
 }
 
 // the second half of a split step 5
@@ -681,9 +730,16 @@ int lorb_map_step_dev(lorb_map* M, const lorb_frame_params* frame, const float p
                       const uint8_t* d_desc, const float* d_x, const float* d_y, const float* d_depth,
                       const lorb_lm_options* opt) {
   if (!M || !opt) return LORB_E_INVALID;
-  LORB_TRY(map_prepare(M, frame, pose, Tcw, n, d_desc, d_x, d_y, d_depth));
-  // 6. LocalPoseOptimization, then the float write-back
-  LORB_TRY(lorb_ba_plan_solve(M->plan, opt));
+  LORB_TRY(map_prepare(M, frame, pose, Tcw, n, d_desc, d_x, d_y, d_depth, false, true));
+  // 6. LocalPoseOptimization, then the float write-back.  Behind a speculative build the solve is
+  // enqueued first and the build verified after it (a solve that could not be enqueued leaves the
+  // build unverified: the counts are re-read as after a failed build)
+  if (const int rc = lorb_ba_plan_solve(M->plan, opt); rc != LORB_OK) {
+    if (!M->spec) return rc;
+    M->spec = false;
+    return map_build_fail(M, rc);
+  }
+  if (M->spec) LORB_TRY(map_spec_verify(M, opt));
   LORB_TRY(map_mark(M, 5));
   return map_finish(M);
 }
@@ -702,9 +758,10 @@ int lorb_map_counts(lorb_map* M, int32_t* out, int32_t n) {
   lorb_ctx* ctx = M->ctx;
   LORB_HIP(ctx, hipMemcpyAsync(M->pinned, M->m.cnt, sizeof(int) * 8, hipMemcpyDeviceToHost, ctx->stream));
   LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const int32_t v[9] = {M->pinned[0], M->pinned[1], M->t0, M->last_n, M->pinned[3], M->pinned[4], M->pinned[5], M->m.W,
-                        M->n_overlapped};
-  for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
+  // ([9], [10]: plan builds that speculated, and those of them that fell back)
+  const int32_t v[11] = {M->pinned[0], M->pinned[1], M->t0, M->last_n, M->pinned[3], M->pinned[4], M->pinned[5], M->m.W,
+                         M->n_overlapped, M->n_spec, M->n_fallback};
+  for (int i = 0; i < n && i < 11; ++i) out[i] = v[i];
   return LORB_OK;
 }
 

@@ -477,7 +477,7 @@ class LocalMap:
     obs_point, obs_kf (keyframe ids in [-F, W)), obs_uv, intr) -- synth.mapping_sequence()["init"]."""
 
     COUNT_KEYS = ("points", "observations", "t0", "keypoints", "new_points", "new_observations", "matches", "window",
-                  "overlapped_steps")
+                  "overlapped_steps", "speculated_builds", "spec_fallbacks")
 
     def __init__(self, ctx, init, max_points=None, max_obs=None, max_keypoints=4096):
         self.ctx, self._keep = ctx, A.KeepAlive()
@@ -527,8 +527,10 @@ class LocalMap:
                 a.free()
 
     def counts(self):
-        v = (C.c_int32 * 9)()
-        self.ctx.check(lib().lorb_map_counts(self._p, v, C.c_int32(9)), "lorb_map_counts")
+        """lorb_map_counts; its last two words count the step's plan builds that speculated on the
+        plan's structure and those of them that fell back to a full build"""
+        v = (C.c_int32 * len(self.COUNT_KEYS))()
+        self.ctx.check(lib().lorb_map_counts(self._p, v, C.c_int32(len(v))), "lorb_map_counts")
         return dict(zip(self.COUNT_KEYS, [int(x) for x in v]))
 
     def read(self):

@@ -1018,6 +1018,141 @@ int lorb_frame_pose_finish_dev(lorb_ctx* ctx, const lorb_track_local_frames_resu
                                const lorb_frame_pose* d_last_pose, lorb_frame_pose* d_cur_pose,
                                lorb_motion_model* d_model);
 
+/* ----------------------------------------------------------------------------------------
+ * The map store as a device object that grows in the frame chain: VisualOdometry::AddKeyFrame
+ * (src/visual_odometry.cpp:356-404) and the map part of Initialize (:86-103), LocalMapping::ProcessNewFrames
+ * step 1 (src/local_mapping.cpp:57-70) and Frame::UpdateConnections (src/frame.cpp:801-869) with AddConnection
+ * and UpdateBestCovisibleFrames (:754-788), as ONE enqueued call behind lorb_frame_pose_finish_dev.
+ *
+ * A lorb_kf_store owns every array of a lorb_map_store (the layout and ordering convention above) plus each
+ * keyframe's mConnectedKeyFrameWeights (the reference rebuilds mvpOrderedKeyFrames from that map, so the store
+ * keeps it).  lorb_kf_store_host is the same store in host arrays: `init` of create (the n_* fields are the
+ * counts; NULL: an empty store) and the target of read (the n_* fields are the CAPACITIES of the caller's
+ * arrays, in entries of each table; any array may be NULL: not read).  conn_off / conn_kf / conn_w is the weight
+ * map as a CSR over the keyframes, entries in ascending keyframe index (std::map<Frame*, size_t> order).
+ *
+ * Capacities: max_kf in [1, 4096] (the counter and the per-row sort of an insertion keep a keyframe row in
+ * LDS), max_points, max_obs, max_kf_slots >= 1; the covisibility table holds max_kf * max_kf entries.
+ *
+ * Counts.  The TRUE counts (n_kf, n_points, n_obs, n_kf_slots, n_cov, n_conn) live on the device, because the
+ * gate of an insertion is decided there.  The host keeps upper BOUNDS it can advance without waiting: one
+ * keyframe, n_max_cur points and n_max_cur keyframe slots per enqueued insertion (each clipped to its capacity),
+ * and the table capacities for n_obs and n_cov.  lorb_kf_store_view returns the device arrays with those bounds
+ * as the host counts (no wait; the pointers never change, so a view taken before the insertions in front of it
+ * have run stays valid).  Rows between a true count and its bound are inert: is_bad = 1 and kf_bad = 1 (set at
+ * create over the whole capacity) and no slot, observation or covisibility list refers to them, so the view
+ * handed to lorb_local_map_update_dev gives the record, slots, gids, local ids, votes, list, l2g, g2l and table
+ * rows the same call gives on an exact store (kf_votes / g2l entries between truth and bound are written as 0
+ * / -1: they are below the counts that call was given).  The slot gids handed to it must be indices the store
+ * issued.  lorb_kf_store_counts waits for the stream, stores the first min(n, 6) true counts in the order above
+ * and replaces the bounds by the truth.  lorb_kf_store_read waits and copies the true rows of every non-NULL
+ * member (LORB_E_INVALID when a capacity field is below its true count).
+ * create validates `init` (counts within the capacities, offsets ascending from 0 and ending at their table's
+ * length, every index inside its table, weight-map rows strictly ascending) and waits for the stream.
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_kf_store lorb_kf_store;
+typedef struct lorb_kf_store_caps { int32_t max_kf, max_points, max_obs, max_kf_slots; } lorb_kf_store_caps;
+typedef struct lorb_kf_store_host {
+  int32_t n_kf, n_points, n_obs, n_kf_slots, n_cov, n_conn;
+  float* pos;                 /* n_points x 3 */
+  float* normal;              /* n_points x 3 */
+  float* max_dist;            /* n_points */
+  float* min_dist;            /* n_points */
+  uint8_t* desc;              /* n_points x 32 */
+  uint8_t* locked;            /* n_points */
+  uint8_t* is_bad;            /* n_points */
+  int32_t* obs_off;           /* n_points + 1 */
+  int32_t* obs_kf;            /* n_obs, each list in ascending keyframe index */
+  uint8_t* kf_bad;            /* n_kf */
+  int32_t* kf_slot_off;       /* n_kf + 1 */
+  int32_t* kf_slot_point;     /* n_kf_slots */
+  int32_t* cov_off;           /* n_kf + 1 */
+  int32_t* cov_kf;            /* n_cov: mvpOrderedKeyFrames */
+  int32_t* conn_off;          /* n_kf + 1 */
+  int32_t* conn_kf;           /* n_conn: mConnectedKeyFrameWeights, keys */
+  int32_t* conn_w;            /* n_conn: its weights */
+} lorb_kf_store_host;
+int lorb_kf_store_create(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_store_host* init, lorb_kf_store** out);
+int lorb_kf_store_destroy(lorb_kf_store* store);
+int lorb_kf_store_view(const lorb_kf_store* store, lorb_map_store* out);         /* no wait */
+int lorb_kf_store_counts(lorb_kf_store* store, int32_t* out, int32_t n);         /* waits; tightens the host bounds */
+int lorb_kf_store_read(lorb_kf_store* store, const lorb_kf_store_host* out);     /* waits */
+
+#define LORB_KF_GATE_RATIO 0   /* AddKeyFrame's ratio test, src/visual_odometry.cpp:360-372 */
+#define LORB_KF_GATE_NONE  1   /* Initialize (:86-103): always inserted; mnMapPoints < 300 (:80) stays the caller's */
+typedef struct lorb_kf_insert_result {
+  int32_t status;      /* 0; 1: bad count or source status; 2: a capacity */
+  int32_t inserted;    /* 0: the gate said no */
+  int32_t n_cur, n_map;
+  int32_t kf;          /* K, or -1 */
+  int32_t n_observed;  /* observations added to points the store already had */
+  int32_t n_adopted, n_created;
+  int32_t n_connected; /* length of K's ordered list */
+  int32_t n_points, n_kf, n_obs;   /* the store after the call */
+} lorb_kf_insert_result;
+
+/* Inserts the current frame as keyframe K = the true n_kf on entry.  In the frame chain it is enqueued behind
+ * lorb_frame_pose_finish_dev with the frame's lorb_local_map_ids_back_dev gids and d_src_status =
+ * &d_local_result->status.  Host values: frame (fx, fy, cx, cy, n_levels, scale_factors are read), n_max_cur,
+ * gate.  d_cur is a host struct of device pointers (counts[0], the left x, y, octave, desc and depth are read),
+ * d_cur_slots a host struct of device arrays (read and written), d_cur_slot_gid n_max_cur device int32 (read and
+ * written), d_cur_pose the frame's block (Twc and status are read); d_src_status, d_refer_kf and d_update are
+ * nullable.  On the device, in this order:
+ *   a. Status: counts[0] negative or above n_max_cur, d_cur_pose->status != 0 or *d_src_status != 0 stores
+ *      status = 1 and NOTHING else.
+ *   b. Gate (:360-372), LORB_KF_GATE_RATIO: nMap = the non-EMPTY slots j < n_cur, ratio = (float)nMap /
+ *      (float)n_cur; ratio > 0.35f stores inserted = 0, n_map and status = 0 and NOTHING else.  n_cur = 0 makes the
+ *      ratio NaN: the comparison is false and an empty keyframe is inserted, as in the reference.
+ *      LORB_KF_GATE_NONE always goes on.
+ *   c. Capacity: status = 2 (with the counts the call found: n_cur, n_map, kf = -1, n_observed, n_adopted,
+ *      n_created, and the store's unchanged n_points, n_kf, n_obs) and nothing written to the store, the slots or
+ *      the gids when K + 1 would exceed max_kf or the new points, observations or keyframe slots would pass
+ *      max_points, max_obs, max_kf_slots.  Decided before the first store write.
+ *   d. Every slot j < n_cur with gid g (an index outside [0, n_points) counts as -1):
+ *        held, g >= 0, point bad      nothing is added (src/local_mapping.cpp:60-61); slot, gid and K's row keep g
+ *        held, g >= 0, not bad        AddObservation(K, j) (src/local_mapping.cpp:62-65, src/map_point.cpp:133-139):
+ *                                     K joins the point's observation list ONCE however many slots hold g (the
+ *                                     lowest slot adds it), last -- lists stay in ascending keyframe index;
+ *                                     locked[g] = 1 and the slot becomes LOCKED
+ *        held, g == -1                a point UpdateFrame created: ADOPTED as a new store point with the slot's
+ *                                     position and descriptor; the slot becomes LOCKED
+ *        EMPTY, depth[j] >= 0         CREATED by Initialize's live rule (:88-98): position = the bits of
+ *                                     lorb_unproject_stereo_dev under d_cur_pose->Twc, descriptor = the frame's
+ *                                     descriptor j; the slot becomes LOCKED with that position and descriptor
+ *        EMPTY, depth[j] < 0          stays EMPTY; its gid and K's row entry are -1
+ *      New points, adopted and created alike, are numbered from n_points in ascending slot order, each with
+ *      locked = 1, is_bad = 0, observation list {K} and its slot's gid set to the new index.  normal, max_dist
+ *      and min_dist are UpdateNormalAndDepth over that one observation (src/map_point.cpp:224-264), RESTATED, not
+ *      verified against OpenCV (as cv::gemm and cv::Mat::inv are restated): d = pos - Ow in float, Ow = (Twc[3],
+ *      Twc[7], Twc[11]); nd = sqrt((double)d.x*d.x + (double)d.y*d.y + (double)d.z*d.z) summed in that order;
+ *      normal = d * (float)(1.0 / nd), a float multiply; dist = (float)nd; max_dist = dist *
+ *      scale_factors[octave[j]]; min_dist = max_dist / scale_factors[n_levels - 1]; no FMA contraction.
+ *   e. K's row: kf_slot_point gets the n_cur gids after step d; kf_bad[K] = 0.
+ *   f. UpdateConnections(K) (src/frame.cpp:801-869).  The counter is taken per SLOT (a point held in two slots
+ *      counts twice) over K's non-EMPTY slots with a non-bad store point and that point's observers other than K.
+ *      For keyframes f in ascending index with count w: w >= 3 enters K's pairs and f.AddConnection(K, w).  With no
+ *      pair at all the reference compares against size_t nMax = -1 and dereferences NULL (:825-848); ORB-SLAM2's
+ *      intent is restated: the first keyframe with the strictly largest count gets the one connection; every
+ *      count zero: none.  K's weight map is the whole counter, entries below 3 included (:855); K's ordered list
+ *      is the pairs ascending by (weight, index) (:851).  f.AddConnection(K, w) (:777-788) sets f's weight for K and
+ *      rebuilds f's ordered list from ALL of f's weight map ascending by (weight, index) (:754-774), entries below
+ *      3 included.  Ascending order means GetBestCovisibleFrames(10) returns the weakest ten: kept.
+ *   g. mReferFrame = mCurrFrame (:402): K is stored at d_refer_kf and in d_update->refer_kf (this frame's
+ *      lorb_local_map_update_dev record, which the next frame's lorb_track_motion_refer_pose_dev re-applies to the
+ *      word in its step b), each when given.  Only on insertion.
+ *   h. The device counts and the record.
+ * Nothing at or past a new true count is written, in any array of the store, the slots or the gids.
+ * LORB_E_INVALID, before anything is enqueued: a null required argument, a store of another ctx, n_max_cur < 1 or
+ * above max_kf_slots, an unknown gate, n_levels outside [1, LORB_MAX_LEVELS], a null array in d_cur / d_cur_slots, a
+ * descriptor array (the frame's left.desc, the slots' desc) that is not 16-byte aligned.
+ * Asynchronous on the ctx stream: 6 kernel launches, no stream synchronise, no device-to-host read and no
+ * host-to-device copy. */
+int lorb_kf_store_insert_dev(lorb_ctx* ctx, lorb_kf_store* store, const lorb_frame_params* frame,
+                             const lorb_frame_out* d_cur, int32_t n_max_cur, const lorb_frame_slots* d_cur_slots,
+                             int32_t* d_cur_slot_gid, const lorb_frame_pose* d_cur_pose, const int32_t* d_src_status,
+                             int32_t gate, int32_t* d_refer_kf, lorb_local_map_result* d_update,
+                             lorb_kf_insert_result* d_result);
+
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.
  * obs_frame[k] >= 0 : optimised pose index (PoseMPCost, src/bundle_adjust.cpp:293-301)

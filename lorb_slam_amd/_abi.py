@@ -255,6 +255,28 @@ class TrackReferResult(C.Structure):  # lorb_track_refer_result
                 ("first_nmatches_retry", C.c_int32)]
 
 
+LORB_KF_GATE_RATIO, LORB_KF_GATE_NONE = 0, 1
+
+
+class KfStoreCaps(C.Structure):  # lorb_kf_store_caps
+    _fields_ = [("max_kf", C.c_int32), ("max_points", C.c_int32), ("max_obs", C.c_int32), ("max_kf_slots", C.c_int32)]
+
+
+class KfStoreHost(C.Structure):  # lorb_kf_store_host (host addresses)
+    _fields_ = [("n_kf", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32), ("n_kf_slots", C.c_int32),
+                ("n_cov", C.c_int32), ("n_conn", C.c_int32), ("pos", C.c_void_p), ("normal", C.c_void_p),
+                ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("desc", C.c_void_p), ("locked", C.c_void_p),
+                ("is_bad", C.c_void_p), ("obs_off", C.c_void_p), ("obs_kf", C.c_void_p), ("kf_bad", C.c_void_p),
+                ("kf_slot_off", C.c_void_p), ("kf_slot_point", C.c_void_p), ("cov_off", C.c_void_p), ("cov_kf", C.c_void_p),
+                ("conn_off", C.c_void_p), ("conn_kf", C.c_void_p), ("conn_w", C.c_void_p)]
+
+
+class KfInsertResult(C.Structure):  # lorb_kf_insert_result
+    _fields_ = [("status", C.c_int32), ("inserted", C.c_int32), ("n_cur", C.c_int32), ("n_map", C.c_int32),
+                ("kf", C.c_int32), ("n_observed", C.c_int32), ("n_adopted", C.c_int32), ("n_created", C.c_int32),
+                ("n_connected", C.c_int32), ("n_points", C.c_int32), ("n_kf", C.c_int32), ("n_obs", C.c_int32)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

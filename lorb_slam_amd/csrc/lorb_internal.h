@@ -392,6 +392,16 @@ __device__ __forceinline__ void unproject_point(float fx, float fy, float cx, fl
     out[r] = (float)s;
   }
 }
+// (a20) Frame::UnprojectStereo of one keypoint: the origin where it has no depth (src/frame.cpp:352-355).
+// Shared by k_unproject, k_slots_fill and the keyframe insertion (lorb_kfstore.hip).
+__device__ __forceinline__ void unproject_kp(const lorb_frame_params& fp, const Mat4f& Twc, float x, float y, float z,
+                                             float* out) {
+  if (z > 0) {
+    unproject_point(fp.fx, fp.fy, fp.cx, fp.cy, Twc, x, y, z, out);
+  } else {
+    out[0] = 0.0f; out[1] = 0.0f; out[2] = 0.0f;
+  }
+}
 // cv::Mat::inv() of a 4x4 CV_32F (hal::LU32f) (lorb_window.hip; float only, compiled
 // -ffp-contract=off: the device value has the bits of the host's).  Device code of lorb_window.hip only.
 __host__ __device__ bool inv4_lu32f(const float* A, float* out);

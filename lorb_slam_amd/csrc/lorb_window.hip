@@ -845,22 +845,13 @@ __global__ __launch_bounds__(64 * kCandWaves) void k_cand_local_fr_dc(KpDev K, W
                                  cand, stride);
 }
 
-// (a20) Frame::UnprojectStereo of one keypoint: the origin where it has no depth (src/frame.cpp:352-355)
-__device__ __forceinline__ void unproject_kp(const lorb_frame_params& fp, const lorb::Mat4f& Twc, float x, float y,
-                                             float z, float* out) {
-  if (z > 0) {
-    lorb::unproject_point(fp.fx, fp.fy, fp.cx, fp.cy, Twc, x, y, z, out);
-  } else {
-    out[0] = 0.0f; out[1] = 0.0f; out[2] = 0.0f;
-  }
-}
 // one thread per keypoint; Twc = mTcw.inv() given
 __global__ __launch_bounds__(256) void k_unproject(lorb_frame_params fp, lorb::Mat4f Twc, int n,
                                                    const float* __restrict__ x, const float* __restrict__ y,
                                                    const float* __restrict__ depth, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  unproject_kp(fp, Twc, x[i], y[i], depth[i], out + 3 * i);
+  lorb::unproject_kp(fp, Twc, x[i], y[i], depth[i], out + 3 * i);
 }
 
 // The map-point slots of a built frame (lorb_frame_slots_fill_dev; the first launch of
@@ -1023,7 +1014,7 @@ __global__ __launch_bounds__(1024) void k_slots_fill(SlotFill a, lorb::FrameCoun
       st = fill ? LORB_SLOT_LOCKED : LORB_SLOT_EMPTY;
     }
     if (fill) {
-      unproject_kp(a.fp, POSE ? twc_blk : a.Twc, a.x[i], a.y[i], a.depth[i], a.pos + 3 * (size_t)i);
+      lorb::unproject_kp(a.fp, POSE ? twc_blk : a.Twc, a.x[i], a.y[i], a.depth[i], a.pos + 3 * (size_t)i);
       a.sdesc[2 * (size_t)i] = a.desc[2 * (size_t)i];
       a.sdesc[2 * (size_t)i + 1] = a.desc[2 * (size_t)i + 1];
       made++;

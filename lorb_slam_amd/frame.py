@@ -409,6 +409,149 @@ def local_map_ids_back(ctx, lmap, cur, cur_slots, slot_id, slot_gid, n_max_cur=N
         C.c_void_p(d_local_status) if d_local_status else None, slot_gid.ptr), "lorb_local_map_ids_back_dev")
 
 
+def _csr(lists):
+    off = np.zeros(len(lists) + 1, np.int32)
+    off[1:] = np.cumsum([len(x) for x in lists])
+    flat = np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in lists]) if len(lists) else np.zeros(0, np.int32)
+    return off, np.ascontiguousarray(flat, np.int32)
+
+
+def _uncsr(off, flat):
+    return [[int(v) for v in flat[off[i]:off[i + 1]]] for i in range(len(off) - 1)]
+
+
+class KeyframeStore:
+    """lorb_kf_store: the map store as a device object that lorb_kf_store_insert_dev grows (keyframe_insert).
+    init: None (empty) or dict(pos, normal, max_dist, min_dist, desc, locked, is_bad or None: n_points rows;
+    obs: per point its observing keyframes; kf_bad; kf_slots: per keyframe its slots' point indices; cov: per
+    keyframe its ordered covisible keyframes; conn: per keyframe {keyframe: weight}, mConnectedKeyFrameWeights).
+    .c is the A.MapStore view with the host's current BOUNDS as counts -- what local_map_update takes as
+    store.c; arrays: DeviceArray views of the store's own memory over its whole capacity (not to be freed)."""
+    COUNTS = ("n_kf", "n_points", "n_obs", "n_kf_slots", "n_cov", "n_conn")
+    _COLS = dict(pos=(np.float32, 3), normal=(np.float32, 3), max_dist=(np.float32, 1), min_dist=(np.float32, 1),
+                 desc=(np.uint8, 32), locked=(np.uint8, 1), is_bad=(np.uint8, 1))
+
+    def __init__(self, ctx, max_kf, max_points, max_obs, max_kf_slots, init=None):
+        self.ctx = ctx
+        self.caps = A.KfStoreCaps(int(max_kf), int(max_points), int(max_obs), int(max_kf_slots))
+        self.max_cov = int(max_kf) * int(max_kf)
+        self._p = C.c_void_p()
+        h, keep = (None, None) if init is None else self._host(init)
+        ctx.check(lib().lorb_kf_store_create(ctx.handle, C.byref(self.caps), C.byref(h) if h is not None else None,
+                                             C.byref(self._p)), "lorb_kf_store_create")
+        v = self.view()
+        cap = dict(n_points=self.caps.max_points, n_kf=self.caps.max_kf)
+
+        def arr(addr, n, dt, w=1):
+            return DeviceArrayView(ctx, addr, (n, w) if w > 1 else (n,), dt)
+
+        self.arrays = {k: arr(getattr(v.points, k), cap["n_points"], dt, w) for k, (dt, w) in self._COLS.items()}
+        self.arrays.update(obs_off=arr(v.obs_off, cap["n_points"] + 1, np.int32), obs_kf=arr(v.obs_kf, self.caps.max_obs, np.int32),
+                           kf_bad=arr(v.kf_bad, cap["n_kf"], np.uint8), kf_slot_off=arr(v.kf_slot_off, cap["n_kf"] + 1, np.int32),
+                           kf_slot_point=arr(v.kf_slot_point, self.caps.max_kf_slots, np.int32),
+                           cov_off=arr(v.cov_off, cap["n_kf"] + 1, np.int32), cov_kf=arr(v.cov_kf, self.max_cov, np.int32))
+
+    @staticmethod
+    def _host(s):
+        n = len(s["pos"])
+        keep = {k: np.ascontiguousarray(s[k], dt).reshape(-1) for k, (dt, _) in KeyframeStore._COLS.items() if s.get(k) is not None}
+        (keep["obs_off"], keep["obs_kf"]), (keep["kf_slot_off"], keep["kf_slot_point"]) = _csr(s["obs"]), _csr(s["kf_slots"])
+        keep["cov_off"], keep["cov_kf"] = _csr(s["cov"])
+        conn = s.get("conn") or [{} for _ in s["kf_bad"]]
+        keep["conn_off"], keep["conn_kf"] = _csr([sorted(c) for c in conn])
+        keep["conn_w"] = _csr([[c[k] for k in sorted(c)] for c in conn])[1]
+        keep["kf_bad"] = np.ascontiguousarray(s["kf_bad"], np.uint8)
+        h = A.KfStoreHost(len(keep["kf_bad"]), n, len(keep["obs_kf"]), len(keep["kf_slot_point"]), len(keep["cov_kf"]),
+                          len(keep["conn_kf"]))
+        for k, a in keep.items():
+            setattr(h, k, a.ctypes.data)
+        h._keep = keep
+        return h, keep
+
+    def view(self):
+        """lorb_kf_store_view: the A.MapStore with the host's bounds as counts (no wait)."""
+        v = A.MapStore()
+        self.ctx.check(lib().lorb_kf_store_view(self._p, C.byref(v)), "lorb_kf_store_view")
+        return v
+
+    @property
+    def c(self):
+        return self.view()
+
+    def counts(self):
+        """lorb_kf_store_counts: dict of the six true counts (waits; tightens the host's bounds)."""
+        out = np.zeros(6, np.int32)
+        self.ctx.check(lib().lorb_kf_store_counts(self._p, out.ctypes.data_as(C.c_void_p), C.c_int32(6)), "lorb_kf_store_counts")
+        return dict(zip(self.COUNTS, (int(v) for v in out)))
+
+    def read(self):
+        """lorb_kf_store_read (waits): dict(the six counts; the point columns; obs, kf_slots, cov as lists per row;
+        kf_bad; conn: per keyframe {keyframe: weight}; csr: the raw offset / index arrays)."""
+        n = self.counts()
+        nk, np_ = n["n_kf"], n["n_points"]
+        a = {k: np.zeros((np_, w) if w > 1 else np_, dt) for k, (dt, w) in self._COLS.items()}
+        a.update(obs_off=np.zeros(np_ + 1, np.int32), obs_kf=np.zeros(n["n_obs"], np.int32), kf_bad=np.zeros(nk, np.uint8),
+                 kf_slot_off=np.zeros(nk + 1, np.int32), kf_slot_point=np.zeros(n["n_kf_slots"], np.int32),
+                 cov_off=np.zeros(nk + 1, np.int32), cov_kf=np.zeros(n["n_cov"], np.int32), conn_off=np.zeros(nk + 1, np.int32),
+                 conn_kf=np.zeros(n["n_conn"], np.int32), conn_w=np.zeros(n["n_conn"], np.int32))
+        h = A.KfStoreHost(*(n[k] for k in self.COUNTS))
+        for k, v in a.items():
+            setattr(h, k, v.ctypes.data)
+        self.ctx.check(lib().lorb_kf_store_read(self._p, C.byref(h)), "lorb_kf_store_read")
+        out = dict(n)
+        out.update({k: a[k] for k in self._COLS})
+        out.update(kf_bad=a["kf_bad"], obs=_uncsr(a["obs_off"], a["obs_kf"]), kf_slots=_uncsr(a["kf_slot_off"], a["kf_slot_point"]),
+                   cov=_uncsr(a["cov_off"], a["cov_kf"]),
+                   conn=[dict(zip(k, w)) for k, w in zip(_uncsr(a["conn_off"], a["conn_kf"]), _uncsr(a["conn_off"], a["conn_w"]))],
+                   csr={k: a[k] for k in a if k.endswith("_off") or k in ("obs_kf", "kf_slot_point", "cov_kf", "conn_kf", "conn_w")})
+        return out
+
+    def fill(self, counts, value=ORB_SENTINEL):
+        """Every array of the view but is_bad / kf_bad set to `value` bytes past the given true counts (a dict as
+        counts() returns): what a test does before a call to see afterwards what the call wrote."""
+        start = dict(obs_off=counts["n_points"] + 1, obs_kf=counts["n_obs"], kf_slot_off=counts["n_kf"] + 1,
+                     kf_slot_point=counts["n_kf_slots"], cov_off=counts["n_kf"] + 1, cov_kf=counts["n_cov"])
+        for k, arr in self.arrays.items():
+            if k in ("is_bad", "kf_bad"):
+                continue
+            row = arr.nbytes // arr.shape[0]
+            at = start.get(k, counts["n_points"]) * row
+            if at < arr.nbytes:
+                self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
+                                                     C.c_size_t(arr.nbytes - at)), "memset")
+
+    def free(self):
+        if self._p:
+            lib().lorb_kf_store_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def keyframe_insert(ctx, store, fp, cur, cur_slots, slot_gid, cur_pose, record, n_max_cur=None, d_src_status=None,
+                    gate=A.LORB_KF_GATE_RATIO, refer_kf=None, update_record=None):
+    """lorb_kf_store_insert_dev enqueued and nothing else: the current frame as a keyframe of a KeyframeStore --
+    AddKeyFrame's gate and new points, ProcessNewFrames' observations, UpdateConnections.  cur: a DeviceFrame
+    (counts[0], the left x, y, octave, desc and depth are read); cur_pose: a DeviceBlock of A.FramePose; record: a
+    device buffer for the A.KfInsertResult; d_src_status: a device address or None; refer_kf: the refer_kf_word
+    or None; update_record: this frame's local-map record (DeviceArray) or None."""
+    fps = A.make_frame_params(fp)
+    nc = cur_slots.n_max if n_max_cur is None else int(n_max_cur)
+    ctx.check(lib().lorb_kf_store_insert_dev(
+        ctx.handle, store._p, C.byref(fps), C.byref(cur.out), C.c_int32(nc), C.byref(cur_slots.c), slot_gid.ptr, cur_pose.ptr,
+        C.c_void_p(d_src_status) if d_src_status else None, C.c_int32(gate), refer_kf.ptr if refer_kf is not None else None,
+        update_record.ptr if update_record is not None else None, record.ptr), "lorb_kf_store_insert_dev")
+
+
+def keyframe_insert_result(record):
+    """The A.KfInsertResult in a device record buffer (waits for the stream)."""
+    return A.KfInsertResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfInsertResult)])
+
+
 def Tcw_to_pose(Tcw):
     """lorb_Tcw_to_pose: (rvec, tvec) float32 of a 4 x 4 pose (cv::Rodrigues matrix -> vector; host)."""
     T, r, t = A.f32(Tcw).reshape(16), np.zeros(3, np.float32), np.zeros(3, np.float32)

@@ -1153,6 +1153,119 @@ int lorb_kf_store_insert_dev(lorb_ctx* ctx, lorb_kf_store* store, const lorb_fra
                              int32_t gate, int32_t* d_refer_kf, lorb_local_map_result* d_update,
                              lorb_kf_insert_result* d_result);
 
+/* ----------------------------------------------------------------------------------------
+ * The store's geometry, and BA::LocalPoseOptimization(mpCurrFrame) (src/bundle_adjust.cpp:207-330, call site
+ * src/local_mapping.cpp:32) fed straight from the store: tracker -> keyframe -> local BA -> refined poses and
+ * points in the store the next frame's lorb_local_map_update_dev reads.
+ *
+ * Geometry.  Beside the arrays of lorb_kf_store_host the store keeps, at capacity and at addresses that never
+ * change:
+ *   kf_pose      max_kf x 6 float        mRvec | mTvec of each keyframe
+ *   kf_slot_uv   max_kf_slots x 2 float  GetKp2d(j) of each keyframe slot, parallel to kf_slot_point (the
+ *                                        observation source include/lorb/adapters.hpp uses for a13)
+ *   obs_slot     max_obs int32           parallel to obs_kf: the slot of point p in keyframe obs_kf[o]
+ *                                        (mObservations[f], the it->second of src/bundle_adjust.cpp:273-296)
+ * INVARIANT: kf_slot_point[kf_slot_off[f] + obs_slot[o]] == p for every observation o of p in f = obs_kf[o].
+ * lorb_kf_store_insert_dev maintains them for keyframe K (still six launches, no wait, no copy): kf_pose[K] = the
+ * bits of d_cur_pose->pose; K's uv row = the frame's left x, y of the slots j < n_cur; obs_slot of the observation
+ * added to a held point = the lowest slot that holds it; obs_slot of a new point's observation = the slot that
+ * adopted or created it; obs_slot moves with obs_kf when the observation CSR is rebuilt.  Nothing at or past a new
+ * true count is written in these arrays either.
+ * lorb_kf_store_create_geom is lorb_kf_store_create with the geometry of the initial keyframes (n_kf, n_kf_slots,
+ * n_obs must equal init's; init NULL: all three 0).  It checks the invariant on the host -- every obs_slot inside
+ * its keyframe's row and pointing back at its point -- and returns LORB_E_INVALID with a message naming the
+ * offending entry.  A store made by lorb_kf_store_create with n_kf > 0 has no geometry for its initial keyframes:
+ * the calls below refuse it with LORB_E_INVALID.  An empty store is complete by construction.
+ * lorb_kf_store_geom_read waits and copies the true rows of every non-NULL member (the n_* fields are the
+ * CAPACITIES of the caller's arrays; LORB_E_INVALID when one is below its true count).
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_kf_store_geom_host {
+  int32_t n_kf, n_kf_slots, n_obs;   /* create: must equal init's; read: capacities */
+  float* kf_pose;                    /* n_kf x 6 */
+  float* kf_slot_uv;                 /* n_kf_slots x 2 */
+  int32_t* obs_slot;                 /* n_obs */
+} lorb_kf_store_geom_host;
+int lorb_kf_store_create_geom(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_store_host* init,
+                              const lorb_kf_store_geom_host* geom, lorb_kf_store** out);
+int lorb_kf_store_geom_read(lorb_kf_store* store, const lorb_kf_store_geom_host* out);   /* waits */
+/* the device arrays themselves, the n_* fields their capacities (no wait; the pointers never change) */
+int lorb_kf_store_geom_view(const lorb_kf_store* store, lorb_kf_store_geom_host* out);
+
+#define LORB_KF_BA_MAX_LOCAL 128   /* local frames of one window: the device plans' camera limit */
+typedef struct lorb_kf_ba_result {   /* device memory, like every record of the chain */
+  int32_t status;        /* 0; 1: source status or kf outside the store; 2: more than 128 local frames; 3: no points
+                            or no observations; 4: a point with 256 or more usable observations */
+  int32_t kf;
+  int32_t n_poses, n_fixed, n_points, n_obs;   /* the window */
+  int32_t n_cov_bad;       /* bad covisible frames skipped (:215-217) */
+  int32_t n_obs_bad_kf;    /* observations skipped: the observing keyframe is bad (:278) */
+  int32_t n_obs_bad_slot;  /* observations skipped: a keyframe or slot outside the store (a damaged store) */
+  int32_t written;         /* 1: the solution was written back */
+} lorb_kf_ba_result;
+typedef struct lorb_kf_ba_window_host {   /* the last gathered window; n_*: the capacities of the caller's arrays */
+  int32_t n_poses, n_fixed, n_points, n_obs;
+  int32_t* local_kf;     /* n_poses: keyframe index of each optimised pose */
+  int32_t* fixed_kf;     /* n_fixed: keyframe index of each fixed pose */
+  int32_t* l2g;          /* n_points: store index of each window point */
+  float* pose_init;      /* n_poses x 6 */
+  float* fixed_pose;     /* n_fixed x 6 */
+  float* point_init;     /* n_points x 3 */
+  int32_t* obs_point;    /* n_obs */
+  int32_t* obs_frame;    /* n_obs: >= 0 optimised pose, -1 - j fixed pose j */
+  float* obs_uv;         /* n_obs x 2 */
+} lorb_kf_ba_window_host;
+
+/* lorb_kf_store_ba_gather_dev builds the window of keyframe *d_kf in the store's own device memory;
+ * lorb_kf_store_local_ba_dev does the same, solves it and writes the solution back into the store.  d_kf is a
+ * device word -- in the chain &d_insert_result->kf, so a refused insertion's -1 makes the call a no-op -- and
+ * d_src_status a nullable device word (&d_insert_result->status).  frame supplies fx, fy, cx, cy
+ * (pCurrFrame->mpCamera).  On the device, in this order, all index arithmetic integer, no result depending on the
+ * order atomics arrive in:
+ *   a. Status: *d_src_status != 0, or kf outside [0, true n_kf), stores status = 1 and NOTHING else.
+ *   b. Frames (:210-220): local[0] = kf (the reference does not ask whether it is bad), then the entries of kf's
+ *      covisibility row (cov_kf: the whole mvpOrderedKeyFrames, src/frame.cpp:729-732) in row order, skipping
+ *      kf_bad ones (counted in n_cov_bad).  An entry outside [0, n_kf), equal to kf, or already listed is skipped.
+ *      More than LORB_KF_BA_MAX_LOCAL local frames stores status = 2 and nothing else.
+ *   c. Points (:224-241): over the local frames in list order and each frame's slots in slot order, a point index
+ *      that is not -1 and not is_bad enters at its first appearance: l2g[i].
+ *   d. Observations (:270-303): window point i's list in list order (ascending keyframe index = std::map<Frame*,
+ *      size_t> order).  A bad keyframe is skipped (:278, n_obs_bad_kf).  A local keyframe gives obs_frame = its
+ *      rank in the list of b; any other keyframe is a FIXED frame, -1 - j, the fixed frames numbered in ascending
+ *      keyframe index among those that occur (the numbering changes no arithmetic: a fixed pose enters only
+ *      through its own observations).  obs_uv = kf_slot_uv[kf_slot_off[f] + obs_slot].  An obs_kf outside
+ *      [0, n_kf) or an obs_slot outside its row is skipped (n_obs_bad_slot).  Observations come out sorted by
+ *      point.
+ *   e. Initial values: pose_init / fixed_pose = the kf_pose rows, point_init = the pos rows.  No points or no
+ *      observations: status = 3, nothing is solved and nothing is written back.  A window point with 256 or more
+ *      usable observations (the device plans' point group): status = 4, likewise.
+ *   f. Solve (lorb_kf_store_local_ba_dev): the window is handed in place, as a lorb_ba_window_dev, to a resident
+ *      device-built plan -- one per camera count in a small LRU with capacities that only grow, the slot logic
+ *      lorb_ba_solver uses -- then lorb_ba_plan_solve(opt).
+ *   g. Write-back (:317-329), one launch: kf_pose[local[i]] and pos[l2g[i]] take the solution rounded to float
+ *      (lorb_ba_plan_result_dev's conversion), whatever the termination, as in the reference; written = 1.
+ *      Nothing else in the store changes: normal, max / min distance, descriptors, flags, every list and every
+ *      count stay (SetWorldPos, src/map_point.cpp:52-55, sets the position only).
+ * Host side.  The gather is 6 kernel launches, then ONE copy of a 64-byte header (status and the window's counts,
+ * which pick the plan) and ONE wait.  lorb_kf_store_ba_gather_dev ends there.  lorb_kf_store_local_ba_dev goes on
+ * with the plan build (lorb_ba_plan_update_dev: its launches, one small readback, one wait), the captured LM
+ * graph and 1 write-back launch, all left enqueued; summary != NULL adds one copy and a final wait.  In steady
+ * state (a camera count already seen, sizes within the slot's capacities) the call allocates nothing.
+ * Returns LORB_OK for status 0, 1 and 3.  LORB_E_INVALID before anything is enqueued: a null required argument,
+ * a store of another ctx, a store without geometry.  LORB_E_UNSUPPORTED with the store untouched: status 2 or 4
+ * (no host-plan fallback is built).  Every path leaves the per-point scratch at rest: a failed call followed by
+ * a good one gives the window the good call alone gives.
+ * lorb_kf_ba_window_read waits and copies the last gathered window's true rows (counts as the record's) into
+ * every non-NULL member; LORB_E_INVALID when a capacity is below its count or no window was gathered.
+ * Out of scope: a host-array form or a C++ adapter; lorb_frame_pose blocks the caller holds for a reference
+ * keyframe (NOT updated by the write-back); running the BA on a second stream beside the tracker;
+ * MapPointsCulling / KeyFramesCulling; lorb_map_step_dev, which keeps its own ring map. */
+int lorb_kf_store_ba_gather_dev(lorb_ctx* ctx, lorb_kf_store* store, const lorb_frame_params* frame,
+                                const int32_t* d_kf, const int32_t* d_src_status, lorb_kf_ba_result* d_result);
+int lorb_kf_store_local_ba_dev(lorb_ctx* ctx, lorb_kf_store* store, const lorb_frame_params* frame,
+                               const int32_t* d_kf, const int32_t* d_src_status, const lorb_lm_options* opt,
+                               lorb_kf_ba_result* d_result, lorb_ba_summary* summary);
+int lorb_kf_ba_window_read(lorb_kf_store* store, const lorb_kf_ba_window_host* out);   /* waits */
+
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.
  * obs_frame[k] >= 0 : optimised pose index (PoseMPCost, src/bundle_adjust.cpp:293-301)

@@ -277,6 +277,27 @@ class KfInsertResult(C.Structure):  # lorb_kf_insert_result
                 ("n_connected", C.c_int32), ("n_points", C.c_int32), ("n_kf", C.c_int32), ("n_obs", C.c_int32)]
 
 
+LORB_KF_BA_MAX_LOCAL = 128
+
+
+class KfStoreGeomHost(C.Structure):  # lorb_kf_store_geom_host (host addresses)
+    _fields_ = [("n_kf", C.c_int32), ("n_kf_slots", C.c_int32), ("n_obs", C.c_int32), ("kf_pose", C.c_void_p),
+                ("kf_slot_uv", C.c_void_p), ("obs_slot", C.c_void_p)]
+
+
+class KfBaResult(C.Structure):  # lorb_kf_ba_result
+    _fields_ = [("status", C.c_int32), ("kf", C.c_int32), ("n_poses", C.c_int32), ("n_fixed", C.c_int32),
+                ("n_points", C.c_int32), ("n_obs", C.c_int32), ("n_cov_bad", C.c_int32), ("n_obs_bad_kf", C.c_int32),
+                ("n_obs_bad_slot", C.c_int32), ("written", C.c_int32)]
+
+
+class KfBaWindowHost(C.Structure):  # lorb_kf_ba_window_host (host addresses)
+    _fields_ = [("n_poses", C.c_int32), ("n_fixed", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32),
+                ("local_kf", C.c_void_p), ("fixed_kf", C.c_void_p), ("l2g", C.c_void_p), ("pose_init", C.c_void_p),
+                ("fixed_pose", C.c_void_p), ("point_init", C.c_void_p), ("obs_point", C.c_void_p), ("obs_frame", C.c_void_p),
+                ("obs_uv", C.c_void_p)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

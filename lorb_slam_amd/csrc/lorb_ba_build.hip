@@ -1073,6 +1073,25 @@ __global__ __launch_bounds__(256) void k_db_result(BaDev d, int C, int P, const 
     for (int k = i; k < 3 * P; k += gridDim.x * 256) pt_out[k] = (float)d.x_pt[cur][k];
 }
 
+// the same scattered into tables: pose c to row pose_row[c] of pose_tab, point i to row pt_row[i] of pt_tab (the
+// keyframe store's write-back, lorb_kfba.hip); *done = 1
+__global__ __launch_bounds__(256) void k_db_result_rows(BaDev d, int C, int P, const int* __restrict__ perm,
+                                                        const int* __restrict__ pose_row, float* __restrict__ pose_tab,
+                                                        const int* __restrict__ pt_row, float* __restrict__ pt_tab,
+                                                        int* __restrict__ done) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int cur = d.st[0].cur;
+  if (i < 6 * C) {
+    const int c = i / 6, q = i - 6 * c;
+    pose_tab[6 * (size_t)pose_row[c] + q] = (float)d.x_pose[cur][6 * perm[c] + q];
+  }
+  for (int k = i; k < 3 * P; k += gridDim.x * 256) {
+    const int r = k / 3;
+    pt_tab[3 * (size_t)pt_row[r] + (k - 3 * r)] = (float)d.x_pt[cur][k];
+  }
+  if (i == 0) *done = 1;
+}
+
 // the same in double (the Ceres parameter blocks after Solve) plus the summary, into one buffer for
 // one D2H copy: [poses 6C (caller order) | points 3P | iterations, successful steps, termination,
 // initial cost, final cost]
@@ -1689,6 +1708,15 @@ int ba_plan_result_ring_dev(lorb_ba_plan* P, float* ring, int R, int t0, float* 
   if (!P || !P->devb || !ring || R < 1) return LORB_E_INVALID;
   hipLaunchKernelGGL(k_db_result, result_grid(P), dim3(256), 0, P->ctx->stream, P->dev, P->Ctot, P->Ptot,
                      P->devb->perm, (float*)nullptr, d_point_out, ring, R, t0);
+  LORB_CHECK_LAUNCH(P->ctx);
+  return LORB_OK;
+}
+
+int ba_plan_result_rows_dev(lorb_ba_plan* P, const int* pose_row, float* pose_tab, const int* pt_row, float* pt_tab,
+                            int* done) {
+  if (!P || !P->devb || !pose_row || !pose_tab || !pt_row || !pt_tab || !done) return LORB_E_INVALID;
+  hipLaunchKernelGGL(k_db_result_rows, result_grid(P), dim3(256), 0, P->ctx->stream, P->dev, P->Ctot, P->Ptot,
+                     P->devb->perm, pose_row, pose_tab, pt_row, pt_tab, done);
   LORB_CHECK_LAUNCH(P->ctx);
   return LORB_OK;
 }

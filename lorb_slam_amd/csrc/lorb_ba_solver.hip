@@ -16,22 +16,20 @@
 // device build ignores.  Windows the device plans do not take (no cameras / points / observations,
 // a point with kGB or more observations) run through lorb_ba_local (the host-built plan on the
 // same GPU kernels): there is no CPU path.
+//
+// The resident plans -- one per camera count, LRU, grow-only capacities -- are lorb::PlanSlots
+// (lorb_ba_slots.h), implemented at the end of the anonymous part of this file; the keyframe store's
+// local BA (lorb_kfba.hip) keeps its plans through the same interface.
 #include <algorithm>
 
+#include "lorb_ba_slots.h"
 #include "lorb_internal.h"
 
 namespace {
 
-constexpr int kSlots = 4;
-
-struct Slot {
-  int C = -1, F_cap = 0, P_cap = 0, K_cap = 0;
-  lorb_ba_plan* plan = nullptr;
-  unsigned char* d_in = nullptr;  // packed window (counts | pose | fixed | point | obs_point | obs_frame | uv)
-  size_t in_bytes = 0;
-  double* d_out = nullptr;        // 6C + 3 P_cap + 5
-  unsigned long long last_use = 0;
-};
+// a slot's blocks here: d_in the packed window (counts | pose | fixed | point | obs_point | obs_frame | uv),
+// d_out 6C + 3 P_cap + 5 doubles
+using Slot = lorb::PlanSlot;
 
 inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 
@@ -53,32 +51,20 @@ struct Layout {
 
 struct lorb_ba_solver {
   lorb_ctx* ctx = nullptr;
-  Slot slot[kSlots];
-  unsigned long long clock = 0;
+  lorb::PlanSlots slots;
   unsigned char* h_in = nullptr; size_t h_in_sz = 0;    // pinned staging
   double* h_out = nullptr; size_t h_out_n = 0;
-  int creations = 0, last_fallback = 0, last_slot = -1;
+  int last_fallback = 0, last_slot = -1;
   bool sorted = false;  // the current window's observations are sorted by point
   ~lorb_ba_solver() {
     if (ctx) (void)hipStreamSynchronize(ctx->stream);
-    for (Slot& s : slot) {
-      if (s.plan) (void)lorb_ba_plan_destroy(s.plan);
-      if (s.d_in) (void)hipFree(s.d_in);
-      if (s.d_out) (void)hipFree(s.d_out);
-    }
+    slots.release_all();
     if (h_in) (void)hipHostFree(h_in);
     if (h_out) (void)hipHostFree(h_out);
   }
 };
 
 namespace {
-
-void release(Slot& s) {
-  if (s.plan) (void)lorb_ba_plan_destroy(s.plan);
-  if (s.d_in) (void)hipFree(s.d_in);
-  if (s.d_out) (void)hipFree(s.d_out);
-  s = Slot{};
-}
 
 int pinned_grow(lorb_ba_solver* S, size_t in_bytes, size_t out_n) {
   lorb_ctx* ctx = S->ctx;
@@ -99,39 +85,12 @@ int pinned_grow(lorb_ba_solver* S, size_t in_bytes, size_t out_n) {
   return LORB_OK;
 }
 
-// the slot for C cameras with room for F fixed rows, P points, K observations (fresh = no plan yet)
-int pick_slot(lorb_ba_solver* S, int C, int F, int P, int K, Slot** out) {
-  lorb_ctx* ctx = S->ctx;
-  Slot* hit = nullptr;
-  for (Slot& s : S->slot)
-    if (s.C == C) hit = &s;
-  if (hit && (hit->F_cap < F || hit->P_cap < P || hit->K_cap < K)) {  // outgrown: rebuild larger
-    LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int f = std::max(hit->F_cap, F), p = std::max(hit->P_cap, P), k = std::max(hit->K_cap, K);
-    release(*hit);
-    hit->F_cap = f + f / 2; hit->P_cap = p + p / 2; hit->K_cap = k + k / 2;
-  }
-  if (!hit) {
-    Slot* lru = &S->slot[0];
-    for (Slot& s : S->slot) {
-      if (s.C < 0) { lru = &s; break; }
-      if (s.last_use < lru->last_use) lru = &s;
-    }
-    if (lru->C >= 0) {
-      LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      release(*lru);
-    }
-    hit = lru;
-    hit->F_cap = std::max(F + F / 2, 8); hit->P_cap = std::max(P + P / 4, 64); hit->K_cap = std::max(K + K / 4, 256);
-  }
-  if (!hit->d_in) {
-    hit->C = C;
-    hit->in_bytes = Layout(C, hit->F_cap, hit->P_cap, hit->K_cap).end;
-    LORB_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&hit->d_in), hit->in_bytes));
-    LORB_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&hit->d_out), sizeof(double) * (6 * (size_t)C + 3 * (size_t)hit->P_cap + 5)));
-  }
-  hit->last_use = ++S->clock;
-  *out = hit;
+// the slot's blocks, allocated when the slot is fresh
+int slot_blocks(lorb_ctx* ctx, Slot* s) {
+  if (s->d_in) return LORB_OK;
+  s->in_bytes = Layout(s->C, s->F_cap, s->P_cap, s->K_cap).end;
+  LORB_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&s->d_in), s->in_bytes));
+  LORB_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&s->d_out), sizeof(double) * (6 * (size_t)s->C + 3 * (size_t)s->P_cap + 5)));
   return LORB_OK;
 }
 
@@ -147,6 +106,73 @@ int solve_fallback(lorb_ba_solver* S, const lorb_ba_window* w, const lorb_lm_opt
 }
 
 }  // namespace
+
+namespace lorb {
+
+void PlanSlots::release(PlanSlot& s) {
+  if (s.plan) (void)lorb_ba_plan_destroy(s.plan);
+  if (s.d_in) (void)hipFree(s.d_in);
+  if (s.d_out) (void)hipFree(s.d_out);
+  s = PlanSlot{};
+}
+
+void PlanSlots::release_all() {
+  for (PlanSlot& s : slot) release(s);
+}
+
+int PlanSlots::resident() const {
+  int n = 0;
+  for (const PlanSlot& s : slot) n += s.plan != nullptr;
+  return n;
+}
+
+int PlanSlots::pick(lorb_ctx* ctx, int C, int F, int P, int K, PlanSlot** out, int F_max, int P_max, int K_max) {
+  PlanSlot* hit = nullptr;
+  for (PlanSlot& s : slot)
+    if (s.C == C) hit = &s;
+  if (hit && (hit->F_cap < F || hit->P_cap < P || hit->K_cap < K)) {  // outgrown: rebuild larger
+    LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int f = std::max(hit->F_cap, F), p = std::max(hit->P_cap, P), k = std::max(hit->K_cap, K);
+    release(*hit);
+    hit->F_cap = f + f / 2; hit->P_cap = p + p / 2; hit->K_cap = k + k / 2;
+  } else if (!hit) {
+    PlanSlot* lru = &slot[0];
+    for (PlanSlot& s : slot) {
+      if (s.C < 0) { lru = &s; break; }
+      if (s.last_use < lru->last_use) lru = &s;
+    }
+    if (lru->C >= 0) {
+      LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      release(*lru);
+    }
+    hit = lru;
+    hit->F_cap = std::max(F + F / 2, 8); hit->P_cap = std::max(P + P / 4, 64); hit->K_cap = std::max(K + K / 4, 256);
+  }
+  if (hit->C < 0) {  // fresh: the capacities under the owner's limits
+    if (F_max > 0) hit->F_cap = std::max(std::min(hit->F_cap, F_max), F);
+    if (P_max > 0) hit->P_cap = std::max(std::min(hit->P_cap, P_max), P);
+    if (K_max > 0) hit->K_cap = std::max(std::min(hit->K_cap, K_max), K);
+    hit->C = C;
+  }
+  hit->last_use = ++clock;
+  *out = hit;
+  return LORB_OK;
+}
+
+int PlanSlots::build(lorb_ctx* ctx, PlanSlot* s, const lorb_ba_window_dev* w, bool sorted) {
+  if (!s->plan) {
+    const int rc = lorb_ba_plan_create_dev(ctx, w, &s->plan);
+    if (rc == LORB_OK) {
+      creations++;
+      ba_plan_sorted_hint(s->plan, sorted);
+    }
+    return rc;
+  }
+  ba_plan_sorted_hint(s->plan, sorted);
+  return lorb_ba_plan_update_dev(s->plan, w);
+}
+
+}  // namespace lorb
 
 extern "C" {
 
@@ -172,8 +198,9 @@ int lorb_ba_solver_solve(lorb_ba_solver* S, const lorb_ba_window* w, const lorb_
   S->last_fallback = 0;
   if (C == 0 || P == 0 || K == 0) return solve_fallback(S, w, opt, pose_out, point_out, summary);
   Slot* sl = nullptr;
-  LORB_TRY(pick_slot(S, C, F, P, K, &sl));
-  S->last_slot = (int)(sl - S->slot);
+  LORB_TRY(S->slots.pick(ctx, C, F, P, K, &sl));
+  LORB_TRY(slot_blocks(ctx, sl));
+  S->last_slot = (int)(sl - S->slots.slot);
   const Layout L(C, sl->F_cap, P, K);
   const size_t out_n = 6 * (size_t)C + 3 * (size_t)P + 5;
   LORB_TRY(pinned_grow(S, L.end, out_n));
@@ -219,22 +246,15 @@ int lorb_ba_solver_solve(lorb_ba_solver* S, const lorb_ba_window* w, const lorb_
   wd.d_obs_frame = reinterpret_cast<const int32_t*>(sl->d_in + L.ofr);
   wd.d_obs_uv = reinterpret_cast<const float*>(sl->d_in + L.uv);
   // 2. the device plan build (one readback)
-  int rc;
-  if (!sl->plan) {
-    rc = lorb_ba_plan_create_dev(ctx, &wd, &sl->plan);
-    if (rc == LORB_OK) S->creations++;
-  } else {
-    lorb::ba_plan_sorted_hint(sl->plan, S->sorted);
-    rc = lorb_ba_plan_update_dev(sl->plan, &wd);
-  }
+  const int rc = S->slots.build(ctx, sl, &wd, S->sorted);
   if (rc == LORB_E_UNSUPPORTED) {
     // a point with more observations than a device plan's point group holds: the host-built plan
     // takes it (a point observed twice by one camera is an error in both builders)
     LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (!sl->plan) release(*sl);
+    if (!sl->plan) S->slots.release(*sl);
     return solve_fallback(S, w, opt, pose_out, point_out, summary);
   }
-  if (rc != LORB_OK && !sl->plan) release(*sl);
+  if (rc != LORB_OK && !sl->plan) S->slots.release(*sl);
   LORB_TRY(rc);
   // 3. LM (captured graph)  4. result + summary, one copy
   LORB_TRY(lorb_ba_plan_solve(sl->plan, opt));
@@ -255,12 +275,11 @@ int lorb_ba_solver_solve(lorb_ba_solver* S, const lorb_ba_window* w, const lorb_
 
 int lorb_ba_solver_info(lorb_ba_solver* S, int32_t* info, int32_t n) {
   if (!S || !info || n < 0) return LORB_E_INVALID;
-  int resident = 0;
-  for (const Slot& s : S->slot) resident += s.plan != nullptr;
+  const int resident = S->slots.resident();
   int32_t pinfo[8] = {0, -1, 0, 0, 0, 0, 0, 0};
-  if (!S->last_fallback && S->last_slot >= 0 && S->slot[S->last_slot].plan)
-    LORB_TRY(lorb_ba_plan_info(S->slot[S->last_slot].plan, pinfo, 8));
-  const int32_t v[6] = {resident, S->creations, S->last_fallback, pinfo[0], pinfo[1], pinfo[7]};
+  if (!S->last_fallback && S->last_slot >= 0 && S->slots.slot[S->last_slot].plan)
+    LORB_TRY(lorb_ba_plan_info(S->slots.slot[S->last_slot].plan, pinfo, 8));
+  const int32_t v[6] = {resident, S->slots.creations, S->last_fallback, pinfo[0], pinfo[1], pinfo[7]};
   for (int i = 0; i < n && i < 6; ++i) info[i] = v[i];
   return LORB_OK;
 }
@@ -268,8 +287,8 @@ int lorb_ba_solver_info(lorb_ba_solver* S, int32_t* info, int32_t n) {
 int lorb_ba_solver_trace(lorb_ba_solver* S, lorb_lm_iteration* out, int32_t cap, int32_t* n_out) {
   if (!S || !n_out) return LORB_E_INVALID;
   *n_out = 0;
-  if (S->last_fallback || S->last_slot < 0 || !S->slot[S->last_slot].plan) return LORB_OK;
-  return lorb_ba_plan_trace(S->slot[S->last_slot].plan, 0, out, cap, n_out);
+  if (S->last_fallback || S->last_slot < 0 || !S->slots.slot[S->last_slot].plan) return LORB_OK;
+  return lorb_ba_plan_trace(S->slots.slot[S->last_slot].plan, 0, out, cap, n_out);
 }
 
 int lorb_ba_solver_destroy(lorb_ba_solver* S) {

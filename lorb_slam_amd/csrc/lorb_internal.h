@@ -116,6 +116,10 @@ int ba_plan_result64_dev(lorb_ba_plan* P, double* d_out);
 // the same as lorb_ba_plan_result_dev with the poses written into a keyframe ring (pose c of the
 // window to slot (t0 + c) mod R, 6 floats each) instead of a pose array
 int ba_plan_result_ring_dev(lorb_ba_plan* P, float* ring, int R, int t0, float* d_point_out);
+// the same conversion scattered into tables: pose c of the window to row pose_row[c] of pose_tab (6 floats), point
+// i to row pt_row[i] of pt_tab (3 floats); *done = 1.  One launch.  All device pointers.
+int ba_plan_result_rows_dev(lorb_ba_plan* P, const int* pose_row, float* pose_tab, const int* pt_row, float* pt_tab,
+                            int* done);
 // a device-built plan whose callers keep the observation slots sorted by point (stably, no unused
 // slots) builds without the counting sort; slots found out of order fall back to it (same result)
 void ba_plan_sorted_hint(lorb_ba_plan* P, bool sorted);

@@ -1,0 +1,68 @@
+// lorb_kfstore.h -- the keyframe store's object, shared by lorb_kfstore.hip (create / read / insertion) and
+// lorb_kfba.hip (the local bundle adjustment fed from the store).
+#pragma once
+
+#include "lorb_ba_slots.h"
+#include "lorb_internal.h"
+
+namespace lorb {
+
+// k_kf_head's verdict and the counts an insertion's later kernels read
+struct KfCtl {
+  int go;                // the insertion runs
+  int n, K, P, O, S;     // n_cur and the true counts on entry
+  int n_obs_add, n_new;  // observations added to old points; adopted + created points
+  int n_touch;           // neighbours whose weight map took K (touch[])
+  int fallback;          // the largest-count neighbour when no count reached 3, else -1
+  int n_connected;       // length of K's ordered list
+  int pad;
+};
+
+constexpr int kKfBaMaxLocal = 128;  // the device plans' camera limit
+constexpr int kKfBaNoFirst = 0x7f7f7f7f;  // ba_first[] at rest (a memset of 0x7f); above every sequence position
+
+// the header of the last gathered window (device; the host reads it once per call)
+struct KfBaHdr {
+  int status;            // the record's status
+  int go;                // the gather's later kernels run
+  int C, F, P, K;        // local frames, fixed frames, window points, observations
+  int maxk;              // the most usable observations of one window point
+  int T;                 // the local frames' slots, concatenated
+  int kf, n_kf, n_pts, n_obs_store, n_slots;  // K and the store's true counts on entry
+  int n_cov_bad, n_obs_bad_kf, n_obs_bad_slot;
+};
+
+}  // namespace lorb
+
+struct lorb_kf_store {
+  lorb_ctx* ctx = nullptr;
+  lorb_kf_store_caps cap{};
+  int max_cov = 0;                                          // max_kf * max_kf
+  int b_kf = 0, b_points = 0, b_obs = 0, b_slots = 0, b_cov = 0;  // the host's bounds on the true counts
+  bool geom_ok = false;  // kf_pose / kf_slot_uv / obs_slot cover every keyframe the store holds
+  lorb::Arena mem;
+  // the lorb_map_store arrays
+  float *pos = nullptr, *normal = nullptr, *max_dist = nullptr, *min_dist = nullptr;
+  uint8_t *desc = nullptr, *locked = nullptr, *is_bad = nullptr, *kf_bad = nullptr;
+  int *obs_off = nullptr, *obs_kf = nullptr, *kf_slot_off = nullptr, *kf_slot_point = nullptr;
+  int *cov_off = nullptr, *cov_kf = nullptr;
+  // the geometry: mRvec | mTvec per keyframe, GetKp2d per keyframe slot, the slot of every observation
+  float *kf_pose = nullptr, *kf_slot_uv = nullptr;
+  int* obs_slot = nullptr;
+  // weight maps and ordered lists: rows of stride max_kf
+  int *conn_n = nullptr, *conn_kf = nullptr, *conn_w = nullptr, *ord_n = nullptr, *ord_kf = nullptr;
+  int* cnt = nullptr;  // n_kf, n_points, n_obs, n_kf_slots, n_cov, n_conn
+  // scratch of an insertion
+  int *owner = nullptr, *off2 = nullptr, *kf2 = nullptr, *slot2 = nullptr, *tile_cnt = nullptr, *touch = nullptr;
+  lorb::KfCtl* ctl = nullptr;
+  // the local BA's window (lorb_kfba.hip): gathered on the device, read by the plan in place
+  lorb::KfBaHdr* ba_hdr = nullptr;
+  int *ba_first = nullptr;   // per point: the first sequence position that holds it; at rest between calls
+  int *ba_rank = nullptr, *ba_fixed_id = nullptr, *ba_fixed_flag = nullptr;  // per keyframe
+  int *ba_seq_off = nullptr;  // kKfBaMaxLocal + 1
+  int *ba_tile = nullptr, *ba_ocnt = nullptr, *ba_ooff = nullptr;
+  int *w_local = nullptr, *w_fixed = nullptr, *w_l2g = nullptr, *w_obs_point = nullptr, *w_obs_frame = nullptr;
+  float *w_pose = nullptr, *w_fixed_pose = nullptr, *w_point = nullptr, *w_uv = nullptr;
+  lorb::KfBaHdr* h_hdr = nullptr;  // pinned
+  lorb::PlanSlots plans;
+};

@@ -11,15 +11,20 @@
 // the ordered lists are kept as fixed-stride rows (stride max_kf) with a length per keyframe -- K is the largest
 // index, so AddConnection appends -- and the covisibility CSR of the view is compacted from the ordered rows.
 // The true counts live in cnt[6] on the device; the host object only carries upper bounds.
+// The geometry a bundle adjustment needs rides along: kf_pose (mRvec | mTvec per keyframe), kf_slot_uv (GetKp2d
+// per keyframe slot, parallel to kf_slot_point) and obs_slot (parallel to obs_kf: the slot of the point in that
+// keyframe, kf_slot_point[kf_slot_off[f] + obs_slot[o]] == p).  lorb_kfba.hip reads them.
 //
 // An insertion is six launches on the ctx stream:
 //   k_kf_head         one workgroup walking the slots: status, gate, the classification of every slot, the
 //                     lowest-slot owner of every held point (atomicMin on a per-point word that is at rest
 //                     between calls), the counts, the capacity verdict -- all before the first store write --
 //                     then the ordered numbering of the new points, their rows, the slots, the gids, K's slot
-//                     row, the counts, the refer words and the record
-//   k_kf_obs_count    owners per 1024-point tile; the observation CSR copied to scratch
-//   k_kf_obs_scatter  the CSR back with K appended to the owned points' lists, the new points' lists {K}
+//                     row with its keypoints, K's pose vector, the counts, the refer words and the record; a new
+//                     point's slot is left in owner[] for k_kf_obs_scatter
+//   k_kf_obs_count    owners per 1024-point tile; the observation CSR (keyframes and slots) copied to scratch
+//   k_kf_obs_scatter  the CSR back with K (and its owning slot) appended to the owned points' lists, the new
+//                     points' lists {K} with the slot that made them
 //   k_kf_connect      one workgroup: UpdateConnections' counter (k_lm_vote's pattern, kCountWin keyframes in LDS
 //                     at a time), K's weight map, the pairs, AddConnection's append to each neighbour's map
 //   k_kf_order        one workgroup per changed row: the (weight, index) keys sorted in LDS (bitonic)
@@ -29,6 +34,7 @@
 #include <algorithm>
 
 #include "lorb_internal.h"
+#include "lorb_kfstore.h"
 
 namespace {
 
@@ -39,36 +45,9 @@ constexpr int kSortMax = 4096;   // keys of one row sort in LDS = the largest ma
 constexpr int kNoOwner = 0x7f7f7f7f;  // owner[] at rest (a memset of 0x7f); above every slot index
 static_assert(kCountWin == kWalk && kTile == kWalk, "one counter / one point per thread");
 
-struct Ctl {
-  int go;                // k_kf_head's verdict: the insertion runs
-  int n, K, P, O, S;     // n_cur and the true counts on entry
-  int n_obs_add, n_new;  // observations added to old points; adopted + created points
-  int n_touch;           // neighbours whose weight map took K (touch[])
-  int fallback;          // the largest-count neighbour when no count reached 3, else -1
-  int n_connected;       // length of K's ordered list
-  int pad;
-};
+using Ctl = lorb::KfCtl;
 
 }  // namespace
-
-struct lorb_kf_store {
-  lorb_ctx* ctx = nullptr;
-  lorb_kf_store_caps cap{};
-  int max_cov = 0;                                          // max_kf * max_kf
-  int b_kf = 0, b_points = 0, b_obs = 0, b_slots = 0, b_cov = 0;  // the host's bounds on the true counts
-  lorb::Arena mem;
-  // the lorb_map_store arrays
-  float *pos = nullptr, *normal = nullptr, *max_dist = nullptr, *min_dist = nullptr;
-  uint8_t *desc = nullptr, *locked = nullptr, *is_bad = nullptr, *kf_bad = nullptr;
-  int *obs_off = nullptr, *obs_kf = nullptr, *kf_slot_off = nullptr, *kf_slot_point = nullptr;
-  int *cov_off = nullptr, *cov_kf = nullptr;
-  // weight maps and ordered lists: rows of stride max_kf
-  int *conn_n = nullptr, *conn_kf = nullptr, *conn_w = nullptr, *ord_n = nullptr, *ord_kf = nullptr;
-  int* cnt = nullptr;  // n_kf, n_points, n_obs, n_kf_slots, n_cov, n_conn
-  // scratch
-  int *owner = nullptr, *off2 = nullptr, *kf2 = nullptr, *tile_cnt = nullptr, *touch = nullptr;
-  Ctl* ctl = nullptr;
-};
 
 namespace {
 
@@ -93,6 +72,7 @@ struct HeadArgs {
   uint4* desc;
   uint8_t *locked, *is_bad, *kf_bad;
   int *kf_slot_off, *kf_slot_point;
+  float *kf_pose, *kf_slot_uv;
   int *cnt, *owner;
   Ctl* ctl;
   int* refer_kf;                  // or null
@@ -233,11 +213,15 @@ __global__ __launch_bounds__(kWalk) void k_kf_head(HeadArgs a) {
       }
       a.state[j] = LORB_SLOT_LOCKED;
       new_point(a, at, p, d0, d1, Ow, a.octave[j]);
+      a.owner[at] = j;  // the slot that adopted or created it: k_kf_obs_scatter's obs_slot, which puts the word to rest
       row = at;
     }
     if (kind != kHeldBad && kind != kObserve) a.gid[j] = row;  // the new index; -1 for a slot left EMPTY
     a.kf_slot_point[S + j] = row;
+    a.kf_slot_uv[2 * ((size_t)S + j)] = a.x[j];  // GetKp2d(j)
+    a.kf_slot_uv[2 * ((size_t)S + j) + 1] = a.y[j];
   }
+  if (t < 6) a.kf_pose[6 * (size_t)K + t] = a.pose->pose[t];  // mRvec | mTvec
   if (t == 0) {
     a.kf_bad[K] = 0;
     a.kf_slot_off[K + 1] = S + n;
@@ -254,7 +238,8 @@ __global__ __launch_bounds__(kWalk) void k_kf_head(HeadArgs a) {
 
 // owners per tile of the old points; the observation CSR as it stands into scratch
 __global__ __launch_bounds__(kTile) void k_kf_obs_count(const Ctl* ctl, const int* owner, const int* obs_off,
-                                                        const int* obs_kf, int* off2, int* kf2, int* tile_cnt) {
+                                                        const int* obs_kf, const int* obs_slot, int* off2, int* kf2,
+                                                        int* slot2, int* tile_cnt) {
   __shared__ int wsum[16];
   if (!ctl->go) return;
   const int P = ctl->P, O = ctl->O;
@@ -263,13 +248,17 @@ __global__ __launch_bounds__(kTile) void k_kf_obs_count(const Ctl* ctl, const in
   int tot;
   lorb::block_excl_scan_1024(p < P && owner[p] != kNoOwner, wsum, &tot);
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
-  for (long long o = p; o < O; o += (long long)gridDim.x * kTile) kf2[o] = obs_kf[o];
+  for (long long o = p; o < O; o += (long long)gridDim.x * kTile) {
+    kf2[o] = obs_kf[o];
+    slot2[o] = obs_slot[o];
+  }
 }
 
 // the CSR back: point p's list moves right by the owned points before it and takes K when p is owned; the new
 // points' lists are {K}.  Launched over the bound on n_points + n_max_cur + 1.
 __global__ __launch_bounds__(kTile) void k_kf_obs_scatter(const Ctl* ctl, int* owner, const int* off2, const int* kf2,
-                                                          const int* tile_cnt, int* obs_off, int* obs_kf) {
+                                                          const int* slot2, const int* tile_cnt, int* obs_off, int* obs_kf,
+                                                          int* obs_slot) {
   __shared__ int wsum[16];
   if (!ctl->go) return;
   const int t = threadIdx.x, b = blockIdx.x;
@@ -286,16 +275,24 @@ __global__ __launch_bounds__(kTile) void k_kf_obs_scatter(const Ctl* ctl, int* o
     const int lo = off2[p], hi = off2[p + 1], at = lo + before;
     if (before) {
       obs_off[p] = at;
-      for (int o = lo; o < hi; ++o) obs_kf[at + (o - lo)] = kf2[o];
+      for (int o = lo; o < hi; ++o) {
+        obs_kf[at + (o - lo)] = kf2[o];
+        obs_slot[at + (o - lo)] = slot2[o];
+      }
     }
     if (f) {
       obs_kf[at + (hi - lo)] = K;  // the largest index: last (src/map_point.cpp:133-139)
+      obs_slot[at + (hi - lo)] = owner[p];  // mObservations[K]: the lowest slot that holds p
       owner[p] = kNoOwner;
     }
   } else if (p <= P + n_new) {
     const int at = O + n_add + (p - P);
     obs_off[p] = at;
-    if (p < P + n_new) obs_kf[at] = K;
+    if (p < P + n_new) {
+      obs_kf[at] = K;
+      obs_slot[at] = owner[p];  // k_kf_head left the new point's slot here
+      owner[p] = kNoOwner;
+    }
   }
 }
 
@@ -489,18 +486,99 @@ const char* init_fault(const lorb_kf_store_caps& c, int max_cov, const lorb_kf_s
   return nullptr;
 }
 
+// the geometry of an init that init_fault passed: the counts are init's, and every observation's slot lies in
+// its keyframe's row and holds its point.  msg: the offending entry.
+bool geom_fault(const lorb_kf_store_host& h, const lorb_kf_store_geom_host& g, char* msg, size_t n) {
+  if (g.n_kf != h.n_kf || g.n_kf_slots != h.n_kf_slots || g.n_obs != h.n_obs) {
+    snprintf(msg, n, "counts %d / %d / %d differ from init's %d / %d / %d (kf, slots, obs)", g.n_kf, g.n_kf_slots, g.n_obs,
+             h.n_kf, h.n_kf_slots, h.n_obs);
+    return true;
+  }
+  if ((g.n_kf > 0 && !g.kf_pose) || (g.n_kf_slots > 0 && !g.kf_slot_uv) || (g.n_obs > 0 && !g.obs_slot)) {
+    snprintf(msg, n, "null array");
+    return true;
+  }
+  for (int p = 0; p < h.n_points; ++p)
+    for (int o = h.obs_off[p]; o < h.obs_off[p + 1]; ++o) {
+      const int f = h.obs_kf[o], s = g.obs_slot[o], len = h.kf_slot_off[f + 1] - h.kf_slot_off[f];
+      if (s < 0 || s >= len) {
+        snprintf(msg, n, "obs_slot[%d] = %d (point %d in keyframe %d) is outside the keyframe's %d slots", o, s, p, f, len);
+        return true;
+      }
+      if (h.kf_slot_point[h.kf_slot_off[f] + s] != p) {
+        snprintf(msg, n, "obs_slot[%d] = %d (point %d in keyframe %d) names a slot that holds %d", o, s, p, f,
+                 h.kf_slot_point[h.kf_slot_off[f] + s]);
+        return true;
+      }
+    }
+  return false;
+}
+
+int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_store_host* init,
+                 const lorb_kf_store_geom_host* geom, lorb_kf_store** out);
+
 }  // namespace
 
 extern "C" {
 
 int lorb_kf_store_destroy(lorb_kf_store* S) {
   if (!S) return LORB_E_INVALID;
+  if (S->ctx) (void)hipStreamSynchronize(S->ctx->stream);
+  S->plans.release_all();
+  if (S->h_hdr) (void)hipHostFree(S->h_hdr);
   S->mem.release();
   delete S;
   return LORB_OK;
 }
 
 int lorb_kf_store_create(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_store_host* init, lorb_kf_store** out) {
+  return create_store(ctx, caps, init, nullptr, out);
+}
+
+int lorb_kf_store_create_geom(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_store_host* init,
+                              const lorb_kf_store_geom_host* geom, lorb_kf_store** out) {
+  if (!ctx) return LORB_E_INVALID;
+  if (!out) return lorb::set_error(ctx, LORB_E_INVALID, "null output");
+  *out = nullptr;
+  if (!geom) return lorb::set_error(ctx, LORB_E_INVALID, "null geometry");
+  if (!init && (geom->n_kf || geom->n_kf_slots || geom->n_obs))
+    return lorb::set_error(ctx, LORB_E_INVALID, "geom: counts without an init");
+  return create_store(ctx, caps, init, geom, out);
+}
+
+int lorb_kf_store_geom_view(const lorb_kf_store* S, lorb_kf_store_geom_host* v) {
+  if (!S || !v) return LORB_E_INVALID;
+  *v = lorb_kf_store_geom_host{S->cap.max_kf, S->cap.max_kf_slots, S->cap.max_obs, S->kf_pose, S->kf_slot_uv, S->obs_slot};
+  return LORB_OK;
+}
+
+int lorb_kf_store_geom_read(lorb_kf_store* S, const lorb_kf_store_geom_host* g) {
+  if (!S || !g) return LORB_E_INVALID;
+  lorb_ctx* ctx = S->ctx;
+  hipStream_t st = ctx->stream;
+  int32_t cnt[6];
+  LORB_HIP(ctx, hipMemcpyAsync(cnt, S->cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  LORB_HIP(ctx, hipStreamSynchronize(st));
+  const int nk = cnt[0], no = cnt[2], ns = cnt[3];
+  if ((g->kf_pose && g->n_kf < nk) || (g->kf_slot_uv && g->n_kf_slots < ns) || (g->obs_slot && g->n_obs < no))
+    return lorb::set_error(ctx, LORB_E_INVALID, "an output array is smaller than the store's count (%d kf, %d slots, %d obs)", nk,
+                           ns, no);
+  auto down = [&](void* dst, const void* src, size_t bytes) {
+    return bytes && dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+  };
+  LORB_HIP(ctx, down(g->kf_pose, S->kf_pose, (size_t)nk * 24));
+  LORB_HIP(ctx, down(g->kf_slot_uv, S->kf_slot_uv, (size_t)ns * 8));
+  LORB_HIP(ctx, down(g->obs_slot, S->obs_slot, (size_t)no * 4));
+  LORB_HIP(ctx, hipStreamSynchronize(st));
+  return LORB_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_store_host* init,
+                 const lorb_kf_store_geom_host* geom, lorb_kf_store** out) {
   if (!ctx) return LORB_E_INVALID;
   if (!out) return lorb::set_error(ctx, LORB_E_INVALID, "null output");
   *out = nullptr;
@@ -514,6 +592,8 @@ int lorb_kf_store_create(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lo
   const int max_cov = caps->max_kf * caps->max_kf;
   if (init) {
     if (const char* why = init_fault(*caps, max_cov, *init)) return lorb::set_error(ctx, LORB_E_INVALID, "init: %s", why);
+    char msg[192];
+    if (geom && geom_fault(*init, *geom, msg, sizeof msg)) return lorb::set_error(ctx, LORB_E_INVALID, "geom: %s", msg);
   }
   lorb_kf_store* S = new (std::nothrow) lorb_kf_store;
   if (!S) return lorb::set_error(ctx, LORB_E_NOMEM, "out of host memory");
@@ -533,12 +613,24 @@ int lorb_kf_store_create(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lo
   A.add(&S->cnt, (size_t)8);
   A.add(&S->owner, np); A.add(&S->off2, np + 1); A.add(&S->kf2, no); A.add(&S->tile_cnt, np / kTile + 2);
   A.add(&S->touch, nk); A.add(&S->ctl, (size_t)1);
+  A.add(&S->kf_pose, nk * 6); A.add(&S->kf_slot_uv, ns * 2); A.add(&S->obs_slot, no); A.add(&S->slot2, no);
+  // the local BA's window and scratch (lorb_kfba.hip)
+  const size_t nl = (size_t)lorb::kKfBaMaxLocal;
+  A.add(&S->ba_hdr, (size_t)1); A.add(&S->ba_first, np); A.add(&S->ba_rank, nk); A.add(&S->ba_fixed_id, nk);
+  A.add(&S->ba_fixed_flag, nk); A.add(&S->ba_seq_off, nl + 1); A.add(&S->ba_tile, ns / kTile + 2);
+  A.add(&S->ba_ocnt, np); A.add(&S->ba_ooff, np + 1);
+  A.add(&S->w_local, nl); A.add(&S->w_fixed, nk); A.add(&S->w_l2g, np); A.add(&S->w_obs_point, no); A.add(&S->w_obs_frame, no);
+  A.add(&S->w_pose, nl * 6); A.add(&S->w_fixed_pose, nk * 6); A.add(&S->w_point, np * 3); A.add(&S->w_uv, no * 2);
   LORB_HIP(ctx, A.commit());
+  LORB_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&S->h_hdr), sizeof(lorb::KfBaHdr)));
+  memset(S->h_hdr, 0, sizeof(lorb::KfBaHdr));
+  S->h_hdr->status = 1;  // no window gathered yet
   hipStream_t st = ctx->stream;
   LORB_HIP(ctx, hipMemsetAsync(A.base, 0, A.total, st));
   LORB_HIP(ctx, hipMemsetAsync(S->is_bad, 1, np, st));  // rows past the true counts are inert
   LORB_HIP(ctx, hipMemsetAsync(S->kf_bad, 1, nk, st));
   LORB_HIP(ctx, hipMemsetAsync(S->owner, 0x7f, np * sizeof(int), st));
+  LORB_HIP(ctx, hipMemsetAsync(S->ba_first, 0x7f, np * sizeof(int), st));
   std::vector<int32_t> conn_n, conn_kf, conn_w, ord_n, ord_kf;  // alive until the wait below
   int32_t cnt[6] = {0, 0, 0, 0, 0, 0};
   if (init) {
@@ -577,15 +669,25 @@ int lorb_kf_store_create(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lo
       LORB_HIP(ctx, up(S->conn_kf, conn_kf.data(), hk * nk * 4)); LORB_HIP(ctx, up(S->conn_w, conn_w.data(), hk * nk * 4));
       LORB_HIP(ctx, up(S->ord_kf, ord_kf.data(), hk * nk * 4));
     }
+    if (geom) {
+      LORB_HIP(ctx, up(S->kf_pose, geom->kf_pose, hk * 24));
+      LORB_HIP(ctx, up(S->kf_slot_uv, geom->kf_slot_uv, (size_t)h.n_kf_slots * 8));
+      LORB_HIP(ctx, up(S->obs_slot, geom->obs_slot, (size_t)h.n_obs * 4));
+    }
     cnt[0] = h.n_kf; cnt[1] = h.n_points; cnt[2] = h.n_obs; cnt[3] = h.n_kf_slots; cnt[4] = h.n_cov; cnt[5] = h.n_conn;
     LORB_HIP(ctx, up(S->cnt, cnt, sizeof cnt));
   }
   LORB_HIP(ctx, hipStreamSynchronize(st));
   S->b_kf = cnt[0]; S->b_points = cnt[1]; S->b_obs = cnt[2]; S->b_slots = cnt[3]; S->b_cov = cnt[4];
+  S->geom_ok = geom != nullptr || cnt[0] == 0;  // an empty store is complete: every insertion writes its own
   guard.s = nullptr;
   *out = S;
   return LORB_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int lorb_kf_store_view(const lorb_kf_store* S, lorb_map_store* v) {
   if (!S || !v) return LORB_E_INVALID;
@@ -684,7 +786,8 @@ int lorb_kf_store_insert_dev(lorb_ctx* ctx, lorb_kf_store* S, const lorb_frame_p
   a.max_kf = S->cap.max_kf; a.max_points = S->cap.max_points; a.max_obs = S->cap.max_obs; a.max_kf_slots = S->cap.max_kf_slots;
   a.pos = S->pos; a.normal = S->normal; a.max_dist = S->max_dist; a.min_dist = S->min_dist;
   a.desc = reinterpret_cast<uint4*>(S->desc); a.locked = S->locked; a.is_bad = S->is_bad; a.kf_bad = S->kf_bad;
-  a.kf_slot_off = S->kf_slot_off; a.kf_slot_point = S->kf_slot_point; a.cnt = S->cnt; a.owner = S->owner; a.ctl = S->ctl;
+  a.kf_slot_off = S->kf_slot_off; a.kf_slot_point = S->kf_slot_point; a.kf_pose = S->kf_pose; a.kf_slot_uv = S->kf_slot_uv;
+  a.cnt = S->cnt; a.owner = S->owner; a.ctl = S->ctl;
   a.refer_kf = d_refer_kf; a.update = d_update; a.rec = d_result;
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(k_kf_head, dim3(1), dim3(kWalk), 0, st, a);
@@ -692,10 +795,10 @@ int lorb_kf_store_insert_dev(lorb_ctx* ctx, lorb_kf_store* S, const lorb_frame_p
   // grids from the bounds: the kernels read the true counts
   const size_t pb = (size_t)S->b_points, pb1 = std::min(pb + (size_t)nk, (size_t)S->cap.max_points);
   hipLaunchKernelGGL(k_kf_obs_count, dim3(lorb::ceil_div(pb + 1, kTile)), dim3(kTile), 0, st, S->ctl, S->owner, S->obs_off,
-                     S->obs_kf, S->off2, S->kf2, S->tile_cnt);
+                     S->obs_kf, S->obs_slot, S->off2, S->kf2, S->slot2, S->tile_cnt);
   LORB_CHECK_LAUNCH(ctx);
   hipLaunchKernelGGL(k_kf_obs_scatter, dim3(lorb::ceil_div(pb1 + 1, kTile)), dim3(kTile), 0, st, S->ctl, S->owner, S->off2,
-                     S->kf2, S->tile_cnt, S->obs_off, S->obs_kf);
+                     S->kf2, S->slot2, S->tile_cnt, S->obs_off, S->obs_kf, S->obs_slot);
   LORB_CHECK_LAUNCH(ctx);
   const int stride = S->cap.max_kf;
   hipLaunchKernelGGL(k_kf_connect, dim3(1), dim3(kWalk), 0, st, S->ctl, S->kf_slot_point, S->is_bad, S->obs_off, S->obs_kf,

@@ -426,19 +426,28 @@ class KeyframeStore:
     obs: per point its observing keyframes; kf_bad; kf_slots: per keyframe its slots' point indices; cov: per
     keyframe its ordered covisible keyframes; conn: per keyframe {keyframe: weight}, mConnectedKeyFrameWeights).
     .c is the A.MapStore view with the host's current BOUNDS as counts -- what local_map_update takes as
-    store.c; arrays: DeviceArray views of the store's own memory over its whole capacity (not to be freed)."""
+    store.c; arrays: DeviceArray views of the store's own memory over its whole capacity (not to be freed).
+    geom: None, or dict(kf_pose: n_kf x 6; kf_slot_uv: per keyframe its slots' (x, y); obs_slot: per point the slot
+    of each observation) -- lorb_kf_store_create_geom.  geometry: the views of kf_pose, kf_slot_uv and obs_slot,
+    kept apart from arrays."""
     COUNTS = ("n_kf", "n_points", "n_obs", "n_kf_slots", "n_cov", "n_conn")
     _COLS = dict(pos=(np.float32, 3), normal=(np.float32, 3), max_dist=(np.float32, 1), min_dist=(np.float32, 1),
                  desc=(np.uint8, 32), locked=(np.uint8, 1), is_bad=(np.uint8, 1))
 
-    def __init__(self, ctx, max_kf, max_points, max_obs, max_kf_slots, init=None):
+    def __init__(self, ctx, max_kf, max_points, max_obs, max_kf_slots, init=None, geom=None):
         self.ctx = ctx
+        self._last_ba_record, self._last_ba_camera = None, None
         self.caps = A.KfStoreCaps(int(max_kf), int(max_points), int(max_obs), int(max_kf_slots))
         self.max_cov = int(max_kf) * int(max_kf)
         self._p = C.c_void_p()
         h, keep = (None, None) if init is None else self._host(init)
-        ctx.check(lib().lorb_kf_store_create(ctx.handle, C.byref(self.caps), C.byref(h) if h is not None else None,
-                                             C.byref(self._p)), "lorb_kf_store_create")
+        if geom is None:
+            ctx.check(lib().lorb_kf_store_create(ctx.handle, C.byref(self.caps), C.byref(h) if h is not None else None,
+                                                 C.byref(self._p)), "lorb_kf_store_create")
+        else:
+            g, gkeep = self._geom_host(geom)
+            ctx.check(lib().lorb_kf_store_create_geom(ctx.handle, C.byref(self.caps), C.byref(h) if h is not None else None,
+                                                      C.byref(g), C.byref(self._p)), "lorb_kf_store_create_geom")
         v = self.view()
         cap = dict(n_points=self.caps.max_points, n_kf=self.caps.max_kf)
 
@@ -450,6 +459,28 @@ class KeyframeStore:
                            kf_bad=arr(v.kf_bad, cap["n_kf"], np.uint8), kf_slot_off=arr(v.kf_slot_off, cap["n_kf"] + 1, np.int32),
                            kf_slot_point=arr(v.kf_slot_point, self.caps.max_kf_slots, np.int32),
                            cov_off=arr(v.cov_off, cap["n_kf"] + 1, np.int32), cov_kf=arr(v.cov_kf, self.max_cov, np.int32))
+        self.geometry = self._geometry_views()
+
+    def _geometry_views(self):
+        """lorb_kf_store_geom_view: kf_pose, kf_slot_uv and obs_slot over their whole capacity (no wait)."""
+        g = A.KfStoreGeomHost()
+        self.ctx.check(lib().lorb_kf_store_geom_view(self._p, C.byref(g)), "lorb_kf_store_geom_view")
+        return dict(kf_pose=DeviceArrayView(self.ctx, g.kf_pose, (g.n_kf, 6), np.float32),
+                    kf_slot_uv=DeviceArrayView(self.ctx, g.kf_slot_uv, (g.n_kf_slots, 2), np.float32),
+                    obs_slot=DeviceArrayView(self.ctx, g.obs_slot, (g.n_obs,), np.int32))
+
+    @staticmethod
+    def _geom_host(g):
+        keep = dict(kf_pose=np.ascontiguousarray(g["kf_pose"], np.float32).reshape(-1, 6),
+                    kf_slot_uv=(np.concatenate([np.asarray(r, np.float32).reshape(-1, 2) for r in g["kf_slot_uv"]])
+                                if len(g["kf_slot_uv"]) else np.zeros((0, 2), np.float32)),
+                    obs_slot=_csr(g["obs_slot"])[1])
+        keep["kf_slot_uv"] = np.ascontiguousarray(keep["kf_slot_uv"], np.float32)
+        h = A.KfStoreGeomHost(len(keep["kf_pose"]), len(keep["kf_slot_uv"]), len(keep["obs_slot"]))
+        for k, a in keep.items():
+            setattr(h, k, a.ctypes.data)
+        h._keep = keep
+        return h, keep
 
     @staticmethod
     def _host(s):
@@ -506,6 +537,44 @@ class KeyframeStore:
                    csr={k: a[k] for k in a if k.endswith("_off") or k in ("obs_kf", "kf_slot_point", "cov_kf", "conn_kf", "conn_w")})
         return out
 
+    def read_geometry(self):
+        """lorb_kf_store_geom_read (waits): dict(kf_pose: n_kf x 6, kf_slot_uv: n_kf_slots x 2, obs_slot: n_obs) -- the
+        true rows, flat as the store keeps them."""
+        n = self.counts()
+        a = dict(kf_pose=np.zeros((n["n_kf"], 6), np.float32), kf_slot_uv=np.zeros((n["n_kf_slots"], 2), np.float32),
+                 obs_slot=np.zeros(n["n_obs"], np.int32))
+        h = A.KfStoreGeomHost(n["n_kf"], n["n_kf_slots"], n["n_obs"])
+        for k, v in a.items():
+            setattr(h, k, v.ctypes.data)
+        self.ctx.check(lib().lorb_kf_store_geom_read(self._p, C.byref(h)), "lorb_kf_store_geom_read")
+        return a
+
+    def fill_geometry(self, counts, value=ORB_SENTINEL):
+        """fill() for the geometry arrays: `value` bytes past the given true counts."""
+        start = dict(kf_pose=counts["n_kf"], kf_slot_uv=counts["n_kf_slots"], obs_slot=counts["n_obs"])
+        for k, arr in self.geometry.items():
+            at = start[k] * (arr.nbytes // arr.shape[0])
+            if at < arr.nbytes:
+                self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
+                                                     C.c_size_t(arr.nbytes - at)), "memset")
+
+    def ba_window(self, result=None):
+        """lorb_kf_ba_window_read (waits): the last gathered window as a dict -- local_kf, fixed_kf, l2g, pose_init,
+        fixed_pose, point_init, obs_point, obs_frame, obs_uv, and intr = (fx, fy, cx, cy) of the call that gathered it:
+        the dict Context.ba_local and the oracle take.
+        result: that call's A.KfBaResult (default: read from the record the last keyframe_local_ba was given)."""
+        r = result if result is not None else keyframe_ba_result(self._last_ba_record)
+        a = dict(local_kf=np.zeros(r.n_poses, np.int32), fixed_kf=np.zeros(r.n_fixed, np.int32), l2g=np.zeros(r.n_points, np.int32),
+                 pose_init=np.zeros((r.n_poses, 6), np.float32), fixed_pose=np.zeros((r.n_fixed, 6), np.float32),
+                 point_init=np.zeros((r.n_points, 3), np.float32), obs_point=np.zeros(r.n_obs, np.int32),
+                 obs_frame=np.zeros(r.n_obs, np.int32), obs_uv=np.zeros((r.n_obs, 2), np.float32))
+        h = A.KfBaWindowHost(r.n_poses, r.n_fixed, r.n_points, r.n_obs)
+        for k, v in a.items():
+            setattr(h, k, v.ctypes.data)
+        self.ctx.check(lib().lorb_kf_ba_window_read(self._p, C.byref(h)), "lorb_kf_ba_window_read")
+        a.update(self._last_ba_camera or {})
+        return a
+
     def fill(self, counts, value=ORB_SENTINEL):
         """Every array of the view but is_bad / kf_bad set to `value` bytes past the given true counts (a dict as
         counts() returns): what a test does before a call to see afterwards what the call wrote."""
@@ -545,6 +614,39 @@ def keyframe_insert(ctx, store, fp, cur, cur_slots, slot_gid, cur_pose, record, 
         ctx.handle, store._p, C.byref(fps), C.byref(cur.out), C.c_int32(nc), C.byref(cur_slots.c), slot_gid.ptr, cur_pose.ptr,
         C.c_void_p(d_src_status) if d_src_status else None, C.c_int32(gate), refer_kf.ptr if refer_kf is not None else None,
         update_record.ptr if update_record is not None else None, record.ptr), "lorb_kf_store_insert_dev")
+
+
+def keyframe_ba_record(ctx):
+    """A device buffer for an A.KfBaResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
+    return _sentinel(ctx, C.sizeof(A.KfBaResult) + ORB_GUARD, np.uint8)
+
+
+def keyframe_local_ba(ctx, store, fp, d_kf, record, d_src_status=None, opt=None, gather_only=False, summary=False):
+    """lorb_kf_store_local_ba_dev (gather_only: lorb_kf_store_ba_gather_dev): BA::LocalPoseOptimization of the
+    keyframe whose index is the device word at address d_kf, on a KeyframeStore -- the window gathered on the device,
+    solved by a resident plan, the solution written back into the store's kf_pose and pos rows.  d_kf /
+    d_src_status: device addresses (in the chain the kf and status words of an insertion's record); record: a
+    device buffer for the A.KfBaResult (keyframe_ba_record).  summary: wait for the solve and return its summary
+    dict (else None: the solve and the write-back stay enqueued)."""
+    fps = A.make_frame_params(fp)
+    store._last_ba_record = record
+    store._last_ba_camera = dict(intr=tuple(np.float32(fp[k]) for k in ("fx", "fy", "cx", "cy")))
+    src = C.c_void_p(d_src_status) if d_src_status else None
+    if gather_only:
+        ctx.check(lib().lorb_kf_store_ba_gather_dev(ctx.handle, store._p, C.byref(fps), C.c_void_p(d_kf), src, record.ptr),
+                  "lorb_kf_store_ba_gather_dev")
+        return None
+    opt = opt or A.LMOptions.default()
+    summ = A.BASummary() if summary else None
+    ctx.check(lib().lorb_kf_store_local_ba_dev(ctx.handle, store._p, C.byref(fps), C.c_void_p(d_kf), src, C.byref(opt),
+                                               record.ptr, C.byref(summ) if summ is not None else None),
+              "lorb_kf_store_local_ba_dev")
+    return summ.as_dict() if summ is not None else None
+
+
+def keyframe_ba_result(record):
+    """The A.KfBaResult in a device record buffer (waits for the stream)."""
+    return A.KfBaResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfBaResult)])
 
 
 def keyframe_insert_result(record):

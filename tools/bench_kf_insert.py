@@ -52,7 +52,8 @@ REFER_KF = 0
 EVERY = 10
 
 
-def build_arms(ctx, calls):
+def build_arms(ctx, calls, expose=None):
+    """expose: a dict that receives the scene's parts (tools/bench_kf_ba.py builds its arms from them)."""
     L, h = lib(), ctx.handle
     inserts = max(calls // EVERY, 1)  # INSERTS_PER_ROUND
     fp = synth.frame_params(width=COLS, height=ROWS)
@@ -217,6 +218,9 @@ def build_arms(ctx, calls):
             x.free()
         fb.close()
 
+    if expose is not None:
+        expose.update(fp=fp, fps=fps, init=init, caps=caps, bufs=bufs, frame=frame, insert=insert, static=static,
+                      lmap_static=lmap_static, keep=keep, opt=opt)
     base = dict(n_last=n_last, bound=BOUND, max_local=MAX_LOCAL, store_points=N_POINTS, store_keyframes=N_KF, caps=caps,
                 inserts_per_round=inserts, every=EVERY)
     return arms, one_insertion, info, base, cleanup

@@ -1258,13 +1258,162 @@ typedef struct lorb_kf_ba_window_host {   /* the last gathered window; n_*: the 
  * every non-NULL member; LORB_E_INVALID when a capacity is below its count or no window was gathered.
  * Out of scope: a host-array form or a C++ adapter; lorb_frame_pose blocks the caller holds for a reference
  * keyframe (NOT updated by the write-back); running the BA on a second stream beside the tracker;
- * MapPointsCulling / KeyFramesCulling; lorb_map_step_dev, which keeps its own ring map. */
+ * KeyFramesCulling (MapPointsCulling is lorb_kf_store_cull_dev below, enqueued in front of this call);
+ * lorb_map_step_dev, which keeps its own ring map. */
 int lorb_kf_store_ba_gather_dev(lorb_ctx* ctx, lorb_kf_store* store, const lorb_frame_params* frame,
                                 const int32_t* d_kf, const int32_t* d_src_status, lorb_kf_ba_result* d_result);
 int lorb_kf_store_local_ba_dev(lorb_ctx* ctx, lorb_kf_store* store, const lorb_frame_params* frame,
                                const int32_t* d_kf, const int32_t* d_src_status, const lorb_lm_options* opt,
                                lorb_kf_ba_result* d_result, lorb_ba_summary* summary);
 int lorb_kf_ba_window_read(lorb_kf_store* store, const lorb_kf_ba_window_host* out);   /* waits */
+
+/* ----------------------------------------------------------------------------------------
+ * The life of the store's points and LocalMapping::MapPointsCulling (src/local_mapping.cpp:82-108) on the store:
+ * the mapper step ProcessNewFrames -> MapPointsCulling -> BA::LocalPoseOptimization (src/local_mapping.cpp:24-36) as
+ * lorb_kf_store_insert_dev -> lorb_kf_store_cull_dev -> lorb_kf_store_local_ba_dev, each behind the other on the
+ * insertion's record words.
+ *
+ * Life state.  Beside its other arrays the store keeps, at capacity and at addresses that never change:
+ *   visible     max_points int32   MapPoint::mnVisible
+ *   found       max_points int32   MapPoint::mnFound
+ *   first_fid   max_points int32   MapPoint::mnFirstFId
+ *   recent      max_points uint8   1: the point is a member of LocalMapping::mvpRecentAddPoints
+ *   kf_fid      max_kf int32       Frame::mnId of each keyframe
+ *   frame word  one int32          the id of the frame the tracker last observed (lorb_kf_store_observe_dev)
+ * The reference's list is a FLAG per point here: a point's verdict depends on that point alone, and a second visit
+ * of a duplicate entry finds the point bad or gone, so the set of culled points and of remaining members is the
+ * list's.  A store from lorb_kf_store_create / _create_geom starts with visible = found = 1 (the MapPoint
+ * constructors, src/map_point.cpp:16-17,33-34), first_fid = 0, recent = 0 and kf_fid = 0 over its initial rows and
+ * a frame word of 0.
+ * lorb_kf_store_life_write waits and replaces the true rows by every non-NULL member: n_kf and n_points must EQUAL
+ * the true counts; visible < 1 or found < 0 is LORB_E_INVALID with a message naming the entry.
+ * lorb_kf_store_life_read waits and copies the true rows into every non-NULL member (the n_* fields are the
+ * CAPACITIES of the caller's arrays; LORB_E_INVALID when one is below its true count).  lorb_kf_store_life_view
+ * returns the device arrays themselves, the n_* fields their capacities, and lorb_kf_store_frame_word_view the
+ * address of the frame word (no wait; the pointers never change).
+ * lorb_kf_store_insert_dev maintains the state for keyframe K (still six launches, no wait, no copy): kf_fid[K] =
+ * the frame word; every new point, adopted or created, gets first_fid = the frame word and visible = found = 1;
+ * recent = 1 for CREATED points only (a created point already has K as an observation, so src/local_mapping.cpp:62-69
+ * pushes it; an adopted one gets AddObservation there and is not pushed) and for an old point K holds in two or
+ * more slots (the lowest slot adds the observation, every later slot finds IsInFrame true and pushes).  A held bad
+ * point changes nothing.  An adopted point's life before it had a store row is not tracked.  Nothing at or past a
+ * new true count is written.
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_kf_store_life_host {
+  int32_t n_kf, n_points;   /* write: must equal the true counts; read: capacities */
+  int32_t* visible;         /* n_points */
+  int32_t* found;           /* n_points */
+  int32_t* first_fid;       /* n_points */
+  uint8_t* recent;          /* n_points */
+  int32_t* kf_fid;          /* n_kf */
+} lorb_kf_store_life_host;
+int lorb_kf_store_life_write(lorb_kf_store* store, const lorb_kf_store_life_host* in);   /* waits */
+int lorb_kf_store_life_read(lorb_kf_store* store, const lorb_kf_store_life_host* out);   /* waits */
+int lorb_kf_store_life_view(const lorb_kf_store* store, lorb_kf_store_life_host* out);   /* no wait */
+int lorb_kf_store_frame_word_view(const lorb_kf_store* store, int32_t** d_word);         /* no wait */
+
+#define LORB_KF_FOUND_NEVER 0   /* the reference: IncreaseFound is never called, GetFoundRatio() is 1 / mnVisible */
+#define LORB_KF_FOUND_SLOTS 1   /* ORB-SLAM2's TrackLocalMap intent: every slot that holds a point after the local stage */
+typedef struct lorb_kf_observe_result {
+  int32_t status;      /* 0; 1: a bad count or source status, nothing else was written */
+  int32_t n_held;      /* increments of step c */
+  int32_t n_in_view;   /* increments of step d */
+  int32_t n_found;     /* increments of step e */
+} lorb_kf_observe_result;
+
+/* The tracker's two IncreaseVisible sites (src/visual_odometry.cpp:165,191) on the store.  Enqueued behind
+ * lorb_track_local_frames_dev and in front of lorb_local_map_ids_back_dev.  Host values: frame_id
+ * (mCurrFrame->mnId), n_max_cur, found_rule.  Device inputs: the frame (counts[0]), its slots (state), d_cur_slot_gid
+ * (still the gids lorb_local_map_update_dev left, bad held points already at -1), d_cur_slot_id (the local rows
+ * after the local stage), lmap (the lorb_local_map_view arrays: l2g and max_local are read), d_update (that
+ * frame's lorb_local_map_update_dev record: status and n_local are read on the device), d_in_view (the local
+ * stage's), d_local_status (nullable; in the chain the local stage's &d_result->status).  On the device, in this
+ * order:
+ *   a. Status: counts[0] negative or above n_max_cur, n_local negative or above max_local, *d_local_status != 0 or
+ *      d_update->status != 0 stores status = 1 in the record and NOTHING else -- the frame word included.
+ *   b. The frame word = frame_id.
+ *   c. Every slot j < n_cur with a gid in [0, true n_points): visible[g] += 1 (:153-171).  Per slot: a point in two
+ *      slots gets 2.
+ *   d. Every local row k < n_local with in_view[k] != 0 and l2g[k] inside the store: visible[l2g[k]] += 1 (:188-194).
+ *   e. found_rule.  LORB_KF_FOUND_NEVER (the reference): nothing.  LORB_KF_FOUND_SLOTS: every slot that is non-EMPTY
+ *      after the stage adds 1 to found of the store point it holds -- l2g[lid] when lid = d_cur_slot_id[j] >= 0
+ *      (lid < n_local), else the slot's gid -- when that index is inside the store.  This is ORB-SLAM2's
+ *      TrackLocalMap intent; the reference does not do it.
+ *   f. The record.
+ * The increments are integer atomics: no result depends on the order they arrive in.  LORB_E_INVALID, before
+ * anything is enqueued: a null required argument, a store of another ctx, n_max_cur < 1, an unknown rule, a null
+ * array in d_cur / d_cur_slots / lmap.  Asynchronous on the ctx stream: 1 kernel launch, no stream synchronise, no
+ * device-to-host read and no host-to-device copy. */
+int lorb_kf_store_observe_dev(lorb_ctx* ctx, lorb_kf_store* store, int32_t frame_id, const lorb_frame_out* d_cur,
+                              int32_t n_max_cur, const lorb_frame_slots* d_cur_slots, const int32_t* d_cur_slot_gid,
+                              const int32_t* d_cur_slot_id, const lorb_local_map_arrays* lmap,
+                              const lorb_local_map_result* d_update, const uint8_t* d_in_view,
+                              const int32_t* d_local_status, int32_t found_rule, lorb_kf_observe_result* d_result);
+
+typedef struct lorb_kf_cull_params {   /* a host struct */
+  float min_found_ratio;   /* GetFoundRatio() below this culls (src/local_mapping.cpp:92) */
+  int32_t age_obs;         /* at this age in frame ids ... */
+  int32_t min_obs;         /* ... fewer observations than this culls (:98) */
+  int32_t age_out;         /* at this age the point leaves the list (:104) */
+} lorb_kf_cull_params;
+#define LORB_KF_CULL_REFERENCE { 0.25f, 2, 3, 3 }
+typedef struct lorb_kf_cull_result {   /* device memory, like every record of the chain */
+  int32_t status;          /* 0; 1: source status or kf outside the store, nothing else was written */
+  int32_t kf;
+  int32_t n_examined;      /* members of the list on entry */
+  int32_t n_bad_before;    /* verdict 1: already bad, left the list */
+  int32_t n_culled_ratio;  /* verdict 2 */
+  int32_t n_culled_obs;    /* verdict 3 */
+  int32_t n_aged_out;      /* verdict 4: left the list */
+  int32_t n_recent;        /* verdict 5: members left */
+  int32_t n_obs_removed;   /* observations of the culled points */
+  int32_t n_slots_erased;  /* keyframe slots set to -1 */
+  int32_t n_frame_slots_emptied;   /* slots of the tracker's frame made EMPTY */
+  int32_t n_obs_bad_slot;  /* observations of culled points whose keyframe or slot is outside the store or holds
+                              another point (a damaged store): skipped */
+  int32_t n_obs;           /* the store after the call */
+} lorb_kf_cull_result;
+
+/* MapPointsCulling() after ProcessNewFrames, with a real MapPoint::SetBadFlag (src/map_point.cpp:184-199).  Enqueued
+ * behind lorb_kf_store_insert_dev and in front of lorb_kf_store_local_ba_dev, with d_kf = &d_insert_result->kf and
+ * d_src_status = &d_insert_result->status (nullable) as the BA takes them: a refused insertion's -1 makes the call a
+ * no-op.  par is a host struct; LORB_KF_CULL_REFERENCE holds the reference's thresholds.  The group d_cur, n_max_cur,
+ * d_cur_slots, d_cur_slot_gid is the tracker's objects of the frame that became K: all given or all NULL.  The
+ * store must have its geometry (SetBadFlag needs obs_slot).  On the device, in this order:
+ *   a. Status: *d_src_status != 0, or kf outside [0, true n_kf), stores status = 1 and NOTHING else.
+ *   b. Verdicts.  cur = kf_fid[kf].  Every p < n_points with recent[p] is examined in the order of
+ *      include/lorb/local_mapping.hpp:66-71 (the reference's loop, src/local_mapping.cpp:85-106, without its
+ *      erase-then-increment fault):
+ *        1. is_bad[p]: it leaves the list.
+ *        2. (float)found / (float)visible < min_found_ratio: culled.
+ *        3. age = (uint32)(cur - first_fid[p]); age >= age_obs and the observation list shorter than min_obs: culled.
+ *        4. age >= age_out: it leaves the list.
+ *        5. Otherwise it stays.
+ *   c. SetBadFlag of every culled point: is_bad = 1 and recent = 0; for each of its observations (f, s) with f
+ *      inside the store, s inside f's row and kf_slot_point[kf_slot_off[f] + s] == p that entry becomes -1
+ *      (Frame::EraseMapPoint, src/frame.cpp:896-899; f bad or not), others are counted in n_obs_bad_slot and skipped;
+ *      its list is removed from obs_off / obs_kf / obs_slot: every later list moves left, order kept, and the true
+ *      n_obs drops.  Left as they are, as in the reference: locked, pos, normal, the distances, desc, the weight
+ *      maps, the ordered lists and cov_*.  Point rows are not reclaimed: indices stay stable.
+ *   d. With the frame group: every slot j < counts[0] whose gid names a point culled BY THIS CALL becomes EMPTY
+ *      with gid -1 (K's Frame is the tracker's frame in the reference).  A slot holding a point that was bad before
+ *      the call stays as it is.  counts[0] outside [0, n_max_cur]: no slot is touched.
+ *   e. The true counts and the record.
+ * When no point is culled the kernels after the verdicts return at once: the CSR is not rewritten.  The invariant
+ * kf_slot_point[kf_slot_off[f] + obs_slot[o]] == p holds after the call, so lorb_kf_store_ba_gather_dev and
+ * lorb_local_map_update_dev read the store as before: a culled point is bad, in no keyframe row and has no
+ * observation.  Nothing at or past a true count is written.  All counting is integer.  The per-point scratch mark
+ * is back at rest when the call ends, on every path.
+ * LORB_E_INVALID, before anything is enqueued: a null required argument, a store of another ctx, a store without
+ * geometry, a negative age or a NaN ratio, a frame group given in part (or n_max_cur < 1 with it).
+ * Asynchronous on the ctx stream: 4 kernel launches, no stream synchronise, no device-to-host read and no
+ * host-to-device copy.
+ * Out of scope: KeyFramesCulling (empty in the reference, src/local_mapping.cpp:110-113); reclaiming rows (point
+ * rows are not reclaimed); MapPoint::EraseObservation's own SetBadFlag at mnObs <= 2 (nothing in the chain erases a
+ * single observation); the life of an adopted point before it had a store row. */
+int lorb_kf_store_cull_dev(lorb_ctx* ctx, lorb_kf_store* store, const int32_t* d_kf, const int32_t* d_src_status,
+                           const lorb_kf_cull_params* par, const lorb_frame_out* d_cur, int32_t n_max_cur,
+                           const lorb_frame_slots* d_cur_slots, int32_t* d_cur_slot_gid, lorb_kf_cull_result* d_result);
 
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.

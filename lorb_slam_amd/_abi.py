@@ -298,6 +298,30 @@ class KfBaWindowHost(C.Structure):  # lorb_kf_ba_window_host (host addresses)
                 ("obs_uv", C.c_void_p)]
 
 
+LORB_KF_FOUND_NEVER, LORB_KF_FOUND_SLOTS = 0, 1
+LORB_KF_CULL_REFERENCE = (0.25, 2, 3, 3)  # min_found_ratio, age_obs, min_obs, age_out
+
+
+class KfStoreLifeHost(C.Structure):  # lorb_kf_store_life_host (host addresses)
+    _fields_ = [("n_kf", C.c_int32), ("n_points", C.c_int32), ("visible", C.c_void_p), ("found", C.c_void_p),
+                ("first_fid", C.c_void_p), ("recent", C.c_void_p), ("kf_fid", C.c_void_p)]
+
+
+class KfObserveResult(C.Structure):  # lorb_kf_observe_result
+    _fields_ = [("status", C.c_int32), ("n_held", C.c_int32), ("n_in_view", C.c_int32), ("n_found", C.c_int32)]
+
+
+class KfCullParams(C.Structure):  # lorb_kf_cull_params
+    _fields_ = [("min_found_ratio", C.c_float), ("age_obs", C.c_int32), ("min_obs", C.c_int32), ("age_out", C.c_int32)]
+
+
+class KfCullResult(C.Structure):  # lorb_kf_cull_result
+    _fields_ = [("status", C.c_int32), ("kf", C.c_int32), ("n_examined", C.c_int32), ("n_bad_before", C.c_int32),
+                ("n_culled_ratio", C.c_int32), ("n_culled_obs", C.c_int32), ("n_aged_out", C.c_int32), ("n_recent", C.c_int32),
+                ("n_obs_removed", C.c_int32), ("n_slots_erased", C.c_int32), ("n_frame_slots_emptied", C.c_int32),
+                ("n_obs_bad_slot", C.c_int32), ("n_obs", C.c_int32)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

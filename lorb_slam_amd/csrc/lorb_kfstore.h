@@ -1,5 +1,6 @@
-// lorb_kfstore.h -- the keyframe store's object, shared by lorb_kfstore.hip (create / read / insertion) and
-// lorb_kfba.hip (the local bundle adjustment fed from the store).
+// lorb_kfstore.h -- the keyframe store's object, shared by lorb_kfstore.hip (create / read / insertion),
+// lorb_kfba.hip (the local bundle adjustment fed from the store) and lorb_kfcull.hip (the points' life and
+// MapPointsCulling).
 #pragma once
 
 #include "lorb_ba_slots.h"
@@ -30,6 +31,35 @@ struct KfBaHdr {
   int T;                 // the local frames' slots, concatenated
   int kf, n_kf, n_pts, n_obs_store, n_slots;  // K and the store's true counts on entry
   int n_cov_bad, n_obs_bad_kf, n_obs_bad_slot;
+};
+
+// k_kf_cull_head's verdict and the counts a cull's later kernels read (lorb_kfcull.hip)
+struct KfCullCtl {
+  int go;           // the cull runs
+  int kf, cur;      // K and kf_fid[K]
+  int nk, P, O, S;  // the true counts on entry
+  int n_culled;     // points culled by this call: 0 makes the kernels after the verdicts return at once
+};
+
+// the points' life as one block of ints, so that a kernel takes one pointer: visible | found | first_fid | recent
+// (bytes) over max_points each, kf_fid over max_kf, the frame word; every part starts on a multiple of 64 ints
+struct KfLife {
+  int *visible, *found, *first_fid;
+  uint8_t* recent;
+  int *kf_fid, *frame_word;
+  __host__ __device__ static size_t pad(size_t n) { return (n + 63) & ~size_t(63); }
+  __host__ __device__ static size_t ints(int max_points, int max_kf) {
+    return 3 * pad((size_t)max_points) + pad(((size_t)max_points + 3) / 4) + pad((size_t)max_kf) + 64;
+  }
+  __host__ __device__ KfLife(int* base, int max_points, int max_kf) {
+    const size_t np = pad((size_t)max_points);
+    visible = base;
+    found = base + np;
+    first_fid = base + 2 * np;
+    recent = reinterpret_cast<uint8_t*>(base + 3 * np);
+    kf_fid = base + 3 * np + pad(((size_t)max_points + 3) / 4);
+    frame_word = kf_fid + pad((size_t)max_kf);
+  }
 };
 
 }  // namespace lorb
@@ -64,5 +94,12 @@ struct lorb_kf_store {
   int *w_local = nullptr, *w_fixed = nullptr, *w_l2g = nullptr, *w_obs_point = nullptr, *w_obs_frame = nullptr;
   float *w_pose = nullptr, *w_fixed_pose = nullptr, *w_point = nullptr, *w_uv = nullptr;
   lorb::KfBaHdr* h_hdr = nullptr;  // pinned
+  // the points' life (lorb_kfcull.hip): mnVisible, mnFound, mnFirstFId, membership of mvpRecentAddPoints; mnId per
+  // keyframe; the id of the frame the tracker last observed
+  int* life = nullptr;  // the block lorb::KfLife lays out; the members below point into it
+  int *visible = nullptr, *found = nullptr, *first_fid = nullptr, *kf_fid = nullptr, *frame_word = nullptr;
+  uint8_t* recent = nullptr;
+  uint8_t* cull_mark = nullptr;  // per point: culled by the call in flight; at rest (0) between calls
+  lorb::KfCullCtl* cull_ctl = nullptr;
   lorb::PlanSlots plans;
 };

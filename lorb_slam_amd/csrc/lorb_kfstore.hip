@@ -21,7 +21,9 @@
 //                     between calls), the counts, the capacity verdict -- all before the first store write --
 //                     then the ordered numbering of the new points, their rows, the slots, the gids, K's slot
 //                     row with its keypoints, K's pose vector, the counts, the refer words and the record; a new
-//                     point's slot is left in owner[] for k_kf_obs_scatter
+//                     point's slot is left in owner[] for k_kf_obs_scatter; the points' life (lorb_kfcull.hip):
+//                     kf_fid[K], a new point's visible, found, first_fid, recent for created points and for an
+//                     old point K holds in two or more slots
 //   k_kf_obs_count    owners per 1024-point tile; the observation CSR (keyframes and slots) copied to scratch
 //   k_kf_obs_scatter  the CSR back with K (and its owning slot) appended to the owned points' lists, the new
 //                     points' lists {K} with the slot that made them
@@ -73,6 +75,7 @@ struct HeadArgs {
   uint8_t *locked, *is_bad, *kf_bad;
   int *kf_slot_off, *kf_slot_point;
   float *kf_pose, *kf_slot_uv;
+  int* life;  // the points' life (lorb_kfcull.hip): one block, lorb::KfLife's layout over max_points / max_kf
   int *cnt, *owner;
   Ctl* ctl;
   int* refer_kf;                  // or null
@@ -94,7 +97,7 @@ __device__ __forceinline__ int slot_kind(const HeadArgs& a, int j, int P, int* g
 // a new store point seen from K alone: MapPoint::UpdateNormalAndDepth over one observation
 // (src/map_point.cpp:224-264), OpenCV's arithmetic restated (lorb_c.h): cv::norm accumulates in double
 __device__ __forceinline__ void new_point(const HeadArgs& a, int at, const float* p, const uint4& d0, const uint4& d1,
-                                          const float* Ow, int octave) {
+                                          const float* Ow, int octave, const lorb::KfLife& life, int fid, int created) {
 #pragma clang fp contract(off)
   const float dx = p[0] - Ow[0], dy = p[1] - Ow[1], dz = p[2] - Ow[2];
   const double nd = sqrt((double)dx * (double)dx + (double)dy * (double)dy + (double)dz * (double)dz);
@@ -110,6 +113,12 @@ __device__ __forceinline__ void new_point(const HeadArgs& a, int at, const float
   a.desc[2 * r + 1] = d1;
   a.locked[r] = 1;
   a.is_bad[r] = 0;
+  // its life starts with this frame; a created point already has K as an observation, so ProcessNewFrames pushes
+  // it to mvpRecentAddPoints (src/local_mapping.cpp:62-69); an adopted one gets AddObservation there
+  life.visible[r] = 1;
+  life.found[r] = 1;
+  life.first_fid[r] = fid;
+  life.recent[r] = (uint8_t)created;
 }
 
 __global__ __launch_bounds__(kWalk) void k_kf_head(HeadArgs a) {
@@ -179,6 +188,8 @@ __global__ __launch_bounds__(kWalk) void k_kf_head(HeadArgs a) {
 #pragma unroll
   for (int k = 0; k < 16; ++k) twc.v[k] = a.pose->Twc[k];
   const float Ow[3] = {twc.v[3], twc.v[7], twc.v[11]};
+  const lorb::KfLife life(a.life, a.max_points, a.max_kf);
+  const int fid = life.frame_word[0];  // mCurrFrame->mnId, as lorb_kf_store_observe_dev left it
   int run = 0;
   for (int base = 0; base < n; base += kWalk) {
     const int j = base + t;
@@ -196,6 +207,8 @@ __global__ __launch_bounds__(kWalk) void k_kf_head(HeadArgs a) {
       row = g;  // AddObservation: the owner's mark stays for k_kf_obs_scatter
       a.locked[g] = 1;
       a.state[j] = LORB_SLOT_LOCKED;
+      // a later slot of a point held twice finds IsInFrame true: pushed (src/local_mapping.cpp:66-69)
+      if (__hip_atomic_load(&a.owner[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != j) life.recent[g] = 1;
     } else if (is_new) {
       float p[3];
       uint4 d0, d1;
@@ -212,7 +225,7 @@ __global__ __launch_bounds__(kWalk) void k_kf_head(HeadArgs a) {
         a.sdesc[2 * (size_t)j + 1] = d1;
       }
       a.state[j] = LORB_SLOT_LOCKED;
-      new_point(a, at, p, d0, d1, Ow, a.octave[j]);
+      new_point(a, at, p, d0, d1, Ow, a.octave[j], life, fid, kind == kCreate);
       a.owner[at] = j;  // the slot that adopted or created it: k_kf_obs_scatter's obs_slot, which puts the word to rest
       row = at;
     }
@@ -224,6 +237,7 @@ __global__ __launch_bounds__(kWalk) void k_kf_head(HeadArgs a) {
   if (t < 6) a.kf_pose[6 * (size_t)K + t] = a.pose->pose[t];  // mRvec | mTvec
   if (t == 0) {
     a.kf_bad[K] = 0;
+    life.kf_fid[K] = fid;
     a.kf_slot_off[K + 1] = S + n;
     a.cnt[0] = K + 1; a.cnt[1] = P + n_new; a.cnt[2] = O + n_observed + n_new; a.cnt[3] = S + n;
     *a.ctl = Ctl{1, n, K, P, O, S, n_observed, n_new, 0, -1, 0, 0};
@@ -621,7 +635,14 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
   A.add(&S->ba_ocnt, np); A.add(&S->ba_ooff, np + 1);
   A.add(&S->w_local, nl); A.add(&S->w_fixed, nk); A.add(&S->w_l2g, np); A.add(&S->w_obs_point, no); A.add(&S->w_obs_frame, no);
   A.add(&S->w_pose, nl * 6); A.add(&S->w_fixed_pose, nk * 6); A.add(&S->w_point, np * 3); A.add(&S->w_uv, no * 2);
+  // the points' life and the cull's scratch (lorb_kfcull.hip)
+  A.add(&S->life, lorb::KfLife::ints(caps->max_points, caps->max_kf)); A.add(&S->cull_mark, np); A.add(&S->cull_ctl, (size_t)1);
   LORB_HIP(ctx, A.commit());
+  {
+    const lorb::KfLife life(S->life, caps->max_points, caps->max_kf);
+    S->visible = life.visible; S->found = life.found; S->first_fid = life.first_fid; S->recent = life.recent;
+    S->kf_fid = life.kf_fid; S->frame_word = life.frame_word;
+  }
   LORB_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&S->h_hdr), sizeof(lorb::KfBaHdr)));
   memset(S->h_hdr, 0, sizeof(lorb::KfBaHdr));
   S->h_hdr->status = 1;  // no window gathered yet
@@ -631,7 +652,7 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
   LORB_HIP(ctx, hipMemsetAsync(S->kf_bad, 1, nk, st));
   LORB_HIP(ctx, hipMemsetAsync(S->owner, 0x7f, np * sizeof(int), st));
   LORB_HIP(ctx, hipMemsetAsync(S->ba_first, 0x7f, np * sizeof(int), st));
-  std::vector<int32_t> conn_n, conn_kf, conn_w, ord_n, ord_kf;  // alive until the wait below
+  std::vector<int32_t> conn_n, conn_kf, conn_w, ord_n, ord_kf, ones;  // alive until the wait below
   int32_t cnt[6] = {0, 0, 0, 0, 0, 0};
   if (init) {
     const lorb_kf_store_host& h = *init;
@@ -646,6 +667,8 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
     else if (hp) LORB_HIP(ctx, hipMemsetAsync(S->is_bad, 0, hp, st));
     if (h.kf_bad) LORB_HIP(ctx, up(S->kf_bad, h.kf_bad, hk));
     else if (hk) LORB_HIP(ctx, hipMemsetAsync(S->kf_bad, 0, hk, st));
+    ones.assign(hp, 1);  // mnVisible = mnFound = 1 (src/map_point.cpp's constructors); first_fid, recent, kf_fid stay 0
+    LORB_HIP(ctx, up(S->visible, ones.data(), hp * 4)); LORB_HIP(ctx, up(S->found, ones.data(), hp * 4));
     if (h.obs_off) LORB_HIP(ctx, up(S->obs_off, h.obs_off, (hp + 1) * 4));
     LORB_HIP(ctx, up(S->obs_kf, h.obs_kf, (size_t)h.n_obs * 4));
     if (hk) {
@@ -787,6 +810,7 @@ int lorb_kf_store_insert_dev(lorb_ctx* ctx, lorb_kf_store* S, const lorb_frame_p
   a.pos = S->pos; a.normal = S->normal; a.max_dist = S->max_dist; a.min_dist = S->min_dist;
   a.desc = reinterpret_cast<uint4*>(S->desc); a.locked = S->locked; a.is_bad = S->is_bad; a.kf_bad = S->kf_bad;
   a.kf_slot_off = S->kf_slot_off; a.kf_slot_point = S->kf_slot_point; a.kf_pose = S->kf_pose; a.kf_slot_uv = S->kf_slot_uv;
+  a.life = S->life;
   a.cnt = S->cnt; a.owner = S->owner; a.ctl = S->ctl;
   a.refer_kf = d_refer_kf; a.update = d_update; a.rec = d_result;
   hipStream_t st = ctx->stream;

@@ -429,8 +429,9 @@ class KeyframeStore:
     store.c; arrays: DeviceArray views of the store's own memory over its whole capacity (not to be freed).
     geom: None, or dict(kf_pose: n_kf x 6; kf_slot_uv: per keyframe its slots' (x, y); obs_slot: per point the slot
     of each observation) -- lorb_kf_store_create_geom.  geometry: the views of kf_pose, kf_slot_uv and obs_slot,
-    kept apart from arrays."""
-    COUNTS = ("n_kf", "n_points", "n_obs", "n_kf_slots", "n_cov", "n_conn")
+    kept apart from arrays.  life: the views of visible, found, first_fid, recent, kf_fid and the one-word
+    frame_word (read_life / write_life; keyframe_observe and keyframe_cull work on them)."""
+    COUNTS =("n_kf", "n_points", "n_obs", "n_kf_slots", "n_cov", "n_conn")
     _COLS = dict(pos=(np.float32, 3), normal=(np.float32, 3), max_dist=(np.float32, 1), min_dist=(np.float32, 1),
                  desc=(np.uint8, 32), locked=(np.uint8, 1), is_bad=(np.uint8, 1))
 
@@ -460,6 +461,19 @@ class KeyframeStore:
                            kf_slot_point=arr(v.kf_slot_point, self.caps.max_kf_slots, np.int32),
                            cov_off=arr(v.cov_off, cap["n_kf"] + 1, np.int32), cov_kf=arr(v.cov_kf, self.max_cov, np.int32))
         self.geometry = self._geometry_views()
+        self.life = self._life_views()
+
+    def _life_views(self):
+        """lorb_kf_store_life_view / _frame_word_view: visible, found, first_fid, recent, kf_fid over their whole
+        capacity and the one-word frame_word (no wait)."""
+        g, w = A.KfStoreLifeHost(), C.c_void_p()
+        self.ctx.check(lib().lorb_kf_store_life_view(self._p, C.byref(g)), "lorb_kf_store_life_view")
+        self.ctx.check(lib().lorb_kf_store_frame_word_view(self._p, C.byref(w)), "lorb_kf_store_frame_word_view")
+        out = {k: DeviceArrayView(self.ctx, getattr(g, k), (g.n_points,), np.int32) for k in ("visible", "found", "first_fid")}
+        out.update(recent=DeviceArrayView(self.ctx, g.recent, (g.n_points,), np.uint8),
+                   kf_fid=DeviceArrayView(self.ctx, g.kf_fid, (g.n_kf,), np.int32),
+                   frame_word=DeviceArrayView(self.ctx, w.value, (1,), np.int32))
+        return out
 
     def _geometry_views(self):
         """lorb_kf_store_geom_view: kf_pose, kf_slot_uv and obs_slot over their whole capacity (no wait)."""
@@ -548,6 +562,42 @@ class KeyframeStore:
             setattr(h, k, v.ctypes.data)
         self.ctx.check(lib().lorb_kf_store_geom_read(self._p, C.byref(h)), "lorb_kf_store_geom_read")
         return a
+
+    _LIFE = dict(visible=np.int32, found=np.int32, first_fid=np.int32, recent=np.uint8, kf_fid=np.int32)
+
+    def read_life(self):
+        """lorb_kf_store_life_read (waits): dict(visible, found, first_fid, recent: n_points; kf_fid: n_kf) -- the true
+        rows -- and frame_word, the id of the frame the tracker last observed."""
+        n = self.counts()
+        a = {k: np.zeros(n["n_kf"] if k == "kf_fid" else n["n_points"], dt) for k, dt in self._LIFE.items()}
+        h = A.KfStoreLifeHost(n["n_kf"], n["n_points"])
+        for k, v in a.items():
+            setattr(h, k, v.ctypes.data)
+        self.ctx.check(lib().lorb_kf_store_life_read(self._p, C.byref(h)), "lorb_kf_store_life_read")
+        a["frame_word"] = int(self.life["frame_word"].numpy()[0])
+        return a
+
+    def write_life(self, life, n_kf=None, n_points=None):
+        """lorb_kf_store_life_write (waits): replaces the true rows by every array of `life` that is given (keys of
+        read_life but frame_word).  n_kf / n_points default to the true counts; they must equal them."""
+        n = self.counts()
+        keep = {k: np.ascontiguousarray(life[k], dt) for k, dt in self._LIFE.items() if life.get(k) is not None}
+        h = A.KfStoreLifeHost(n["n_kf"] if n_kf is None else int(n_kf), n["n_points"] if n_points is None else int(n_points))
+        for k, v in keep.items():
+            if len(v) != (h.n_kf if k == "kf_fid" else h.n_points):
+                raise LorbError(f"life: {k} has {len(v)} entries")
+            setattr(h, k, v.ctypes.data)
+        self.ctx.check(lib().lorb_kf_store_life_write(self._p, C.byref(h)), "lorb_kf_store_life_write")
+
+    def fill_life(self, counts, value=ORB_SENTINEL):
+        """fill() for the life arrays: `value` bytes past the given true counts (the frame word is left alone)."""
+        for k, arr in self.life.items():
+            if k == "frame_word":
+                continue
+            at = counts["n_kf" if k == "kf_fid" else "n_points"] * arr.dtype.itemsize
+            if at < arr.nbytes:
+                self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
+                                                     C.c_size_t(arr.nbytes - at)), "memset")
 
     def fill_geometry(self, counts, value=ORB_SENTINEL):
         """fill() for the geometry arrays: `value` bytes past the given true counts."""
@@ -647,6 +697,56 @@ def keyframe_local_ba(ctx, store, fp, d_kf, record, d_src_status=None, opt=None,
 def keyframe_ba_result(record):
     """The A.KfBaResult in a device record buffer (waits for the stream)."""
     return A.KfBaResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfBaResult)])
+
+
+def keyframe_observe_record(ctx):
+    """A device buffer for an A.KfObserveResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
+    return _sentinel(ctx, C.sizeof(A.KfObserveResult) + ORB_GUARD, np.uint8)
+
+
+def keyframe_observe(ctx, store, frame_id, cur, cur_slots, slot_gid, slot_id, lmap, update_record, in_view, record,
+                     n_max_cur=None, d_local_status=None, found_rule=A.LORB_KF_FOUND_NEVER):
+    """lorb_kf_store_observe_dev enqueued and nothing else: the tracker's two IncreaseVisible sites on a
+    KeyframeStore, behind track_local_frames and in front of local_map_ids_back.  frame_id: mCurrFrame->mnId;
+    slot_gid / slot_id: the frame's gids and local rows (DeviceArrays); lmap: a LocalMap or an A.LocalMapArrays;
+    update_record: the frame's local-map record; in_view: the local stage's d_in_view; d_local_status: a device
+    address or None; record: a device buffer for the A.KfObserveResult."""
+    nc = cur_slots.n_max if n_max_cur is None else int(n_max_cur)
+    view = lmap.view if hasattr(lmap, "view") else lmap
+    ctx.check(lib().lorb_kf_store_observe_dev(
+        ctx.handle, store._p, C.c_int32(int(frame_id)), C.byref(cur.out), C.c_int32(nc), C.byref(cur_slots.c), slot_gid.ptr,
+        slot_id.ptr, C.byref(view), update_record.ptr, in_view.ptr, C.c_void_p(d_local_status) if d_local_status else None,
+        C.c_int32(found_rule), record.ptr), "lorb_kf_store_observe_dev")
+
+
+def keyframe_observe_result(record):
+    """The A.KfObserveResult in a device record buffer (waits for the stream)."""
+    return A.KfObserveResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfObserveResult)])
+
+
+def keyframe_cull_record(ctx):
+    """A device buffer for an A.KfCullResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
+    return _sentinel(ctx, C.sizeof(A.KfCullResult) + ORB_GUARD, np.uint8)
+
+
+def keyframe_cull(ctx, store, d_kf, record, d_src_status=None, params=A.LORB_KF_CULL_REFERENCE, cur=None, cur_slots=None,
+                  slot_gid=None, n_max_cur=None):
+    """lorb_kf_store_cull_dev enqueued and nothing else: MapPointsCulling with SetBadFlag on a KeyframeStore, behind
+    keyframe_insert and in front of keyframe_local_ba.  d_kf / d_src_status: device addresses (the kf and status
+    words of the insertion's record); params: (min_found_ratio, age_obs, min_obs, age_out) or an A.KfCullParams;
+    cur, cur_slots, slot_gid: the tracker's objects of the frame that became K, all three or none; record: a device
+    buffer for the A.KfCullResult (keyframe_cull_record)."""
+    par = params if isinstance(params, A.KfCullParams) else A.KfCullParams(*params)
+    nc = 0 if cur_slots is None else (cur_slots.n_max if n_max_cur is None else int(n_max_cur))
+    ctx.check(lib().lorb_kf_store_cull_dev(
+        ctx.handle, store._p, C.c_void_p(d_kf), C.c_void_p(d_src_status) if d_src_status else None, C.byref(par),
+        C.byref(cur.out) if cur is not None else None, C.c_int32(nc), C.byref(cur_slots.c) if cur_slots is not None else None,
+        slot_gid.ptr if slot_gid is not None else None, record.ptr), "lorb_kf_store_cull_dev")
+
+
+def keyframe_cull_result(record):
+    """The A.KfCullResult in a device record buffer (waits for the stream)."""
+    return A.KfCullResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfCullResult)])
 
 
 def keyframe_insert_result(record):

@@ -127,8 +127,9 @@ def build_arms(ctx, calls, expose=None):
         return L.lorb_kf_store_insert_dev(h, store._p, C.byref(fps), C.byref(b["f"].out), nb, C.byref(b["cs"].c), b["gid"].ptr,
                                           b["pose"].ptr, b["d_lstatus"], C.c_int32(gate), b["kf"].ptr, b["urec"].ptr, b["irec"].ptr)
 
-    def frame(b, lmap, view):
-        """One frame: tools/bench_frame_loop_refer.py's arm c on the given store view."""
+    def frame(b, lmap, view, between=None):
+        """One frame: tools/bench_frame_loop_refer.py's arm c on the given store view.  between: a call enqueued behind
+        the local stage and in front of the ids' way back (tools/bench_kf_cull.py: lorb_kf_store_observe_dev)."""
         o = b["out"]
         rc = L.lorb_frame_build_dev(fb._p, b["l"].ptr, cols, b["r"].ptr, cols, C.byref(b["f"].out))
         rc |= L.lorb_track_motion_frames_pose_dev(h, C.byref(fps), b["pose"].ptr, C.byref(b["f"].out), nb, C.byref(b["cs"].c),
@@ -143,6 +144,8 @@ def build_arms(ctx, calls, expose=None):
         rc |= L.lorb_track_local_frames_dev(h, C.byref(fps), C.byref(b["f"].out), nb, C.byref(b["cs"].c), b["sid"].ptr, b["d_pose"],
                                             b["d_ustatus"], None, C.byref(lmap.c), C.byref(lpar), C.byref(opt), o.in_view.ptr,
                                             o.track.ptr, o.level.ptr, o.assign.ptr, o.record.ptr)
+        if between is not None:
+            rc |= between(b, lmap)
         rc |= L.lorb_local_map_ids_back_dev(h, lmap._p, C.byref(b["f"].out), nb, C.byref(b["cs"].c), b["sid"].ptr, b["d_lstatus"],
                                             b["gid"].ptr)
         return rc | L.lorb_frame_pose_finish_dev(h, o.record.ptr, last_pose.ptr, b["pose"].ptr, b["model"].ptr)
@@ -220,7 +223,7 @@ def build_arms(ctx, calls, expose=None):
 
     if expose is not None:
         expose.update(fp=fp, fps=fps, init=init, caps=caps, bufs=bufs, frame=frame, insert=insert, static=static,
-                      lmap_static=lmap_static, keep=keep, opt=opt)
+                      lmap_static=lmap_static, lmap_grow=lmap_grow, model_I=model_I, keep=keep, opt=opt)
     base = dict(n_last=n_last, bound=BOUND, max_local=MAX_LOCAL, store_points=N_POINTS, store_keyframes=N_KF, caps=caps,
                 inserts_per_round=inserts, every=EVERY)
     return arms, one_insertion, info, base, cleanup

@@ -94,8 +94,9 @@ __global__ __launch_bounds__(256) void k_ba_init(BaDev d, int W, int ctot, int n
 // by point) number <= kGB, processed by one 256-thread workgroup: observation-parallel phases
 // (thread = observation, coalesced, no serial load chains) alternate with point phases (thread =
 // point) that reduce their observations from LDS serially in observation order -- the same
-// summation order as a point-serial loop.  A point with more than kGB observations gets a group
-// of its own and the observation phases loop over chunks.
+// summation order as a point-serial loop.  A group holds whole points, so no point may have more than
+// kGB observations: both plan builders refuse such a window (lorb_ba_build.hip: the host builder takes a
+// point with up to kGB observations, the device builder up to kGB - 1); ls_group has no chunk loop.
 
 // deterministic point-group reductions (fixed butterfly per wave, fixed wave order) over the
 // kGB / 64 waves of a point-group workgroup

@@ -1394,7 +1394,8 @@ typedef struct lorb_kf_cull_result {   /* device memory, like every record of th
  *      (Frame::EraseMapPoint, src/frame.cpp:896-899; f bad or not), others are counted in n_obs_bad_slot and skipped;
  *      its list is removed from obs_off / obs_kf / obs_slot: every later list moves left, order kept, and the true
  *      n_obs drops.  Left as they are, as in the reference: locked, pos, normal, the distances, desc, the weight
- *      maps, the ordered lists and cov_*.  Point rows are not reclaimed: indices stay stable.
+ *      maps, the ordered lists and cov_*.  Point rows are not reclaimed by this call: indices stay stable until the
+ *      caller enqueues lorb_kf_store_compact_dev.
  *   d. With the frame group: every slot j < counts[0] whose gid names a point culled BY THIS CALL becomes EMPTY
  *      with gid -1 (K's Frame is the tracker's frame in the reference).  A slot holding a point that was bad before
  *      the call stays as it is.  counts[0] outside [0, n_max_cur]: no slot is touched.
@@ -1409,11 +1410,83 @@ typedef struct lorb_kf_cull_result {   /* device memory, like every record of th
  * Asynchronous on the ctx stream: 4 kernel launches, no stream synchronise, no device-to-host read and no
  * host-to-device copy.
  * Out of scope: KeyFramesCulling (empty in the reference, src/local_mapping.cpp:110-113); reclaiming rows (point
- * rows are not reclaimed); MapPoint::EraseObservation's own SetBadFlag at mnObs <= 2 (nothing in the chain erases a
+ * rows are not reclaimed here: lorb_kf_store_compact_dev below); MapPoint::EraseObservation's own SetBadFlag at mnObs <= 2 (nothing in the chain erases a
  * single observation); the life of an adopted point before it had a store row. */
 int lorb_kf_store_cull_dev(lorb_ctx* ctx, lorb_kf_store* store, const int32_t* d_kf, const int32_t* d_src_status,
                            const lorb_kf_cull_params* par, const lorb_frame_out* d_cur, int32_t n_max_cur,
                            const lorb_frame_slots* d_cur_slots, int32_t* d_cur_slot_gid, lorb_kf_cull_result* d_result);
+
+/* ----------------------------------------------------------------------------------------
+ * Reclaiming dead point rows: Map::EraseMapPoint for the store.  lorb_kf_store_cull_dev leaves a culled point its
+ * index and its row; lorb_kf_store_compact_dev deletes the rows nothing can name any more, renumbers the survivors
+ * in their order and rewrites every place that holds a point index -- in the store, and in the gid tables the
+ * caller names.  It is a pure renumbering: every later call gives what it would have given without it, up to the
+ * index map.
+ * -------------------------------------------------------------------------------------- */
+#define LORB_KF_COMPACT_MAX_TABLES 8
+typedef struct lorb_kf_gid_table {   /* a host struct of device addresses: one frame's gids */
+  int32_t* d_gid;            /* n_max int32: the array lorb_track_motion_refer_pose_dev reads as d_last_slot_gid /
+                                d_refer_slot_gid, or any table of store indices the caller keeps */
+  int32_t n_max;             /* its bound */
+  const int32_t* d_count;    /* the device word with the number of entries in use: the frame's counts[0] */
+} lorb_kf_gid_table;
+typedef struct lorb_kf_compact_result {   /* device memory, like every record of the chain */
+  int32_t status;             /* 0; 1: a source status, a table count outside [0, n_max] or a damaged count of the
+                                 store: nothing else was written */
+  int32_t n_points_before;    /* the true n_points on entry */
+  int32_t n_dropped;          /* rows reclaimed */
+  int32_t n_points;           /* the store after the call */
+  int32_t n_bad_kept;         /* bad points that keep their row: still observed, or held by a keyframe slot or a table */
+  int32_t n_kf_slots_mapped;  /* keyframe slots rewritten through the map (0 when nothing was dropped) */
+  int32_t n_gids_mapped;      /* table entries rewritten through the map (0 when nothing was dropped) */
+} lorb_kf_compact_result;
+
+/* Enqueued behind lorb_kf_store_local_ba_dev of a keyframe step (or of every n-th one), in front of the next
+ * frame's motion stage, with d_src_status = &d_insert_result->status (nullable).  tables is a host array of
+ * n_tables <= LORB_KF_COMPACT_MAX_TABLES entries (NULL with n_tables = 0): in the loop the gids of the frame that
+ * becomes d_last, of the refer frame, and of every other frame the caller keeps.  Two entries with the same d_gid,
+ * n_max and d_count are one table; tables must not overlap otherwise.  d_map is nullable: max_points device int32.
+ * NOT between a frame's lorb_local_map_update_dev and its lorb_local_map_ids_back_dev / lorb_kf_store_observe_dev:
+ * that frame's local map (l2g, g2l) holds the old indices until the next update rebuilds it.  A lorb_local_map is
+ * not remapped.  On the device, in this order, P, O, S the true n_points, n_obs, n_kf_slots on entry:
+ *   a. Status, in the first launch and before the first write: *d_src_status != 0, a table's *d_count outside
+ *      [0, n_max], or P / S outside the store's capacities stores status = 1 and NOTHING else.  A table that cannot
+ *      be examined refuses the whole call: skipping it would leave stale indices in it.
+ *   b. Holds.  A bad point p < P named by a keyframe slot kf_slot_point[i], i < S, or by an entry j < *d_count of a
+ *      table is held.  (The insertion's "held, point bad: slot, gid and K's row keep g" and the cull's "a slot
+ *      holding a point that was bad before the call stays as it is" produce such holds; both stay as they are.)
+ *   c. Verdict.  p < P is DROPPED when is_bad[p], its observation list is empty (obs_off clamped to [0, O] as the
+ *      cull reads it) and it is not held; every other point is kept.  A point lorb_kf_store_cull_dev culled is
+ *      dropped; a bad point that is still observed, or held, is kept (n_bad_kept) and goes in a later call once it
+ *      is released.  new(p) = the number of kept points below p: the order of the survivors is preserved, so the
+ *      local point table, the numbering of new points and every tile scan see the order they saw before.
+ *   d. d_map, when given: new(p) for kept and -1 for dropped p < P; the identity when nothing is dropped.
+ *   With nothing to drop the call ends here: NOT A BYTE of the store or of a table changes.
+ *   e. Rows.  pos, normal, max_dist, min_dist, desc, locked, is_bad, obs_off, visible, found, first_fid, recent of
+ *      every kept p move to row new(p), as bytes, through staging memory the store owns (the pointers of
+ *      lorb_kf_store_view / _geom_view / _life_view never change).  obs_kf and obs_slot do not move -- dropped
+ *      points have empty lists -- and obs_off[new n_points] = O.  Rows [new n_points, P) return to what a fresh
+ *      store has there: zero bytes, is_bad = 1; obs_off (new n_points, P] = 0.
+ *   f. Indices.  Every kf_slot_point[i], i < S, and every table entry j < *d_count that holds an index in [0, P)
+ *      becomes new(index) -- never -1, by b.  The invariant kf_slot_point[kf_slot_off[f] + obs_slot[o]] == p holds
+ *      for the new p.  -1, an index outside [0, P) and entries at or past *d_count stay as they are.
+ *   g. The true n_points and the record.  The counters are integer: no result depends on the order atomics arrive.
+ * Nothing at or past the OLD true count is written in any array of the store (obs_off: past P), nothing at or past
+ * *d_count in a table.  The per-point words at rest between calls (the insertion's owner, the BA's first position,
+ * the cull's mark, this call's hold) are at rest over the whole capacity when the call ends, on every path.  The
+ * host's bounds stay valid upper bounds and are not touched; lorb_kf_store_counts tightens them at the caller's
+ * next wait.  Capacity is decided on the device against the true counts: the next insertion can use the reclaimed
+ * rows at once.
+ * LORB_E_INVALID, before anything is enqueued: a null required argument (ctx, store, d_result; tables with
+ * n_tables > 0), a store of another ctx, n_tables outside [0, LORB_KF_COMPACT_MAX_TABLES], a null d_gid or d_count,
+ * n_max < 1, two entries with the same d_gid but another n_max or d_count.
+ * Asynchronous on the ctx stream: 5 kernel launches, no stream synchronise, no device-to-host read and no
+ * host-to-device copy.
+ * Out of scope: keyframe rows and KeyFramesCulling; the weight maps' layout; a host-array form or a C++ adapter;
+ * remapping a lorb_local_map; lorb_map_step_dev. */
+int lorb_kf_store_compact_dev(lorb_ctx* ctx, lorb_kf_store* store, const int32_t* d_src_status,
+                              const lorb_kf_gid_table* tables, int32_t n_tables, int32_t* d_map,
+                              lorb_kf_compact_result* d_result);
 
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.

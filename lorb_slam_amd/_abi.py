@@ -322,6 +322,18 @@ class KfCullResult(C.Structure):  # lorb_kf_cull_result
                 ("n_obs_bad_slot", C.c_int32), ("n_obs", C.c_int32)]
 
 
+LORB_KF_COMPACT_MAX_TABLES = 8
+
+
+class KfGidTable(C.Structure):  # lorb_kf_gid_table (device addresses)
+    _fields_ = [("d_gid", C.c_void_p), ("n_max", C.c_int32), ("d_count", C.c_void_p)]
+
+
+class KfCompactResult(C.Structure):  # lorb_kf_compact_result
+    _fields_ = [("status", C.c_int32), ("n_points_before", C.c_int32), ("n_dropped", C.c_int32), ("n_points", C.c_int32),
+                ("n_bad_kept", C.c_int32), ("n_kf_slots_mapped", C.c_int32), ("n_gids_mapped", C.c_int32)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

@@ -1,6 +1,6 @@
 // lorb_kfstore.h -- the keyframe store's object, shared by lorb_kfstore.hip (create / read / insertion),
-// lorb_kfba.hip (the local bundle adjustment fed from the store) and lorb_kfcull.hip (the points' life and
-// MapPointsCulling).
+// lorb_kfba.hip (the local bundle adjustment fed from the store), lorb_kfcull.hip (the points' life and
+// MapPointsCulling) and lorb_kfcompact.hip (reclaiming the dead point rows).
 #pragma once
 
 #include "lorb_ba_slots.h"
@@ -39,6 +39,14 @@ struct KfCullCtl {
   int kf, cur;      // K and kf_fid[K]
   int nk, P, O, S;  // the true counts on entry
   int n_culled;     // points culled by this call: 0 makes the kernels after the verdicts return at once
+};
+
+// k_kf_compact_head's verdict and the counts a compaction's later kernels read (lorb_kfcompact.hip)
+struct KfCompactCtl {
+  int go;       // the compaction runs
+  int P, O, S;  // the true counts on entry
+  int n_drop;   // rows dropped by this call: 0 makes the kernels after the count return at once
+  int pad[3];
 };
 
 // the points' life as one block of ints, so that a kernel takes one pointer: visible | found | first_fid | recent
@@ -101,5 +109,13 @@ struct lorb_kf_store {
   uint8_t* recent = nullptr;
   uint8_t* cull_mark = nullptr;  // per point: culled by the call in flight; at rest (0) between calls
   lorb::KfCullCtl* cull_ctl = nullptr;
+  // a compaction's staging (lorb_kfcompact.hip): the surviving point rows on their way to their new index (the
+  // offsets ride in off2, the tile counts in tile_cnt), old -> new per point, and the holds
+  float *cp_pos = nullptr, *cp_normal = nullptr, *cp_max_dist = nullptr, *cp_min_dist = nullptr;
+  uint8_t *cp_desc = nullptr, *cp_locked = nullptr, *cp_is_bad = nullptr, *cp_recent = nullptr;
+  int *cp_visible = nullptr, *cp_found = nullptr, *cp_first_fid = nullptr;
+  int* cp_map = nullptr;       // per point: its rank among its tile's kept points, then its new index; -1: dropped
+  uint8_t* cp_hold = nullptr;  // per point: bad and named by a keyframe slot or a gid table; at rest (0) between calls
+  lorb::KfCompactCtl* cp_ctl = nullptr;
   lorb::PlanSlots plans;
 };

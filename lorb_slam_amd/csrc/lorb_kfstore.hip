@@ -637,6 +637,11 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
   A.add(&S->w_pose, nl * 6); A.add(&S->w_fixed_pose, nk * 6); A.add(&S->w_point, np * 3); A.add(&S->w_uv, no * 2);
   // the points' life and the cull's scratch (lorb_kfcull.hip)
   A.add(&S->life, lorb::KfLife::ints(caps->max_points, caps->max_kf)); A.add(&S->cull_mark, np); A.add(&S->cull_ctl, (size_t)1);
+  // a compaction's staging (lorb_kfcompact.hip): 79 bytes of rows, 4 of map and 1 of hold per point
+  A.add(&S->cp_pos, np * 3); A.add(&S->cp_normal, np * 3); A.add(&S->cp_max_dist, np); A.add(&S->cp_min_dist, np);
+  A.add(&S->cp_desc, np * 32); A.add(&S->cp_locked, np); A.add(&S->cp_is_bad, np); A.add(&S->cp_recent, np);
+  A.add(&S->cp_visible, np); A.add(&S->cp_found, np); A.add(&S->cp_first_fid, np);
+  A.add(&S->cp_map, np); A.add(&S->cp_hold, np); A.add(&S->cp_ctl, (size_t)1);
   LORB_HIP(ctx, A.commit());
   {
     const lorb::KfLife life(S->life, caps->max_points, caps->max_kf);

@@ -430,7 +430,8 @@ class KeyframeStore:
     geom: None, or dict(kf_pose: n_kf x 6; kf_slot_uv: per keyframe its slots' (x, y); obs_slot: per point the slot
     of each observation) -- lorb_kf_store_create_geom.  geometry: the views of kf_pose, kf_slot_uv and obs_slot,
     kept apart from arrays.  life: the views of visible, found, first_fid, recent, kf_fid and the one-word
-    frame_word (read_life / write_life; keyframe_observe and keyframe_cull work on them)."""
+    frame_word (read_life / write_life; keyframe_observe and keyframe_cull work on them).  compact() reclaims the
+    rows of dead points (lorb_kf_store_compact_dev); the views stay valid, the indices in them change."""
     COUNTS =("n_kf", "n_points", "n_obs", "n_kf_slots", "n_cov", "n_conn")
     _COLS = dict(pos=(np.float32, 3), normal=(np.float32, 3), max_dist=(np.float32, 1), min_dist=(np.float32, 1),
                  desc=(np.uint8, 32), locked=(np.uint8, 1), is_bad=(np.uint8, 1))
@@ -639,6 +640,25 @@ class KeyframeStore:
                 self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
                                                      C.c_size_t(arr.nbytes - at)), "memset")
 
+    def compact(self, record, tables=(), d_src_status=None, d_map=None):
+        """lorb_kf_store_compact_dev enqueued and nothing else: the store's dead point rows -- bad, unobserved, named
+        by no keyframe slot and no table -- are reclaimed and the survivors renumbered in their order, behind
+        keyframe_local_ba and in front of the next frame's motion stage (never between a frame's local_map_update
+        and its local_map_ids_back / keyframe_observe).  tables: at most A.LORB_KF_COMPACT_MAX_TABLES entries
+        (slot_gid, count) or (slot_gid, count, n_max) -- a frame's gid DeviceArray and the device ADDRESS of its
+        counts[0] (a DeviceFrame's out.counts) or a DeviceArray holding it; n_max defaults to the gid array's
+        length.  d_src_status: a device address or None; d_map: a DeviceArray of max_points int32 or None; record: a
+        device buffer for the A.KfCompactResult (keyframe_compact_record)."""
+        tabs = (A.KfGidTable * max(len(tables), 1))()
+        for i, tb in enumerate(tables):
+            gid, count = tb[0], tb[1]
+            n_max = int(tb[2]) if len(tb) > 2 else int(gid.shape[0])
+            addr = count.ptr.value if hasattr(count, "ptr") else (count.value if hasattr(count, "value") else count)
+            tabs[i] = A.KfGidTable(gid.ptr.value, n_max, addr)
+        self.ctx.check(lib().lorb_kf_store_compact_dev(
+            self.ctx.handle, self._p, C.c_void_p(d_src_status) if d_src_status else None, tabs if len(tables) else None,
+            C.c_int32(len(tables)), d_map.ptr if d_map is not None else None, record.ptr), "lorb_kf_store_compact_dev")
+
     def free(self):
         if self._p:
             lib().lorb_kf_store_destroy(self._p)
@@ -747,6 +767,16 @@ def keyframe_cull(ctx, store, d_kf, record, d_src_status=None, params=A.LORB_KF_
 def keyframe_cull_result(record):
     """The A.KfCullResult in a device record buffer (waits for the stream)."""
     return A.KfCullResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfCullResult)])
+
+
+def keyframe_compact_record(ctx):
+    """A device buffer for an A.KfCompactResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
+    return _sentinel(ctx, C.sizeof(A.KfCompactResult) + ORB_GUARD, np.uint8)
+
+
+def keyframe_compact_result(record):
+    """The A.KfCompactResult in a device record buffer (waits for the stream)."""
+    return A.KfCompactResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfCompactResult)])
 
 
 def keyframe_insert_result(record):

@@ -223,7 +223,7 @@ def build_arms(ctx, calls, expose=None):
 
     if expose is not None:
         expose.update(fp=fp, fps=fps, init=init, caps=caps, bufs=bufs, frame=frame, insert=insert, static=static,
-                      lmap_static=lmap_static, lmap_grow=lmap_grow, model_I=model_I, keep=keep, opt=opt)
+                      lmap_static=lmap_static, lmap_grow=lmap_grow, model_I=model_I, keep=keep, opt=opt, fa=fa, last_gid=d_last_gid)
     base = dict(n_last=n_last, bound=BOUND, max_local=MAX_LOCAL, store_points=N_POINTS, store_keyframes=N_KF, caps=caps,
                 inserts_per_round=inserts, every=EVERY)
     return arms, one_insertion, info, base, cleanup

@@ -1488,6 +1488,111 @@ int lorb_kf_store_compact_dev(lorb_ctx* ctx, lorb_kf_store* store, const int32_t
                               const lorb_kf_gid_table* tables, int32_t n_tables, int32_t* d_map,
                               lorb_kf_compact_result* d_result);
 
+/* ----------------------------------------------------------------------------------------
+ * The appearance of the store and the refresh of a window's points: MapPoint::ComputeDescriptor
+ * (src/map_point.cpp:69-129) and MapPoint::UpdateNormalAndDepth (:224-264) on the keyframe store.  The reference
+ * calls the two only where a point has exactly one observation (src/visual_odometry.cpp:94-95,392-393); ORB-SLAM2,
+ * which it follows, calls them in ProcessNewKeyFrame and after LocalBundleAdjustment.  Like MapPointsCulling it is a
+ * call of its own: the mapper step becomes lorb_kf_store_insert_dev -> _cull_dev -> _local_ba_dev -> _refresh_dev ->
+ * _compact_dev, and a caller who leaves the refresh out gets the store the other four give.
+ *
+ * Appearance.  Beside its other arrays the store keeps, at capacity and at addresses that never change:
+ *   kf_slot_desc    max_kf_slots x 32 uint8, 16-byte aligned   Frame::GetDescriptor(j) of every keyframe slot,
+ *                                                              parallel to kf_slot_point
+ *   kf_slot_octave  max_kf_slots int32                         mvKeysUn[j].octave
+ *   kf_center       max_kf x 3 float                           mptCameraCenter of every keyframe
+ * lorb_kf_store_insert_dev maintains them for keyframe K (still six launches, no wait, no copy): K's descriptor and
+ * octave rows are the frame's left descriptors and octave[j] of the slots j < n_cur, kf_center[K] = (Twc[3], Twc[7],
+ * Twc[11]) of d_cur_pose -- exactly the values a new point's row is made from.  Nothing at or past a new true count
+ * is written; a refused, failed or full insertion writes none of it.  lorb_kf_store_cull_dev and
+ * lorb_kf_store_compact_dev renumber neither slots nor keyframes and leave the three arrays alone.
+ * A store created with n_kf > 0 has no appearance for its initial keyframes until lorb_kf_store_appear_write:
+ * lorb_kf_store_refresh_dev refuses it, as the BA refuses a store without geometry.  An empty store is complete by
+ * construction.
+ * lorb_kf_store_appear_write waits and replaces the true rows by every non-NULL member: n_kf and n_kf_slots must EQUAL
+ * the true counts; an octave outside [0, LORB_MAX_LEVELS) is LORB_E_INVALID with a message naming the entry.  The
+ * store is complete once one call has given every array that has rows.  lorb_kf_store_appear_read waits and copies
+ * the true rows into every non-NULL member (the n_* fields are the CAPACITIES of the caller's arrays; LORB_E_INVALID
+ * when one is below its true count).  lorb_kf_store_appear_view returns the device arrays themselves, the n_* fields
+ * their capacities (no wait; the pointers never change).
+ * -------------------------------------------------------------------------------------- */
+typedef struct lorb_kf_store_appear_host {
+  int32_t n_kf, n_kf_slots;   /* write: must equal the true counts; read: capacities */
+  uint8_t* kf_slot_desc;      /* n_kf_slots x 32 */
+  int32_t* kf_slot_octave;    /* n_kf_slots */
+  float* kf_center;           /* n_kf x 3 */
+} lorb_kf_store_appear_host;
+int lorb_kf_store_appear_write(lorb_kf_store* store, const lorb_kf_store_appear_host* in);   /* waits */
+int lorb_kf_store_appear_read(lorb_kf_store* store, const lorb_kf_store_appear_host* out);   /* waits */
+int lorb_kf_store_appear_view(const lorb_kf_store* store, lorb_kf_store_appear_host* out);   /* no wait */
+
+#define LORB_KF_REFRESH_CENTERS      1   /* Frame::SetPose of the window's keyframes: kf_center from kf_pose */
+#define LORB_KF_REFRESH_NORMAL_DEPTH 2   /* MapPoint::UpdateNormalAndDepth: normal, max_dist, min_dist */
+#define LORB_KF_REFRESH_DESCRIPTOR   4   /* MapPoint::ComputeDescriptor: desc */
+#define LORB_KF_REFRESH_ALL          7
+typedef struct lorb_kf_refresh_result {   /* device memory, like every record of the chain */
+  int32_t status;          /* 0; 1: the BA record's status is not 0 (or no good window), nothing else was written */
+  int32_t kf;              /* the window's keyframe */
+  int32_t n_points;        /* window points */
+  int32_t n_refreshed;     /* points whose rows were recomputed */
+  int32_t n_bad;           /* skipped: is_bad (:230) */
+  int32_t n_empty;         /* skipped: no observation (:238), or none inside the store */
+  int32_t n_obs_bad_slot;  /* observations skipped in both halves: a keyframe or slot outside the store */
+  int32_t n_desc_changed;  /* BITS of desc that changed, over all points */
+  int32_t n_centers;       /* camera centres recomputed: the window's poses, or 0 */
+} lorb_kf_refresh_result;
+
+/* Enqueued behind lorb_kf_store_local_ba_dev (or behind a bare lorb_kf_store_ba_gather_dev) and in front of
+ * lorb_kf_store_compact_dev.  frame supplies n_levels and scale_factors; d_ba_result is that call's record (status
+ * and written are read on the device); what is a non-empty OR of the LORB_KF_REFRESH_* flags.  The point set is the
+ * window the store last gathered (its header, local frames and l2g), read in place in device memory.  On the
+ * device, in this order:
+ *   a. Status: d_ba_result->status != 0 stores status = 1 and NOTHING else.  (1: the BA was a no-op; 3: there are no
+ *      points; 2 and 4 already failed on the host.)
+ *   b. Centres, with LORB_KF_REFRESH_CENTERS and only when d_ba_result->written == 1: SetPose(Tvec, Rvec) ->
+ *      UpdatePoseMat, src/frame.cpp:577-594.  For every local keyframe f = local[i], i < n_poses: Tcw =
+ *      pose_to_Tcw(kf_pose[f]), Twc = cv::Mat::inv() (lorb_pose_to_Tcw's and lorb_frame_pose_from_Tcw's arithmetic),
+ *      kf_center[f] = (Twc[3], Twc[7], Twc[11]).  Fixed frames and keyframes outside the window are not touched: the
+ *      reference moves only the window's frames.  As for Tcw_in of the local stage, the device's double sin / cos are
+ *      not libm's, so kf_center is DEFINED as what the store reports; a pose whose rvec is exactly 0 takes
+ *      Rodrigues' identity branch and has the host's bits.
+ *   c. Points.  For every window point i < n_points, g = l2g[i]: a point with is_bad[g] is skipped and counted in
+ *      n_bad (:230; a cull may have run since the gather); an empty observation list is skipped and counted in
+ *      n_empty (:238); an observation whose keyframe or slot lies outside the store is skipped in both halves and
+ *      counted in n_obs_bad_slot (a list with no other observation counts as empty).
+ *      UpdateNormalAndDepth (LORB_KF_REFRESH_NORMAL_DEPTH) over ALL of the point's observations in list order -- the
+ *      reference does not skip bad keyframes here -- OpenCV's arithmetic restated as the insertion's one-observation
+ *      form restates it, no FMA contraction: d = pos - kf_center[f] in float; nd = sqrt((double)dx dx + (double)dy dy
+ *      + (double)dz dz) in that order; sum += d * (float)(1.0 / nd), a float multiply and then a float add per
+ *      component, from 0, in list order; normal = sum * (float)(1.0 / (double)n).  mpRefKF is the FIRST entry of the
+ *      list: lists ascend by keyframe index and no operation of the store erases an observation of a live point, so
+ *      that is the keyframe that created the point (:23, and EraseObservation's mObservations.begin(), :147-148).
+ *      dist = (float)norm(pos - kf_center[ref]); max_dist = dist * scale_factors[octave of ref's slot, clamped to
+ *      [0, LORB_MAX_LEVELS)]; min_dist = max_dist / scale_factors[n_levels - 1]: the insertion's clamps.
+ *      ComputeDescriptor (LORB_KF_REFRESH_DESCRIPTOR) over the observations whose keyframe is not kf_bad (:77-78), in
+ *      list order, by lorb_compute_descriptor's rule: element (n - 1) / 2 of each sorted row of the all-pairs
+ *      Hamming matrix, self-distance included (:115-118); the smallest median wins, the first index on ties (:119).
+ *      desc[g] becomes that observation's kf_slot_desc row.  With no usable observation the descriptor STAYS (the
+ *      reference indexes an empty vector there).
+ *   d. The record.
+ * A point with one observation, created by an insertion, is a fixed point: the inputs are the ones its row was made
+ * from, and all four columns keep their bits.  Nothing else in the store changes: no pos, no list, no count, no
+ * flag, no life word; the tracker's slots keep their own copies of a descriptor; the BA's per-point scratch stays at
+ * rest.  No atomics: every point writes only its own row.
+ * Divergences: the four-argument MapPoint constructor (:26-49) leaves mpRefKF unset where this
+ * call takes the first observer; an adopted point's first observer is K, the keyframe that adopted it, not the
+ * frame whose tracker created it.
+ * LORB_E_INVALID, before anything is enqueued: a null argument, a store of another ctx, a store without geometry or
+ * without appearance, what zero or with an unknown bit, n_levels outside [1, LORB_MAX_LEVELS], no CURRENT window.
+ * Whether the window is current is a host flag: a gather sets it and lorb_kf_store_compact_dev clears it, because
+ * a compaction renumbers the points l2g names.  Returns LORB_OK for status 0 and 1.
+ * Asynchronous on the ctx stream: 3 kernel launches, the centres in front of the points, no stream synchronise, no
+ * device-to-host read and no host-to-device copy.
+ * Out of scope: the tracker's slot copies of a descriptor; a host-array form or a C++ adapter; KeyFramesCulling;
+ * running the BA on a second stream. */
+int lorb_kf_store_refresh_dev(lorb_ctx* ctx, lorb_kf_store* store, const lorb_frame_params* frame,
+                              const lorb_kf_ba_result* d_ba_result, int32_t what, lorb_kf_refresh_result* d_result);
+
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.
  * obs_frame[k] >= 0 : optimised pose index (PoseMPCost, src/bundle_adjust.cpp:293-301)

@@ -334,6 +334,20 @@ class KfCompactResult(C.Structure):  # lorb_kf_compact_result
                 ("n_bad_kept", C.c_int32), ("n_kf_slots_mapped", C.c_int32), ("n_gids_mapped", C.c_int32)]
 
 
+LORB_KF_REFRESH_CENTERS, LORB_KF_REFRESH_NORMAL_DEPTH, LORB_KF_REFRESH_DESCRIPTOR, LORB_KF_REFRESH_ALL = 1, 2, 4, 7
+
+
+class KfStoreAppearHost(C.Structure):  # lorb_kf_store_appear_host (host addresses)
+    _fields_ = [("n_kf", C.c_int32), ("n_kf_slots", C.c_int32), ("kf_slot_desc", C.c_void_p), ("kf_slot_octave", C.c_void_p),
+                ("kf_center", C.c_void_p)]
+
+
+class KfRefreshResult(C.Structure):  # lorb_kf_refresh_result
+    _fields_ = [("status", C.c_int32), ("kf", C.c_int32), ("n_points", C.c_int32), ("n_refreshed", C.c_int32),
+                ("n_bad", C.c_int32), ("n_empty", C.c_int32), ("n_obs_bad_slot", C.c_int32), ("n_desc_changed", C.c_int32),
+                ("n_centers", C.c_int32)]
+
+
 LM_STEP_NAMES = {0: "invalid", 1: "accepted", 2: "rejected", 3: "parameter_tol", 4: "function_tol"}
 LM_TRACE_CAP = 64
 

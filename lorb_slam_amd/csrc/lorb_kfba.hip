@@ -341,6 +341,7 @@ int gather(lorb_ctx* ctx, lorb_kf_store* S, const lorb_frame_params* frame, cons
   LORB_CHECK_LAUNCH(ctx);
   LORB_HIP(ctx, hipMemcpyAsync(S->h_hdr, S->ba_hdr, sizeof(Hdr), hipMemcpyDeviceToHost, st));
   LORB_HIP(ctx, lorb::spin_sync(ctx));
+  S->window_current = true;  // until a compaction renumbers the points (lorb_kf_store_refresh_dev)
   const Hdr& h = *S->h_hdr;
   if (h.status == 2)
     return lorb::set_error(ctx, LORB_E_UNSUPPORTED, "keyframe %d has more than %d local frames", h.kf, kMaxLocal);

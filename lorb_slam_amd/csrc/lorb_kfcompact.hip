@@ -298,6 +298,7 @@ int lorb_kf_store_compact_dev(lorb_ctx* ctx, lorb_kf_store* S, const int32_t* d_
   LORB_CHECK_LAUNCH(ctx);
   hipLaunchKernelGGL(k_kf_compact_back, dim3(back_blocks), dim3(kT), 0, st, a);
   LORB_CHECK_LAUNCH(ctx);
+  S->window_current = false;  // w_l2g may hold the old numbers (lorb_kf_store_refresh_dev refuses it)
   return LORB_OK;
 }
 

@@ -1,6 +1,7 @@
 // lorb_kfstore.h -- the keyframe store's object, shared by lorb_kfstore.hip (create / read / insertion),
 // lorb_kfba.hip (the local bundle adjustment fed from the store), lorb_kfcull.hip (the points' life and
-// MapPointsCulling) and lorb_kfcompact.hip (reclaiming the dead point rows).
+// MapPointsCulling), lorb_kfcompact.hip (reclaiming the dead point rows) and lorb_kfrefresh.hip (the appearance and
+// the refresh of the window's points).
 #pragma once
 
 #include "lorb_ba_slots.h"
@@ -49,6 +50,14 @@ struct KfCompactCtl {
   int pad[3];
 };
 
+// what the refresh's point kernel leaves per window point for the record (lorb_kfrefresh.hip): no atomics
+struct KfRefreshStat {
+  int kind;          // 0 refreshed, 1 bad, 2 no observation inside the store
+  int n_bad_slot;    // observations skipped: a keyframe or slot outside the store
+  int n_desc_bits;   // bits of desc that changed
+  int pad;
+};
+
 // the points' life as one block of ints, so that a kernel takes one pointer: visible | found | first_fid | recent
 // (bytes) over max_points each, kf_fid over max_kf, the frame word; every part starts on a multiple of 64 ints
 struct KfLife {
@@ -78,6 +87,8 @@ struct lorb_kf_store {
   int max_cov = 0;                                          // max_kf * max_kf
   int b_kf = 0, b_points = 0, b_obs = 0, b_slots = 0, b_cov = 0;  // the host's bounds on the true counts
   bool geom_ok = false;  // kf_pose / kf_slot_uv / obs_slot cover every keyframe the store holds
+  bool appear_ok = false;  // kf_slot_desc / kf_slot_octave / kf_center cover every keyframe the store holds
+  bool window_current = false;  // w_l2g names the points as they are numbered now: a gather sets it, a compaction clears it
   lorb::Arena mem;
   // the lorb_map_store arrays
   float *pos = nullptr, *normal = nullptr, *max_dist = nullptr, *min_dist = nullptr;
@@ -117,5 +128,11 @@ struct lorb_kf_store {
   int* cp_map = nullptr;       // per point: its rank among its tile's kept points, then its new index; -1: dropped
   uint8_t* cp_hold = nullptr;  // per point: bad and named by a keyframe slot or a gid table; at rest (0) between calls
   lorb::KfCompactCtl* cp_ctl = nullptr;
+  // the appearance (lorb_kfrefresh.hip): GetDescriptor and mvKeysUn[].octave per keyframe slot, parallel to
+  // kf_slot_point; mptCameraCenter per keyframe; the refresh's verdict per window point (lorb::KfRefreshStat)
+  uint8_t* kf_slot_desc = nullptr;
+  int* kf_slot_octave = nullptr;
+  float* kf_center = nullptr;
+  lorb::KfRefreshStat* rf_stat = nullptr;
   lorb::PlanSlots plans;
 };

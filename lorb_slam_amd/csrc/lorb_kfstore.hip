@@ -23,7 +23,8 @@
 //                     row with its keypoints, K's pose vector, the counts, the refer words and the record; a new
 //                     point's slot is left in owner[] for k_kf_obs_scatter; the points' life (lorb_kfcull.hip):
 //                     kf_fid[K], a new point's visible, found, first_fid, recent for created points and for an
-//                     old point K holds in two or more slots
+//                     old point K holds in two or more slots; K's appearance (lorb_kfrefresh.hip): the descriptor and
+//                     octave of every slot, the camera centre
 //   k_kf_obs_count    owners per 1024-point tile; the observation CSR (keyframes and slots) copied to scratch
 //   k_kf_obs_scatter  the CSR back with K (and its owning slot) appended to the owned points' lists, the new
 //                     points' lists {K} with the slot that made them
@@ -76,6 +77,10 @@ struct HeadArgs {
   int *kf_slot_off, *kf_slot_point;
   float *kf_pose, *kf_slot_uv;
   int* life;  // the points' life (lorb_kfcull.hip): one block, lorb::KfLife's layout over max_points / max_kf
+  // the appearance (lorb_kfrefresh.hip)
+  uint4* kf_slot_desc;
+  int* kf_slot_octave;
+  float* kf_center;
   int *cnt, *owner;
   Ctl* ctl;
   int* refer_kf;                  // or null
@@ -233,7 +238,11 @@ __global__ __launch_bounds__(kWalk) void k_kf_head(HeadArgs a) {
     a.kf_slot_point[S + j] = row;
     a.kf_slot_uv[2 * ((size_t)S + j)] = a.x[j];  // GetKp2d(j)
     a.kf_slot_uv[2 * ((size_t)S + j) + 1] = a.y[j];
+    a.kf_slot_desc[2 * ((size_t)S + j)] = a.fdesc[2 * (size_t)j];  // GetDescriptor(j), mvKeysUn[j].octave: what new_point reads
+    a.kf_slot_desc[2 * ((size_t)S + j) + 1] = a.fdesc[2 * (size_t)j + 1];
+    a.kf_slot_octave[(size_t)S + j] = a.octave[j];
   }
+  if (t < 3) a.kf_center[3 * (size_t)K + t] = Ow[t];  // mptCameraCenter
   if (t < 6) a.kf_pose[6 * (size_t)K + t] = a.pose->pose[t];  // mRvec | mTvec
   if (t == 0) {
     a.kf_bad[K] = 0;
@@ -642,6 +651,8 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
   A.add(&S->cp_desc, np * 32); A.add(&S->cp_locked, np); A.add(&S->cp_is_bad, np); A.add(&S->cp_recent, np);
   A.add(&S->cp_visible, np); A.add(&S->cp_found, np); A.add(&S->cp_first_fid, np);
   A.add(&S->cp_map, np); A.add(&S->cp_hold, np); A.add(&S->cp_ctl, (size_t)1);
+  // the appearance and the refresh's verdicts (lorb_kfrefresh.hip)
+  A.add(&S->kf_slot_desc, ns * 32); A.add(&S->kf_slot_octave, ns); A.add(&S->kf_center, nk * 3); A.add(&S->rf_stat, np);
   LORB_HIP(ctx, A.commit());
   {
     const lorb::KfLife life(S->life, caps->max_points, caps->max_kf);
@@ -708,6 +719,7 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
   LORB_HIP(ctx, hipStreamSynchronize(st));
   S->b_kf = cnt[0]; S->b_points = cnt[1]; S->b_obs = cnt[2]; S->b_slots = cnt[3]; S->b_cov = cnt[4];
   S->geom_ok = geom != nullptr || cnt[0] == 0;  // an empty store is complete: every insertion writes its own
+  S->appear_ok = cnt[0] == 0;                   // initial keyframes: lorb_kf_store_appear_write
   guard.s = nullptr;
   *out = S;
   return LORB_OK;
@@ -816,6 +828,7 @@ int lorb_kf_store_insert_dev(lorb_ctx* ctx, lorb_kf_store* S, const lorb_frame_p
   a.desc = reinterpret_cast<uint4*>(S->desc); a.locked = S->locked; a.is_bad = S->is_bad; a.kf_bad = S->kf_bad;
   a.kf_slot_off = S->kf_slot_off; a.kf_slot_point = S->kf_slot_point; a.kf_pose = S->kf_pose; a.kf_slot_uv = S->kf_slot_uv;
   a.life = S->life;
+  a.kf_slot_desc = reinterpret_cast<uint4*>(S->kf_slot_desc); a.kf_slot_octave = S->kf_slot_octave; a.kf_center = S->kf_center;
   a.cnt = S->cnt; a.owner = S->owner; a.ctl = S->ctl;
   a.refer_kf = d_refer_kf; a.update = d_update; a.rec = d_result;
   hipStream_t st = ctx->stream;

@@ -1032,41 +1032,6 @@ __global__ __launch_bounds__(1024) void k_slots_fill(SlotFill a, lorb::FrameCoun
 
 }  // namespace
 
-// cv::Mat::inv() for 4x4 CV_32F: hal::LU32f (partial pivoting, float), host and device
-__host__ __device__ bool lorb::inv4_lu32f(const float* Ain, float* out) {
-  float A[16], b[16];
-  for (int i = 0; i < 16; i++) A[i] = Ain[i];
-  for (int i = 0; i < 16; i++) b[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-  const float eps = 1.1920928955078125e-07f * 10;
-  for (int i = 0; i < 4; i++) {
-    int k = i;
-    for (int j = i + 1; j < 4; j++)
-      if (fabsf(A[j * 4 + i]) > fabsf(A[k * 4 + i])) k = j;
-    if (fabsf(A[k * 4 + i]) < eps) {
-      for (int j = 0; j < 16; j++) out[j] = 0.0f;
-      return false;
-    }
-    if (k != i) {
-      for (int j = i; j < 4; j++) { const float v = A[i * 4 + j]; A[i * 4 + j] = A[k * 4 + j]; A[k * 4 + j] = v; }
-      for (int j = 0; j < 4; j++) { const float v = b[i * 4 + j]; b[i * 4 + j] = b[k * 4 + j]; b[k * 4 + j] = v; }
-    }
-    const float dd = -1 / A[i * 4 + i];
-    for (int j = i + 1; j < 4; j++) {
-      const float alpha = A[j * 4 + i] * dd;
-      for (int kk = i + 1; kk < 4; kk++) A[j * 4 + kk] += alpha * A[i * 4 + kk];
-      for (int kk = 0; kk < 4; kk++) b[j * 4 + kk] += alpha * b[i * 4 + kk];
-    }
-  }
-  for (int i = 3; i >= 0; i--)
-    for (int j = 0; j < 4; j++) {
-      float s = b[i * 4 + j];
-      for (int k = i + 1; k < 4; k++) s -= A[i * 4 + k] * b[k * 4 + j];
-      b[i * 4 + j] = s / A[i * 4 + i];
-    }
-  for (int i = 0; i < 16; i++) out[i] = b[i];
-  return true;
-}
-
 namespace {
 using lorb::inv4_lu32f;
 

@@ -431,7 +431,9 @@ class KeyframeStore:
     of each observation) -- lorb_kf_store_create_geom.  geometry: the views of kf_pose, kf_slot_uv and obs_slot,
     kept apart from arrays.  life: the views of visible, found, first_fid, recent, kf_fid and the one-word
     frame_word (read_life / write_life; keyframe_observe and keyframe_cull work on them).  compact() reclaims the
-    rows of dead points (lorb_kf_store_compact_dev); the views stay valid, the indices in them change."""
+    rows of dead points (lorb_kf_store_compact_dev); the views stay valid, the indices in them change.
+    appearance: the views of kf_slot_desc, kf_slot_octave and kf_center (read_appearance / write_appearance; a store
+    made with keyframes needs write_appearance before keyframe_refresh)."""
     COUNTS =("n_kf", "n_points", "n_obs", "n_kf_slots", "n_cov", "n_conn")
     _COLS = dict(pos=(np.float32, 3), normal=(np.float32, 3), max_dist=(np.float32, 1), min_dist=(np.float32, 1),
                  desc=(np.uint8, 32), locked=(np.uint8, 1), is_bad=(np.uint8, 1))
@@ -463,6 +465,15 @@ class KeyframeStore:
                            cov_off=arr(v.cov_off, cap["n_kf"] + 1, np.int32), cov_kf=arr(v.cov_kf, self.max_cov, np.int32))
         self.geometry = self._geometry_views()
         self.life = self._life_views()
+        self.appearance = self._appearance_views()
+
+    def _appearance_views(self):
+        """lorb_kf_store_appear_view: kf_slot_desc, kf_slot_octave and kf_center over their whole capacity (no wait)."""
+        g = A.KfStoreAppearHost()
+        self.ctx.check(lib().lorb_kf_store_appear_view(self._p, C.byref(g)), "lorb_kf_store_appear_view")
+        return dict(kf_slot_desc=DeviceArrayView(self.ctx, g.kf_slot_desc, (g.n_kf_slots, 32), np.uint8),
+                    kf_slot_octave=DeviceArrayView(self.ctx, g.kf_slot_octave, (g.n_kf_slots,), np.int32),
+                    kf_center=DeviceArrayView(self.ctx, g.kf_center, (g.n_kf, 3), np.float32))
 
     def _life_views(self):
         """lorb_kf_store_life_view / _frame_word_view: visible, found, first_fid, recent, kf_fid over their whole
@@ -600,6 +611,43 @@ class KeyframeStore:
                 self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
                                                      C.c_size_t(arr.nbytes - at)), "memset")
 
+    _APPEAR = dict(kf_slot_desc=(np.uint8, 32), kf_slot_octave=(np.int32, 1), kf_center=(np.float32, 3))
+
+    def read_appearance(self):
+        """lorb_kf_store_appear_read (waits): dict(kf_slot_desc: n_kf_slots x 32, kf_slot_octave: n_kf_slots, kf_center:
+        n_kf x 3) -- the true rows, flat as the store keeps them."""
+        n = self.counts()
+        rows = dict(kf_slot_desc=n["n_kf_slots"], kf_slot_octave=n["n_kf_slots"], kf_center=n["n_kf"])
+        a = {k: np.zeros((rows[k], w) if w > 1 else rows[k], dt) for k, (dt, w) in self._APPEAR.items()}
+        h = A.KfStoreAppearHost(n["n_kf"], n["n_kf_slots"])
+        for k, v in a.items():
+            setattr(h, k, v.ctypes.data)
+        self.ctx.check(lib().lorb_kf_store_appear_read(self._p, C.byref(h)), "lorb_kf_store_appear_read")
+        return a
+
+    def write_appearance(self, app, n_kf=None, n_kf_slots=None):
+        """lorb_kf_store_appear_write (waits): replaces the true rows by every array of `app` that is given (keys of
+        read_appearance).  n_kf / n_kf_slots default to the true counts; they must equal them.  A store created with
+        keyframes has no appearance until one call has given all three."""
+        n = self.counts()
+        keep = {k: np.ascontiguousarray(app[k], dt).reshape((-1, w) if w > 1 else -1) for k, (dt, w) in self._APPEAR.items()
+                if app.get(k) is not None}
+        h = A.KfStoreAppearHost(n["n_kf"] if n_kf is None else int(n_kf), n["n_kf_slots"] if n_kf_slots is None else int(n_kf_slots))
+        for k, v in keep.items():
+            if len(v) != (h.n_kf if k == "kf_center" else h.n_kf_slots):
+                raise LorbError(f"appearance: {k} has {len(v)} rows")
+            setattr(h, k, v.ctypes.data)
+        self.ctx.check(lib().lorb_kf_store_appear_write(self._p, C.byref(h)), "lorb_kf_store_appear_write")
+
+    def fill_appearance(self, counts, value=ORB_SENTINEL):
+        """fill() for the appearance arrays: `value` bytes past the given true counts."""
+        start = dict(kf_slot_desc=counts["n_kf_slots"], kf_slot_octave=counts["n_kf_slots"], kf_center=counts["n_kf"])
+        for k, arr in self.appearance.items():
+            at = start[k] * (arr.nbytes // arr.shape[0])
+            if at < arr.nbytes:
+                self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
+                                                     C.c_size_t(arr.nbytes - at)), "memset")
+
     def fill_geometry(self, counts, value=ORB_SENTINEL):
         """fill() for the geometry arrays: `value` bytes past the given true counts."""
         start = dict(kf_pose=counts["n_kf"], kf_slot_uv=counts["n_kf_slots"], obs_slot=counts["n_obs"])
@@ -717,6 +765,27 @@ def keyframe_local_ba(ctx, store, fp, d_kf, record, d_src_status=None, opt=None,
 def keyframe_ba_result(record):
     """The A.KfBaResult in a device record buffer (waits for the stream)."""
     return A.KfBaResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfBaResult)])
+
+
+def keyframe_refresh_record(ctx):
+    """A device buffer for an A.KfRefreshResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
+    return _sentinel(ctx, C.sizeof(A.KfRefreshResult) + ORB_GUARD, np.uint8)
+
+
+def keyframe_refresh(ctx, store, fp, ba_record, record, what=A.LORB_KF_REFRESH_ALL):
+    """lorb_kf_store_refresh_dev enqueued and nothing else: the camera centres of the window's keyframes, then
+    UpdateNormalAndDepth and ComputeDescriptor over the points of the window the store last gathered, behind
+    keyframe_local_ba (or a gather alone) and in front of KeyframeStore.compact.  fp supplies n_levels and
+    scale_factors; ba_record: the device buffer that call wrote its A.KfBaResult to; what: an OR of
+    A.LORB_KF_REFRESH_*; record: a device buffer for the A.KfRefreshResult (keyframe_refresh_record)."""
+    fps = A.make_frame_params(fp)
+    ctx.check(lib().lorb_kf_store_refresh_dev(ctx.handle, store._p, C.byref(fps), ba_record.ptr, C.c_int32(int(what)), record.ptr),
+              "lorb_kf_store_refresh_dev")
+
+
+def keyframe_refresh_result(record):
+    """The A.KfRefreshResult in a device record buffer (waits for the stream)."""
+    return A.KfRefreshResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfRefreshResult)])
 
 
 def keyframe_observe_record(ctx):

@@ -27,7 +27,7 @@ namespace {
 
 using Hdr = lorb::KfBaHdr;
 static_assert(sizeof(Hdr) == 64, "the header is one 64-byte copy");
-constexpr int kT = 1024;                        // threads per workgroup = positions per tile
+constexpr int kT = lorb::kKfTile;               // threads per workgroup = positions per tile
 constexpr int kMaxLocal = lorb::kKfBaMaxLocal;  // local frames
 constexpr int kNoFirst = lorb::kKfBaNoFirst;
 constexpr int kRowMax = 4096;                   // the largest max_kf: a covisibility row in LDS
@@ -45,11 +45,9 @@ struct Store {  // what the gather reads of the store, and its scratch
   float *w_pose, *w_fixed_pose, *w_point, *w_uv;
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // keyframe f's slot row inside the S slots the store holds
 __device__ __forceinline__ void slot_row(const Store& s, int f, int S, int* lo, int* len) {
-  const int l0 = clampi(s.kf_slot_off[f], 0, S), l1 = clampi(s.kf_slot_off[f + 1], l0, S);
+  const auto [l0, l1] = lorb::kf_range(s.kf_slot_off, f, S);
   *lo = l0;
   *len = l1 - l0;
 }
@@ -76,7 +74,8 @@ __global__ __launch_bounds__(kT) void k_kfba_head(Store s, const int* d_kf, cons
   for (int f = t; f < kRowMax; f += kT) s_first[f] = 0x7fffffff;
   if (t == 0) s_tot = 0ull;
   __syncthreads();
-  const int lo = clampi(s.cov_off[kf], 0, NC), len = min(clampi(s.cov_off[kf + 1], lo, NC) - lo, kRowMax);
+  const auto [lo, hi] = lorb::kf_range(s.cov_off, kf, NC);
+  const int len = min(hi - lo, kRowMax);
   for (int q = t; q < len; q += kT) {
     const int f = s.cov_kf[lo + q];
     if ((unsigned)f < (unsigned)nk && f != kf && !s.kf_bad[f]) atomicMin(&s_first[f], q);
@@ -214,9 +213,8 @@ __global__ __launch_bounds__(kT) void k_kfba_points(Store s) {
   if (b * kT >= T) return;
   seq_load(s, h.C, &sq);
   const int n_tiles = (T + kT - 1) / kT;
-  int sum = 0, base, tot;
-  for (int i = t; i < b; i += kT) sum += s.tile[i];
-  lorb::block_excl_scan_1024(sum, wsum, &base);
+  int tot;
+  const int base = lorb::tile_base_1024(s.tile, b, wsum);
   const int q = b * kT + t;
   const int p = q < T ? seq_point(s, sq, h.C, q, h.n_pts, h.n_slots) : -1;
   const int own = p >= 0 && s.first[p] == q;  // a later position of p sees q or the word at rest: not its own
@@ -228,7 +226,7 @@ __global__ __launch_bounds__(kT) void k_kfba_points(Store s) {
 #pragma unroll
   for (int k = 0; k < 3; ++k) s.w_point[3 * (size_t)i + k] = s.pos[3 * (size_t)p + k];  // e. point_init
   const int O = h.n_obs_store;
-  const int lo = clampi(s.obs_off[p], 0, O), hi = clampi(s.obs_off[p + 1], lo, O);
+  const auto [lo, hi] = lorb::kf_range(s.obs_off, p, O);
   int n = 0, bad_kf = 0, bad_slot = 0;
   for (int o = lo; o < hi; ++o) {
     int f, at;
@@ -286,7 +284,7 @@ __global__ __launch_bounds__(kT) void k_kfba_obs(Store s) {
   const int O = h.n_obs_store;
   for (int i = blockIdx.x * kT + threadIdx.x; i < h.P; i += gridDim.x * kT) {
     const int p = s.l2g[i];
-    const int lo = clampi(s.obs_off[p], 0, O), hi = clampi(s.obs_off[p + 1], lo, O);
+    const auto [lo, hi] = lorb::kf_range(s.obs_off, p, O);
     int at = s.ooff[i];
     for (int o = lo; o < hi; ++o) {
       int f, uv;
@@ -317,11 +315,8 @@ Store store_args(const lorb_kf_store* S) {
 // the six launches, the header copy and the wait; LORB_E_UNSUPPORTED for status 2 and 4
 int gather(lorb_ctx* ctx, lorb_kf_store* S, const lorb_frame_params* frame, const int32_t* d_kf, const int32_t* d_src_status,
            lorb_kf_ba_result* d_result) {
-  if (!ctx || !S || !frame || !d_kf || !d_result) return LORB_E_INVALID;
-  if (S->ctx != ctx) return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store belongs to another context");
-  if (!S->geom_ok)
-    return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store has no geometry for its initial keyframes "
-                                                "(lorb_kf_store_create_geom)");
+  if (!frame || !d_kf || !d_result) return LORB_E_INVALID;
+  LORB_TRY(lorb::kf_enter(ctx, S, lorb::kKfNeedGeom));
   const Store s = store_args(S);
   hipStream_t st = ctx->stream;
   // grids from the host's bounds: the kernels read the true counts
@@ -392,8 +387,7 @@ int lorb_kf_store_local_ba_dev(lorb_ctx* ctx, lorb_kf_store* S, const lorb_frame
 int lorb_kf_ba_window_read(lorb_kf_store* S, const lorb_kf_ba_window_host* out) {
   if (!S || !out) return LORB_E_INVALID;
   lorb_ctx* ctx = S->ctx;
-  hipStream_t st = ctx->stream;
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const Hdr h = *S->h_hdr;
   if (h.status != 0 && h.status != 3) return lorb::set_error(ctx, LORB_E_INVALID, "no window was gathered (status %d)", h.status);
   const bool cams = out->local_kf || out->pose_init, fixed = out->fixed_kf || out->fixed_pose,
@@ -401,17 +395,16 @@ int lorb_kf_ba_window_read(lorb_kf_store* S, const lorb_kf_ba_window_host* out) 
   if ((cams && out->n_poses < h.C) || (fixed && out->n_fixed < h.F) || (pts && out->n_points < h.P) || (obs && out->n_obs < h.K))
     return lorb::set_error(ctx, LORB_E_INVALID, "an output array is smaller than the window (%d poses, %d fixed, %d points, "
                            "%d obs)", h.C, h.F, h.P, h.K);
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    return bytes && dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-  };
-  LORB_HIP(ctx, down(out->local_kf, S->w_local, (size_t)h.C * 4)); LORB_HIP(ctx, down(out->pose_init, S->w_pose, (size_t)h.C * 24));
-  LORB_HIP(ctx, down(out->fixed_kf, S->w_fixed, (size_t)h.F * 4));
-  LORB_HIP(ctx, down(out->fixed_pose, S->w_fixed_pose, (size_t)h.F * 24));
-  LORB_HIP(ctx, down(out->l2g, S->w_l2g, (size_t)h.P * 4)); LORB_HIP(ctx, down(out->point_init, S->w_point, (size_t)h.P * 12));
-  LORB_HIP(ctx, down(out->obs_point, S->w_obs_point, (size_t)h.K * 4));
-  LORB_HIP(ctx, down(out->obs_frame, S->w_obs_frame, (size_t)h.K * 4));
-  LORB_HIP(ctx, down(out->obs_uv, S->w_uv, (size_t)h.K * 8));
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_HIP(ctx, lorb::kf_down(S, out->local_kf, S->w_local, (size_t)h.C * 4));
+  LORB_HIP(ctx, lorb::kf_down(S, out->pose_init, S->w_pose, (size_t)h.C * 24));
+  LORB_HIP(ctx, lorb::kf_down(S, out->fixed_kf, S->w_fixed, (size_t)h.F * 4));
+  LORB_HIP(ctx, lorb::kf_down(S, out->fixed_pose, S->w_fixed_pose, (size_t)h.F * 24));
+  LORB_HIP(ctx, lorb::kf_down(S, out->l2g, S->w_l2g, (size_t)h.P * 4));
+  LORB_HIP(ctx, lorb::kf_down(S, out->point_init, S->w_point, (size_t)h.P * 12));
+  LORB_HIP(ctx, lorb::kf_down(S, out->obs_point, S->w_obs_point, (size_t)h.K * 4));
+  LORB_HIP(ctx, lorb::kf_down(S, out->obs_frame, S->w_obs_frame, (size_t)h.K * 4));
+  LORB_HIP(ctx, lorb::kf_down(S, out->obs_uv, S->w_uv, (size_t)h.K * 8));
+  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return LORB_OK;
 }
 

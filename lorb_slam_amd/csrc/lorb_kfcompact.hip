@@ -26,11 +26,9 @@
 
 namespace {
 
-constexpr int kT = 1024;  // threads per workgroup = points per tile (lorb_kfstore.hip's kTile)
+constexpr int kT = lorb::kKfTile;  // threads per workgroup = points per tile
 constexpr int kMaxGrid = 2048;  // workgroups of the grid-stride kernels
 using Ctl = lorb::KfCompactCtl;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 struct Table {
   int* gid;
@@ -42,17 +40,9 @@ struct CompactArgs {
   int max_points, max_kf_slots, n_tables;
   const int* src_status;  // or null
   int* cnt;
-  // the point rows
-  float *pos, *normal, *max_dist, *min_dist;
-  uint4* desc;
-  uint8_t *locked, *is_bad, *recent;
-  int *obs_off, *visible, *found, *first_fid;
+  lorb::KfPointRows row;  // the point rows
   int* kf_slot_point;
-  // staging
-  float *s_pos, *s_normal, *s_max_dist, *s_min_dist;
-  uint4* s_desc;
-  uint8_t *s_locked, *s_is_bad, *s_recent;
-  int *s_off, *s_visible, *s_found, *s_first_fid;
+  lorb::KfPointRows stage;  // their staging
   int *tile, *map;
   uint8_t* hold;
   Ctl* ctl;
@@ -88,14 +78,14 @@ __global__ __launch_bounds__(kT) void k_kf_compact_hold(CompactArgs a) {
   const long long i0 = (long long)blockIdx.x * kT + threadIdx.x, step = (long long)gridDim.x * kT;
   for (long long i = i0; i < S; i += step) {
     const int g = a.kf_slot_point[i];
-    if ((unsigned)g < (unsigned)P && a.is_bad[g]) a.hold[g] = 1;
+    if ((unsigned)g < (unsigned)P && a.row.is_bad[g]) a.hold[g] = 1;
   }
   for (int k = 0; k < a.n_tables; ++k) {
     const int* gid = a.tab[k].gid;
     const int n = a.tab[k].count[0];  // inside [0, n_max]: the head saw it
     for (long long j = i0; j < n; j += step) {
       const int g = gid[j];
-      if ((unsigned)g < (unsigned)P && a.is_bad[g]) a.hold[g] = 1;
+      if ((unsigned)g < (unsigned)P && a.row.is_bad[g]) a.hold[g] = 1;
     }
   }
 }
@@ -110,9 +100,9 @@ __global__ __launch_bounds__(kT) void k_kf_compact_count(CompactArgs a) {
   if ((long long)b * kT >= P) return;
   int keep = 0, bad = 0;
   if (p < P) {
-    const int lo = clampi(a.obs_off[p], 0, O), hi = clampi(a.obs_off[p + 1], lo, O);
+    const auto [lo, hi] = lorb::kf_range(a.row.obs_off, p, O);
     const int held = a.hold[p];
-    bad = a.is_bad[p] != 0;
+    bad = a.row.is_bad[p] != 0;
     keep = !(bad && hi == lo && !held);
     if (held) a.hold[p] = 0;  // back at rest
   }
@@ -142,31 +132,13 @@ __global__ __launch_bounds__(kT) void k_kf_compact_scatter(CompactArgs a) {
     if (a.d_map && p < P) a.d_map[p] = p;
     return;
   }
-  int s = 0, base;
-  for (int i = t; i < b; i += kT) s += a.tile[i];
-  lorb::block_excl_scan_1024(s, wsum, &base);
+  const int base = lorb::tile_base_1024(a.tile, b, wsum);
   if (p >= P) return;
   const int r = a.map[p], q = r < 0 ? -1 : base + r;
   a.map[p] = q;
   if (a.d_map) a.d_map[p] = q;
   if (q < 0) return;
-  const size_t i = (size_t)p, o = (size_t)q;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    a.s_pos[3 * o + k] = a.pos[3 * i + k];
-    a.s_normal[3 * o + k] = a.normal[3 * i + k];
-  }
-  a.s_max_dist[o] = a.max_dist[i];
-  a.s_min_dist[o] = a.min_dist[i];
-  a.s_desc[2 * o] = a.desc[2 * i];
-  a.s_desc[2 * o + 1] = a.desc[2 * i + 1];
-  a.s_locked[o] = a.locked[i];
-  a.s_is_bad[o] = a.is_bad[i];
-  a.s_recent[o] = a.recent[i];
-  a.s_off[o] = a.obs_off[i];
-  a.s_visible[o] = a.visible[i];
-  a.s_found[o] = a.found[i];
-  a.s_first_fid[o] = a.first_fid[i];
+  a.stage.copy_row((size_t)q, a.row, (size_t)p);
 }
 
 // e, f, g. the rows back, the fresh state behind them, the indices through the map, the true count
@@ -177,45 +149,13 @@ __global__ __launch_bounds__(kT) void k_kf_compact_back(CompactArgs a) {
   const int t = threadIdx.x;
   const int P = h.P, O = h.O, S = h.S, N = P - h.n_drop;
   const long long i0 = (long long)blockIdx.x * kT + t, step = (long long)gridDim.x * kT;
-  const uint4 z4 = make_uint4(0, 0, 0, 0);
   for (long long i = i0; i <= P; i += step) {
     const size_t o = (size_t)i;
     if (i < N) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        a.pos[3 * o + k] = a.s_pos[3 * o + k];
-        a.normal[3 * o + k] = a.s_normal[3 * o + k];
-      }
-      a.max_dist[o] = a.s_max_dist[o];
-      a.min_dist[o] = a.s_min_dist[o];
-      a.desc[2 * o] = a.s_desc[2 * o];
-      a.desc[2 * o + 1] = a.s_desc[2 * o + 1];
-      a.locked[o] = a.s_locked[o];
-      a.is_bad[o] = a.s_is_bad[o];
-      a.recent[o] = a.s_recent[o];
-      a.obs_off[o] = a.s_off[o];
-      a.visible[o] = a.s_visible[o];
-      a.found[o] = a.s_found[o];
-      a.first_fid[o] = a.s_first_fid[o];
+      a.row.copy_row(o, a.stage, o);
     } else {
-      a.obs_off[o] = i == N ? O : 0;
-      if (i < P) {  // what a fresh store has there
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          a.pos[3 * o + k] = 0.f;
-          a.normal[3 * o + k] = 0.f;
-        }
-        a.max_dist[o] = 0.f;
-        a.min_dist[o] = 0.f;
-        a.desc[2 * o] = z4;
-        a.desc[2 * o + 1] = z4;
-        a.locked[o] = 0;
-        a.is_bad[o] = 1;
-        a.recent[o] = 0;
-        a.visible[o] = 0;
-        a.found[o] = 0;
-        a.first_fid[o] = 0;
-      }
+      a.row.obs_off[o] = i == N ? O : 0;
+      if (i < P) a.row.fresh_row(o);  // what a fresh store has there
     }
   }
   lorb::I4 c = {{0, 0, 0, 0}}, tot;
@@ -250,8 +190,8 @@ extern "C" {
 
 int lorb_kf_store_compact_dev(lorb_ctx* ctx, lorb_kf_store* S, const int32_t* d_src_status, const lorb_kf_gid_table* tables,
                               int32_t n_tables, int32_t* d_map, lorb_kf_compact_result* d_result) {
-  if (!ctx || !S || !d_result) return LORB_E_INVALID;
-  if (S->ctx != ctx) return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store belongs to another context");
+  if (!d_result) return LORB_E_INVALID;
+  LORB_TRY(lorb::kf_enter(ctx, S));
   if (n_tables < 0 || n_tables > LORB_KF_COMPACT_MAX_TABLES)
     return lorb::set_error(ctx, LORB_E_INVALID, "%d gid tables: outside [0, %d]", n_tables, LORB_KF_COMPACT_MAX_TABLES);
   if (n_tables > 0 && !tables) return lorb::set_error(ctx, LORB_E_INVALID, "null tables");
@@ -273,14 +213,7 @@ int lorb_kf_store_compact_dev(lorb_ctx* ctx, lorb_kf_store* S, const int32_t* d_
     tab_max = std::max(tab_max, (size_t)tb.n_max);
   }
   a.max_points = S->cap.max_points; a.max_kf_slots = S->cap.max_kf_slots; a.src_status = d_src_status; a.cnt = S->cnt;
-  a.pos = S->pos; a.normal = S->normal; a.max_dist = S->max_dist; a.min_dist = S->min_dist;
-  a.desc = reinterpret_cast<uint4*>(S->desc); a.locked = S->locked; a.is_bad = S->is_bad; a.recent = S->recent;
-  a.obs_off = S->obs_off; a.visible = S->visible; a.found = S->found; a.first_fid = S->first_fid;
-  a.kf_slot_point = S->kf_slot_point;
-  a.s_pos = S->cp_pos; a.s_normal = S->cp_normal; a.s_max_dist = S->cp_max_dist; a.s_min_dist = S->cp_min_dist;
-  a.s_desc = reinterpret_cast<uint4*>(S->cp_desc); a.s_locked = S->cp_locked; a.s_is_bad = S->cp_is_bad;
-  a.s_recent = S->cp_recent; a.s_off = S->off2; a.s_visible = S->cp_visible; a.s_found = S->cp_found;
-  a.s_first_fid = S->cp_first_fid;
+  a.row = S->point_rows(); a.kf_slot_point = S->kf_slot_point; a.stage = S->stage_rows();
   a.tile = S->tile_cnt; a.map = S->cp_map; a.hold = S->cp_hold; a.ctl = S->cp_ctl; a.d_map = d_map; a.rec = d_result;
   hipStream_t st = ctx->stream;
   // grids from the host's bounds: the kernels read the true counts

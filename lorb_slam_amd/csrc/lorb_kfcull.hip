@@ -29,10 +29,8 @@
 
 namespace {
 
-constexpr int kT = 1024;  // threads per workgroup = points per tile (lorb_kfstore.hip's kTile)
+constexpr int kT = lorb::kKfTile;  // threads per workgroup = points per tile
 using Ctl = lorb::KfCullCtl;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 struct ObserveArgs {
   int frame_id, n_max, max_local, found_rule;
@@ -136,7 +134,7 @@ __global__ __launch_bounds__(kT) void k_kf_cull_verdict(CullArgs a) {
   if (t < cCount) s_c[t] = 0;
   __syncthreads();
   if (p < P && a.recent[p]) {
-    const int lo = clampi(a.obs_off[p], 0, O), hi = clampi(a.obs_off[p + 1], lo, O);
+    const auto [lo, hi] = lorb::kf_range(a.obs_off, p, O);
     const unsigned age = (unsigned)(h.cur - a.first_fid[p]);
     int kind;
     if (a.is_bad[p]) kind = cBadBefore;  // 1. it leaves the list
@@ -154,7 +152,7 @@ __global__ __launch_bounds__(kT) void k_kf_cull_verdict(CullArgs a) {
       for (int o = lo; o < hi; ++o) {  // Frame::EraseMapPoint(it->second), bad keyframe or not
         const int f = a.obs_kf[o], s = a.obs_slot[o];
         if ((unsigned)f >= (unsigned)nk) continue;
-        const int l0 = clampi(a.kf_slot_off[f], 0, S), l1 = clampi(a.kf_slot_off[f + 1], l0, S);
+        const auto [l0, l1] = lorb::kf_range(a.kf_slot_off, f, S);
         if ((unsigned)s >= (unsigned)(l1 - l0) || a.kf_slot_point[l0 + s] != p) continue;
         a.kf_slot_point[l0 + s] = -1;
         ++erased;
@@ -223,14 +221,13 @@ __global__ __launch_bounds__(kT) void k_kf_cull_scatter(CullArgs a) {
   const int t = threadIdx.x, b = blockIdx.x, P = h.P, O = h.O;
   if ((long long)b * kT > P) return;
   const int n_tiles = (P + kT - 1) / kT;
-  int s = 0, base, tot;
-  for (int i = t; i < min(b, n_tiles); i += kT) s += a.tile[i];
-  lorb::block_excl_scan_1024(s, wsum, &base);
+  int tot;
+  const int base = lorb::tile_base_1024(a.tile, min(b, n_tiles), wsum);
   const int p = b * kT + t;
   int lo = 0, hi = 0, gone = 0;
   if (p < P) {
-    lo = clampi(a.off2[p], 0, O);
-    hi = clampi(a.off2[p + 1], lo, O);
+    const lorb::KfRange r = lorb::kf_range(a.off2, p, O);
+    lo = r.lo; hi = r.hi;
     gone = a.mark[p] != 0;
   }
   const int before = base + lorb::block_excl_scan_1024(gone ? hi - lo : 0, wsum, &tot);
@@ -246,7 +243,7 @@ __global__ __launch_bounds__(kT) void k_kf_cull_scatter(CullArgs a) {
         }
     }
   } else if (p == P) {
-    a.obs_off[P] = max(clampi(a.off2[P], 0, O) - before, 0);
+    a.obs_off[P] = max(lorb::clampi(a.off2[P], 0, O) - before, 0);
   }
 }
 
@@ -258,17 +255,6 @@ CullArgs cull_args(const lorb_kf_store* S) {
   a.kf_slot_off = S->kf_slot_off; a.kf_slot_point = S->kf_slot_point;
   a.off2 = S->off2; a.kf2 = S->kf2; a.slot2 = S->slot2; a.tile = S->tile_cnt; a.ctl = S->cull_ctl;
   return a;
-}
-
-// the true n_kf and n_points (one copy, one wait)
-int true_counts(lorb_kf_store* S, int* nk, int* np) {
-  lorb_ctx* ctx = S->ctx;
-  int32_t cnt[6];
-  LORB_HIP(ctx, hipMemcpyAsync(cnt, S->cnt, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
-  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *nk = cnt[0];
-  *np = cnt[1];
-  return LORB_OK;
 }
 
 }  // namespace
@@ -290,28 +276,27 @@ int lorb_kf_store_frame_word_view(const lorb_kf_store* S, int32_t** d_word) {
 int lorb_kf_store_life_read(lorb_kf_store* S, const lorb_kf_store_life_host* h) {
   if (!S || !h) return LORB_E_INVALID;
   lorb_ctx* ctx = S->ctx;
-  hipStream_t st = ctx->stream;
-  int nk, np;
-  LORB_TRY(true_counts(S, &nk, &np));
+  int32_t cnt[6];
+  LORB_TRY(lorb::kf_true_counts(S, cnt));
+  const int nk = cnt[0], np = cnt[1];
   const bool pts = h->visible || h->found || h->first_fid || h->recent;
   if ((pts && h->n_points < np) || (h->kf_fid && h->n_kf < nk))
     return lorb::set_error(ctx, LORB_E_INVALID, "an output array is smaller than the store's count (%d kf, %d points)", nk, np);
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    return bytes && dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-  };
-  LORB_HIP(ctx, down(h->visible, S->visible, (size_t)np * 4)); LORB_HIP(ctx, down(h->found, S->found, (size_t)np * 4));
-  LORB_HIP(ctx, down(h->first_fid, S->first_fid, (size_t)np * 4)); LORB_HIP(ctx, down(h->recent, S->recent, (size_t)np));
-  LORB_HIP(ctx, down(h->kf_fid, S->kf_fid, (size_t)nk * 4));
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_HIP(ctx, lorb::kf_down(S, h->visible, S->visible, (size_t)np * 4));
+  LORB_HIP(ctx, lorb::kf_down(S, h->found, S->found, (size_t)np * 4));
+  LORB_HIP(ctx, lorb::kf_down(S, h->first_fid, S->first_fid, (size_t)np * 4));
+  LORB_HIP(ctx, lorb::kf_down(S, h->recent, S->recent, (size_t)np));
+  LORB_HIP(ctx, lorb::kf_down(S, h->kf_fid, S->kf_fid, (size_t)nk * 4));
+  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return LORB_OK;
 }
 
 int lorb_kf_store_life_write(lorb_kf_store* S, const lorb_kf_store_life_host* h) {
   if (!S || !h) return LORB_E_INVALID;
   lorb_ctx* ctx = S->ctx;
-  hipStream_t st = ctx->stream;
-  int nk, np;
-  LORB_TRY(true_counts(S, &nk, &np));
+  int32_t cnt[6];
+  LORB_TRY(lorb::kf_true_counts(S, cnt));
+  const int nk = cnt[0], np = cnt[1];
   if (h->n_kf != nk || h->n_points != np)
     return lorb::set_error(ctx, LORB_E_INVALID, "life: counts %d / %d differ from the store's %d / %d (kf, points)", h->n_kf,
                            h->n_points, nk, np);
@@ -321,13 +306,12 @@ int lorb_kf_store_life_write(lorb_kf_store* S, const lorb_kf_store_life_host* h)
     if (h->found && h->found[p] < 0)
       return lorb::set_error(ctx, LORB_E_INVALID, "life: found[%d] = %d must not be negative", p, h->found[p]);
   }
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    return bytes && src ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-  LORB_HIP(ctx, up(S->visible, h->visible, (size_t)np * 4)); LORB_HIP(ctx, up(S->found, h->found, (size_t)np * 4));
-  LORB_HIP(ctx, up(S->first_fid, h->first_fid, (size_t)np * 4)); LORB_HIP(ctx, up(S->recent, h->recent, (size_t)np));
-  LORB_HIP(ctx, up(S->kf_fid, h->kf_fid, (size_t)nk * 4));
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_HIP(ctx, lorb::kf_up(S, S->visible, h->visible, (size_t)np * 4));
+  LORB_HIP(ctx, lorb::kf_up(S, S->found, h->found, (size_t)np * 4));
+  LORB_HIP(ctx, lorb::kf_up(S, S->first_fid, h->first_fid, (size_t)np * 4));
+  LORB_HIP(ctx, lorb::kf_up(S, S->recent, h->recent, (size_t)np));
+  LORB_HIP(ctx, lorb::kf_up(S, S->kf_fid, h->kf_fid, (size_t)nk * 4));
+  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return LORB_OK;
 }
 
@@ -336,9 +320,9 @@ int lorb_kf_store_observe_dev(lorb_ctx* ctx, lorb_kf_store* S, int32_t frame_id,
                               const int32_t* d_cur_slot_id, const lorb_local_map_arrays* lmap,
                               const lorb_local_map_result* d_update, const uint8_t* d_in_view,
                               const int32_t* d_local_status, int32_t found_rule, lorb_kf_observe_result* d_result) {
-  if (!ctx || !S || !d_cur || !d_cur_slots || !d_cur_slot_gid || !d_cur_slot_id || !lmap || !d_update || !d_in_view || !d_result)
+  if (!d_cur || !d_cur_slots || !d_cur_slot_gid || !d_cur_slot_id || !lmap || !d_update || !d_in_view || !d_result)
     return LORB_E_INVALID;
-  if (S->ctx != ctx) return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store belongs to another context");
+  LORB_TRY(lorb::kf_enter(ctx, S));
   if (n_max_cur < 1) return lorb::set_error(ctx, LORB_E_INVALID, "bound %d must be positive", n_max_cur);
   if (found_rule != LORB_KF_FOUND_NEVER && found_rule != LORB_KF_FOUND_SLOTS)
     return lorb::set_error(ctx, LORB_E_INVALID, "unknown found rule %d", found_rule);
@@ -357,11 +341,8 @@ int lorb_kf_store_observe_dev(lorb_ctx* ctx, lorb_kf_store* S, int32_t frame_id,
 int lorb_kf_store_cull_dev(lorb_ctx* ctx, lorb_kf_store* S, const int32_t* d_kf, const int32_t* d_src_status,
                            const lorb_kf_cull_params* par, const lorb_frame_out* d_cur, int32_t n_max_cur,
                            const lorb_frame_slots* d_cur_slots, int32_t* d_cur_slot_gid, lorb_kf_cull_result* d_result) {
-  if (!ctx || !S || !d_kf || !par || !d_result) return LORB_E_INVALID;
-  if (S->ctx != ctx) return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store belongs to another context");
-  if (!S->geom_ok)
-    return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store has no geometry for its initial keyframes "
-                                                "(lorb_kf_store_create_geom)");
+  if (!d_kf || !par || !d_result) return LORB_E_INVALID;
+  LORB_TRY(lorb::kf_enter(ctx, S, lorb::kKfNeedGeom));
   if (par->age_obs < 0 || par->age_out < 0 || std::isnan(par->min_found_ratio))
     return lorb::set_error(ctx, LORB_E_INVALID, "cull parameters: ratio %g, ages %d / %d", (double)par->min_found_ratio,
                            par->age_obs, par->age_out);

@@ -48,7 +48,7 @@ struct Args {
   lorb_kf_refresh_result* rec;
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+using lorb::clampi;
 
 // LDS written by some lanes of a wavefront is read by others
 __device__ __forceinline__ void wave_sync() {
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kT) void k_kfr_points(Args a) {
     if (lane == 0) a.stat[i] = st;
     return;
   }
-  const int lo = clampi(a.obs_off[g], 0, O), hi = clampi(a.obs_off[g + 1], lo, O);
+  const auto [lo, hi] = lorb::kf_range(a.obs_off, g, O);
   const float px = a.pos[3 * (size_t)g], py = a.pos[3 * (size_t)g + 1], pz = a.pos[3 * (size_t)g + 2];
   const unsigned long long below = (1ull << lane) - 1ull;
   float sx = 0.0f, sy = 0.0f, sz = 0.0f;  // the sum, the same in every lane
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(kT) void k_kfr_points(Args a) {
     if (o < hi) {
       f = a.obs_kf[o];
       if ((unsigned)f < (unsigned)nk) {
-        const int l0 = clampi(a.kf_slot_off[f], 0, S), l1 = clampi(a.kf_slot_off[f + 1], l0, S);
+        const auto [l0, l1] = lorb::kf_range(a.kf_slot_off, f, S);
         const int j = a.obs_slot[o];
         if ((unsigned)j < (unsigned)(l1 - l0)) {
           in = true;
@@ -256,17 +256,6 @@ __global__ __launch_bounds__(1024) void k_kfr_record(Args a) {
   a.rec->n_desc_changed = tot2.v[0];
 }
 
-// the true n_kf and n_kf_slots (one copy, one wait)
-int true_counts(lorb_kf_store* S, int* nk, int* ns) {
-  lorb_ctx* ctx = S->ctx;
-  int32_t cnt[6];
-  LORB_HIP(ctx, hipMemcpyAsync(cnt, S->cnt, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
-  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *nk = cnt[0];
-  *ns = cnt[3];
-  return LORB_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -280,27 +269,24 @@ int lorb_kf_store_appear_view(const lorb_kf_store* S, lorb_kf_store_appear_host*
 int lorb_kf_store_appear_read(lorb_kf_store* S, const lorb_kf_store_appear_host* h) {
   if (!S || !h) return LORB_E_INVALID;
   lorb_ctx* ctx = S->ctx;
-  hipStream_t st = ctx->stream;
-  int nk, ns;
-  LORB_TRY(true_counts(S, &nk, &ns));
+  int32_t cnt[6];
+  LORB_TRY(lorb::kf_true_counts(S, cnt));
+  const int nk = cnt[0], ns = cnt[3];
   if (((h->kf_slot_desc || h->kf_slot_octave) && h->n_kf_slots < ns) || (h->kf_center && h->n_kf < nk))
     return lorb::set_error(ctx, LORB_E_INVALID, "an output array is smaller than the store's count (%d kf, %d slots)", nk, ns);
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    return bytes && dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-  };
-  LORB_HIP(ctx, down(h->kf_slot_desc, S->kf_slot_desc, (size_t)ns * 32));
-  LORB_HIP(ctx, down(h->kf_slot_octave, S->kf_slot_octave, (size_t)ns * 4));
-  LORB_HIP(ctx, down(h->kf_center, S->kf_center, (size_t)nk * 12));
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_HIP(ctx, lorb::kf_down(S, h->kf_slot_desc, S->kf_slot_desc, (size_t)ns * 32));
+  LORB_HIP(ctx, lorb::kf_down(S, h->kf_slot_octave, S->kf_slot_octave, (size_t)ns * 4));
+  LORB_HIP(ctx, lorb::kf_down(S, h->kf_center, S->kf_center, (size_t)nk * 12));
+  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return LORB_OK;
 }
 
 int lorb_kf_store_appear_write(lorb_kf_store* S, const lorb_kf_store_appear_host* h) {
   if (!S || !h) return LORB_E_INVALID;
   lorb_ctx* ctx = S->ctx;
-  hipStream_t st = ctx->stream;
-  int nk, ns;
-  LORB_TRY(true_counts(S, &nk, &ns));
+  int32_t cnt[6];
+  LORB_TRY(lorb::kf_true_counts(S, cnt));
+  const int nk = cnt[0], ns = cnt[3];
   if (h->n_kf != nk || h->n_kf_slots != ns)
     return lorb::set_error(ctx, LORB_E_INVALID, "appearance: counts %d / %d differ from the store's %d / %d (kf, slots)", h->n_kf,
                            h->n_kf_slots, nk, ns);
@@ -309,13 +295,10 @@ int lorb_kf_store_appear_write(lorb_kf_store* S, const lorb_kf_store_appear_host
       if (h->kf_slot_octave[s] < 0 || h->kf_slot_octave[s] >= LORB_MAX_LEVELS)
         return lorb::set_error(ctx, LORB_E_INVALID, "appearance: kf_slot_octave[%d] = %d is outside [0, %d)", s,
                                h->kf_slot_octave[s], LORB_MAX_LEVELS);
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    return bytes && src ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-  LORB_HIP(ctx, up(S->kf_slot_desc, h->kf_slot_desc, (size_t)ns * 32));
-  LORB_HIP(ctx, up(S->kf_slot_octave, h->kf_slot_octave, (size_t)ns * 4));
-  LORB_HIP(ctx, up(S->kf_center, h->kf_center, (size_t)nk * 12));
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_HIP(ctx, lorb::kf_up(S, S->kf_slot_desc, h->kf_slot_desc, (size_t)ns * 32));
+  LORB_HIP(ctx, lorb::kf_up(S, S->kf_slot_octave, h->kf_slot_octave, (size_t)ns * 4));
+  LORB_HIP(ctx, lorb::kf_up(S, S->kf_center, h->kf_center, (size_t)nk * 12));
+  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // complete once a call has given every array that has rows
   if ((ns == 0 || (h->kf_slot_desc && h->kf_slot_octave)) && (nk == 0 || h->kf_center)) S->appear_ok = true;
   return LORB_OK;
@@ -323,14 +306,8 @@ int lorb_kf_store_appear_write(lorb_kf_store* S, const lorb_kf_store_appear_host
 
 int lorb_kf_store_refresh_dev(lorb_ctx* ctx, lorb_kf_store* S, const lorb_frame_params* frame,
                               const lorb_kf_ba_result* d_ba_result, int32_t what, lorb_kf_refresh_result* d_result) {
-  if (!ctx || !S || !frame || !d_ba_result || !d_result) return LORB_E_INVALID;
-  if (S->ctx != ctx) return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store belongs to another context");
-  if (!S->geom_ok)
-    return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store has no geometry for its initial keyframes "
-                                                "(lorb_kf_store_create_geom)");
-  if (!S->appear_ok)
-    return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store has no appearance for its initial keyframes "
-                                                "(lorb_kf_store_appear_write)");
+  if (!frame || !d_ba_result || !d_result) return LORB_E_INVALID;
+  LORB_TRY(lorb::kf_enter(ctx, S, lorb::kKfNeedGeom | lorb::kKfNeedAppear));
   if (what == 0 || (what & ~kAll)) return lorb::set_error(ctx, LORB_E_INVALID, "refresh flags 0x%x: empty or unknown", what);
   if (frame->n_levels < 1 || frame->n_levels > LORB_MAX_LEVELS)
     return lorb::set_error(ctx, LORB_E_INVALID, "n_levels %d outside [1, %d]", frame->n_levels, LORB_MAX_LEVELS);

@@ -1,7 +1,9 @@
-// lorb_kfstore.h -- the keyframe store's object, shared by lorb_kfstore.hip (create / read / insertion),
-// lorb_kfba.hip (the local bundle adjustment fed from the store), lorb_kfcull.hip (the points' life and
-// MapPointsCulling), lorb_kfcompact.hip (reclaiming the dead point rows) and lorb_kfrefresh.hip (the appearance and
-// the refresh of the window's points).
+// lorb_kfstore.h -- the keyframe store's object and what its units share.  The units: lorb_kfstore.hip (create /
+// read / insertion, and the shared host helpers declared at the end of this file), lorb_kfba.hip (the local bundle
+// adjustment fed from the store), lorb_kfcull.hip (the points' life and MapPointsCulling), lorb_kfcompact.hip
+// (reclaiming the dead point rows) and lorb_kfrefresh.hip (the appearance and the refresh of the window's points).
+// Shared on the device: clampi, kf_range (a clamped CSR row), tile_base_1024 (the earlier tiles' sum), kKfTile and
+// KfPointRows -- THE list of the per-point arrays: a new per-point array of the store is added there.
 #pragma once
 
 #include "lorb_ba_slots.h"
@@ -19,6 +21,68 @@ struct KfCtl {
   int n_connected;       // length of K's ordered list
   int pad;
 };
+
+constexpr int kKfTile = 1024;  // points per scan tile = threads per workgroup of the tiled kernels
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// row i of a CSR (a point's observation list, a keyframe's slot row, a covisibility row) inside the n entries the
+// store holds: [lo, hi), empty rather than outside whatever the offsets say
+struct KfRange {
+  int lo, hi;
+};
+__device__ __forceinline__ KfRange kf_range(const int* off, int i, int n) {
+  const int lo = clampi(off[i], 0, n);
+  return {lo, clampi(off[i + 1], lo, n)};
+}
+
+// the sum of tile[0 .. n) in every thread of a 1024-thread workgroup: the rows in front of tile n.  Every thread
+// calls it; it holds block_excl_scan_1024's two barriers.  wsum: __shared__ int[16]
+__device__ __forceinline__ int tile_base_1024(const int* tile, int n, int* wsum) {
+  int s = 0, base;
+  for (int i = threadIdx.x; i < n; i += kKfTile) s += tile[i];
+  block_excl_scan_1024(s, wsum, &base);
+  return base;
+}
+
+// The row of a point: every per-point array of the store, live (lorb_kf_store::point_rows) or a compaction's
+// staging (stage_rows).  A new per-point array is added here -- member, copy_row, fresh_row, kStagedBytes -- and
+// in the two builders and create_store's allocation below.
+struct KfPointRows {
+  float *pos, *normal, *max_dist, *min_dist;
+  uint4* desc;
+  uint8_t *locked, *is_bad, *recent;
+  int *obs_off, *visible, *found, *first_fid;
+  // bytes of one row without obs_off, whose staging is the insertion's off2: create_store's "79 bytes of rows"
+  static constexpr size_t kStagedBytes = 2 * 12 + 2 * 4 + 32 + 3 * 1 + 3 * 4;
+  // row dst of this set = row i of src
+  __device__ __forceinline__ void copy_row(size_t dst, const KfPointRows& src, size_t i) const {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      pos[3 * dst + k] = src.pos[3 * i + k];
+      normal[3 * dst + k] = src.normal[3 * i + k];
+    }
+    max_dist[dst] = src.max_dist[i]; min_dist[dst] = src.min_dist[i];
+    desc[2 * dst] = src.desc[2 * i]; desc[2 * dst + 1] = src.desc[2 * i + 1];
+    locked[dst] = src.locked[i]; is_bad[dst] = src.is_bad[i]; recent[dst] = src.recent[i];
+    obs_off[dst] = src.obs_off[i];
+    visible[dst] = src.visible[i]; found[dst] = src.found[i]; first_fid[dst] = src.first_fid[i];
+  }
+  // what a fresh store has in row o: zeros, is_bad = 1.  obs_off is the caller's.
+  __device__ __forceinline__ void fresh_row(size_t o) const {
+    const uint4 z4 = make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      pos[3 * o + k] = 0.f;
+      normal[3 * o + k] = 0.f;
+    }
+    max_dist[o] = 0.f; min_dist[o] = 0.f;
+    desc[2 * o] = z4; desc[2 * o + 1] = z4;
+    locked[o] = 0; is_bad[o] = 1; recent[o] = 0;
+    visible[o] = 0; found[o] = 0; first_fid[o] = 0;
+  }
+};
+static_assert(KfPointRows::kStagedBytes == 79, "create_store's staging comment states the row's bytes");
 
 constexpr int kKfBaMaxLocal = 128;  // the device plans' camera limit
 constexpr int kKfBaNoFirst = 0x7f7f7f7f;  // ba_first[] at rest (a memset of 0x7f); above every sequence position
@@ -135,4 +199,28 @@ struct lorb_kf_store {
   float* kf_center = nullptr;
   lorb::KfRefreshStat* rf_stat = nullptr;
   lorb::PlanSlots plans;
+  // the point rows where they live, and a compaction's staging of them
+  lorb::KfPointRows point_rows() const {
+    return {pos, normal, max_dist, min_dist, reinterpret_cast<uint4*>(desc), locked, is_bad, recent, obs_off, visible, found,
+            first_fid};
+  }
+  lorb::KfPointRows stage_rows() const {
+    return {cp_pos, cp_normal, cp_max_dist, cp_min_dist, reinterpret_cast<uint4*>(cp_desc), cp_locked, cp_is_bad, cp_recent,
+            off2, cp_visible, cp_found, cp_first_fid};
+  }
 };
+
+// the host helpers the units share (lorb_kfstore.hip)
+namespace lorb {
+
+// the store's six true counts (n_kf, n_points, n_obs, n_kf_slots, n_cov, n_conn): one copy to the host, one wait
+int kf_true_counts(lorb_kf_store* S, int32_t cnt[6]);
+// one asynchronous copy to / from the device on the store's stream; a null host pointer or zero bytes is skipped
+hipError_t kf_up(const lorb_kf_store* S, void* dst, const void* host, size_t bytes);
+hipError_t kf_down(const lorb_kf_store* S, void* host, const void* src, size_t bytes);
+// the entry check of the enqueued calls: LORB_E_INVALID for a null ctx or store and for a store of another context;
+// with kKfNeedGeom / kKfNeedAppear also for a store whose initial keyframes lack the geometry / the appearance
+enum { kKfNeedGeom = 1, kKfNeedAppear = 2 };
+int kf_enter(lorb_ctx* ctx, const lorb_kf_store* S, int need = 0);
+
+}  // namespace lorb

@@ -42,7 +42,7 @@
 namespace {
 
 constexpr int kWalk = 1024;      // threads of the one-workgroup walks over the slots
-constexpr int kTile = 1024;      // points per scan tile = threads per workgroup
+constexpr int kTile = lorb::kKfTile;  // points per scan tile = threads per workgroup
 constexpr int kCountWin = 1024;  // keyframes whose counters are held in LDS at a time
 constexpr int kSortMax = 4096;   // keys of one row sort in LDS = the largest max_kf
 constexpr int kNoOwner = 0x7f7f7f7f;  // owner[] at rest (a memset of 0x7f); above every slot index
@@ -107,7 +107,7 @@ __device__ __forceinline__ void new_point(const HeadArgs& a, int at, const float
   const float dx = p[0] - Ow[0], dy = p[1] - Ow[1], dz = p[2] - Ow[2];
   const double nd = sqrt((double)dx * (double)dx + (double)dy * (double)dy + (double)dz * (double)dz);
   const float inv = (float)(1.0 / nd), dist = (float)nd;
-  const int lvl = min(max(octave, 0), LORB_MAX_LEVELS - 1), top = min(max(a.fp.n_levels - 1, 0), LORB_MAX_LEVELS - 1);
+  const int lvl = lorb::clampi(octave, 0, LORB_MAX_LEVELS - 1), top = lorb::clampi(a.fp.n_levels - 1, 0, LORB_MAX_LEVELS - 1);
   const float mx = dist * a.fp.scale_factors[lvl];
   const size_t r = (size_t)at;
   a.pos[3 * r] = p[0]; a.pos[3 * r + 1] = p[1]; a.pos[3 * r + 2] = p[2];
@@ -288,9 +288,8 @@ __global__ __launch_bounds__(kTile) void k_kf_obs_scatter(const Ctl* ctl, int* o
   const int P = ctl->P, O = ctl->O, K = ctl->K, n_add = ctl->n_obs_add, n_new = ctl->n_new;
   if ((long long)b * kTile > (long long)P + n_new) return;
   const int n_tiles = (P + kTile - 1) / kTile;
-  int s = 0, base, tot;
-  for (int i = t; i < min(b, n_tiles); i += kTile) s += tile_cnt[i];
-  lorb::block_excl_scan_1024(s, wsum, &base);
+  int tot;
+  const int base = lorb::tile_base_1024(tile_cnt, min(b, n_tiles), wsum);
   const int p = b * kTile + t;
   const int f = p < P && owner[p] != kNoOwner;
   const int before = base + lorb::block_excl_scan_1024(f, wsum, &tot);
@@ -542,6 +541,38 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
 
 }  // namespace
 
+// the host helpers the store's units share (lorb_kfstore.h)
+namespace lorb {
+
+int kf_true_counts(lorb_kf_store* S, int32_t cnt[6]) {
+  lorb_ctx* ctx = S->ctx;
+  LORB_HIP(ctx, hipMemcpyAsync(cnt, S->cnt, 6 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return LORB_OK;
+}
+
+hipError_t kf_up(const lorb_kf_store* S, void* dst, const void* host, size_t bytes) {
+  return bytes && host ? hipMemcpyAsync(dst, host, bytes, hipMemcpyHostToDevice, S->ctx->stream) : hipSuccess;
+}
+
+hipError_t kf_down(const lorb_kf_store* S, void* host, const void* src, size_t bytes) {
+  return bytes && host ? hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, S->ctx->stream) : hipSuccess;
+}
+
+int kf_enter(lorb_ctx* ctx, const lorb_kf_store* S, int need) {
+  if (!ctx || !S) return LORB_E_INVALID;
+  if (S->ctx != ctx) return set_error(ctx, LORB_E_INVALID, "the keyframe store belongs to another context");
+  if ((need & kKfNeedGeom) && !S->geom_ok)
+    return set_error(ctx, LORB_E_INVALID, "the keyframe store has no geometry for its initial keyframes "
+                                          "(lorb_kf_store_create_geom)");
+  if ((need & kKfNeedAppear) && !S->appear_ok)
+    return set_error(ctx, LORB_E_INVALID, "the keyframe store has no appearance for its initial keyframes "
+                                          "(lorb_kf_store_appear_write)");
+  return LORB_OK;
+}
+
+}  // namespace lorb
+
 extern "C" {
 
 int lorb_kf_store_destroy(lorb_kf_store* S) {
@@ -578,21 +609,16 @@ int lorb_kf_store_geom_view(const lorb_kf_store* S, lorb_kf_store_geom_host* v) 
 int lorb_kf_store_geom_read(lorb_kf_store* S, const lorb_kf_store_geom_host* g) {
   if (!S || !g) return LORB_E_INVALID;
   lorb_ctx* ctx = S->ctx;
-  hipStream_t st = ctx->stream;
   int32_t cnt[6];
-  LORB_HIP(ctx, hipMemcpyAsync(cnt, S->cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_TRY(lorb::kf_true_counts(S, cnt));
   const int nk = cnt[0], no = cnt[2], ns = cnt[3];
   if ((g->kf_pose && g->n_kf < nk) || (g->kf_slot_uv && g->n_kf_slots < ns) || (g->obs_slot && g->n_obs < no))
     return lorb::set_error(ctx, LORB_E_INVALID, "an output array is smaller than the store's count (%d kf, %d slots, %d obs)", nk,
                            ns, no);
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    return bytes && dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-  };
-  LORB_HIP(ctx, down(g->kf_pose, S->kf_pose, (size_t)nk * 24));
-  LORB_HIP(ctx, down(g->kf_slot_uv, S->kf_slot_uv, (size_t)ns * 8));
-  LORB_HIP(ctx, down(g->obs_slot, S->obs_slot, (size_t)no * 4));
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_HIP(ctx, lorb::kf_down(S, g->kf_pose, S->kf_pose, (size_t)nk * 24));
+  LORB_HIP(ctx, lorb::kf_down(S, g->kf_slot_uv, S->kf_slot_uv, (size_t)ns * 8));
+  LORB_HIP(ctx, lorb::kf_down(S, g->obs_slot, S->obs_slot, (size_t)no * 4));
+  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return LORB_OK;
 }
 
@@ -646,7 +672,8 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
   A.add(&S->w_pose, nl * 6); A.add(&S->w_fixed_pose, nk * 6); A.add(&S->w_point, np * 3); A.add(&S->w_uv, no * 2);
   // the points' life and the cull's scratch (lorb_kfcull.hip)
   A.add(&S->life, lorb::KfLife::ints(caps->max_points, caps->max_kf)); A.add(&S->cull_mark, np); A.add(&S->cull_ctl, (size_t)1);
-  // a compaction's staging (lorb_kfcompact.hip): 79 bytes of rows, 4 of map and 1 of hold per point
+  // a compaction's staging (lorb_kfcompact.hip): 79 bytes of rows (lorb::KfPointRows, whose list this one follows),
+  // 4 of map and 1 of hold per point
   A.add(&S->cp_pos, np * 3); A.add(&S->cp_normal, np * 3); A.add(&S->cp_max_dist, np); A.add(&S->cp_min_dist, np);
   A.add(&S->cp_desc, np * 32); A.add(&S->cp_locked, np); A.add(&S->cp_is_bad, np); A.add(&S->cp_recent, np);
   A.add(&S->cp_visible, np); A.add(&S->cp_found, np); A.add(&S->cp_first_fid, np);
@@ -672,26 +699,24 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
   int32_t cnt[6] = {0, 0, 0, 0, 0, 0};
   if (init) {
     const lorb_kf_store_host& h = *init;
-    auto up = [&](void* dst, const void* src, size_t bytes) {
-      return bytes && src ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-    };
     const size_t hp = (size_t)h.n_points, hk = (size_t)h.n_kf;
-    LORB_HIP(ctx, up(S->pos, h.pos, hp * 12)); LORB_HIP(ctx, up(S->normal, h.normal, hp * 12));
-    LORB_HIP(ctx, up(S->max_dist, h.max_dist, hp * 4)); LORB_HIP(ctx, up(S->min_dist, h.min_dist, hp * 4));
-    LORB_HIP(ctx, up(S->desc, h.desc, hp * 32)); LORB_HIP(ctx, up(S->locked, h.locked, hp));
-    if (h.is_bad) LORB_HIP(ctx, up(S->is_bad, h.is_bad, hp));
+    LORB_HIP(ctx, lorb::kf_up(S, S->pos, h.pos, hp * 12)); LORB_HIP(ctx, lorb::kf_up(S, S->normal, h.normal, hp * 12));
+    LORB_HIP(ctx, lorb::kf_up(S, S->max_dist, h.max_dist, hp * 4));
+    LORB_HIP(ctx, lorb::kf_up(S, S->min_dist, h.min_dist, hp * 4));
+    LORB_HIP(ctx, lorb::kf_up(S, S->desc, h.desc, hp * 32)); LORB_HIP(ctx, lorb::kf_up(S, S->locked, h.locked, hp));
+    if (h.is_bad) LORB_HIP(ctx, lorb::kf_up(S, S->is_bad, h.is_bad, hp));
     else if (hp) LORB_HIP(ctx, hipMemsetAsync(S->is_bad, 0, hp, st));
-    if (h.kf_bad) LORB_HIP(ctx, up(S->kf_bad, h.kf_bad, hk));
+    if (h.kf_bad) LORB_HIP(ctx, lorb::kf_up(S, S->kf_bad, h.kf_bad, hk));
     else if (hk) LORB_HIP(ctx, hipMemsetAsync(S->kf_bad, 0, hk, st));
     ones.assign(hp, 1);  // mnVisible = mnFound = 1 (src/map_point.cpp's constructors); first_fid, recent, kf_fid stay 0
-    LORB_HIP(ctx, up(S->visible, ones.data(), hp * 4)); LORB_HIP(ctx, up(S->found, ones.data(), hp * 4));
-    if (h.obs_off) LORB_HIP(ctx, up(S->obs_off, h.obs_off, (hp + 1) * 4));
-    LORB_HIP(ctx, up(S->obs_kf, h.obs_kf, (size_t)h.n_obs * 4));
+    LORB_HIP(ctx, lorb::kf_up(S, S->visible, ones.data(), hp * 4)); LORB_HIP(ctx, lorb::kf_up(S, S->found, ones.data(), hp * 4));
+    if (h.obs_off) LORB_HIP(ctx, lorb::kf_up(S, S->obs_off, h.obs_off, (hp + 1) * 4));
+    LORB_HIP(ctx, lorb::kf_up(S, S->obs_kf, h.obs_kf, (size_t)h.n_obs * 4));
     if (hk) {
-      LORB_HIP(ctx, up(S->kf_slot_off, h.kf_slot_off, (hk + 1) * 4));
-      LORB_HIP(ctx, up(S->kf_slot_point, h.kf_slot_point, (size_t)h.n_kf_slots * 4));
-      LORB_HIP(ctx, up(S->cov_off, h.cov_off, (hk + 1) * 4));
-      LORB_HIP(ctx, up(S->cov_kf, h.cov_kf, (size_t)h.n_cov * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->kf_slot_off, h.kf_slot_off, (hk + 1) * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->kf_slot_point, h.kf_slot_point, (size_t)h.n_kf_slots * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->cov_off, h.cov_off, (hk + 1) * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->cov_kf, h.cov_kf, (size_t)h.n_cov * 4));
       // the fixed-stride rows
       conn_n.assign(hk, 0); ord_n.assign(hk, 0);
       conn_kf.assign(hk * nk, 0); conn_w.assign(hk * nk, 0); ord_kf.assign(hk * nk, 0);
@@ -704,17 +729,19 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
         }
         for (int i = 0; i < ord_n[k]; ++i) ord_kf[k * nk + i] = h.cov_kf[h.cov_off[k] + i];
       }
-      LORB_HIP(ctx, up(S->conn_n, conn_n.data(), hk * 4)); LORB_HIP(ctx, up(S->ord_n, ord_n.data(), hk * 4));
-      LORB_HIP(ctx, up(S->conn_kf, conn_kf.data(), hk * nk * 4)); LORB_HIP(ctx, up(S->conn_w, conn_w.data(), hk * nk * 4));
-      LORB_HIP(ctx, up(S->ord_kf, ord_kf.data(), hk * nk * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->conn_n, conn_n.data(), hk * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->ord_n, ord_n.data(), hk * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->conn_kf, conn_kf.data(), hk * nk * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->conn_w, conn_w.data(), hk * nk * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->ord_kf, ord_kf.data(), hk * nk * 4));
     }
     if (geom) {
-      LORB_HIP(ctx, up(S->kf_pose, geom->kf_pose, hk * 24));
-      LORB_HIP(ctx, up(S->kf_slot_uv, geom->kf_slot_uv, (size_t)h.n_kf_slots * 8));
-      LORB_HIP(ctx, up(S->obs_slot, geom->obs_slot, (size_t)h.n_obs * 4));
+      LORB_HIP(ctx, lorb::kf_up(S, S->kf_pose, geom->kf_pose, hk * 24));
+      LORB_HIP(ctx, lorb::kf_up(S, S->kf_slot_uv, geom->kf_slot_uv, (size_t)h.n_kf_slots * 8));
+      LORB_HIP(ctx, lorb::kf_up(S, S->obs_slot, geom->obs_slot, (size_t)h.n_obs * 4));
     }
     cnt[0] = h.n_kf; cnt[1] = h.n_points; cnt[2] = h.n_obs; cnt[3] = h.n_kf_slots; cnt[4] = h.n_cov; cnt[5] = h.n_conn;
-    LORB_HIP(ctx, up(S->cnt, cnt, sizeof cnt));
+    LORB_HIP(ctx, lorb::kf_up(S, S->cnt, cnt, sizeof cnt));
   }
   LORB_HIP(ctx, hipStreamSynchronize(st));
   S->b_kf = cnt[0]; S->b_points = cnt[1]; S->b_obs = cnt[2]; S->b_slots = cnt[3]; S->b_cov = cnt[4];
@@ -744,8 +771,7 @@ int lorb_kf_store_counts(lorb_kf_store* S, int32_t* out, int32_t n) {
   lorb_ctx* ctx = S->ctx;
   if (n < 1) return lorb::set_error(ctx, LORB_E_INVALID, "%d counts asked for", n);
   int32_t cnt[6];
-  LORB_HIP(ctx, hipMemcpyAsync(cnt, S->cnt, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
-  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  LORB_TRY(lorb::kf_true_counts(S, cnt));
   S->b_kf = cnt[0]; S->b_points = cnt[1]; S->b_obs = cnt[2]; S->b_slots = cnt[3]; S->b_cov = cnt[4];
   for (int i = 0; i < std::min(n, 6); ++i) out[i] = cnt[i];
   return LORB_OK;
@@ -754,10 +780,8 @@ int lorb_kf_store_counts(lorb_kf_store* S, int32_t* out, int32_t n) {
 int lorb_kf_store_read(lorb_kf_store* S, const lorb_kf_store_host* h) {
   if (!S || !h) return LORB_E_INVALID;
   lorb_ctx* ctx = S->ctx;
-  hipStream_t st = ctx->stream;
   int32_t cnt[6];
-  LORB_HIP(ctx, hipMemcpyAsync(cnt, S->cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_TRY(lorb::kf_true_counts(S, cnt));
   const int nk = cnt[0], np = cnt[1], no = cnt[2], ns = cnt[3], nc = cnt[4], nn = cnt[5];
   const bool pts = h->pos || h->normal || h->max_dist || h->min_dist || h->desc || h->locked || h->is_bad || h->obs_off;
   const bool kfs = h->kf_bad || h->kf_slot_off || h->cov_off || h->conn_off;
@@ -765,26 +789,24 @@ int lorb_kf_store_read(lorb_kf_store* S, const lorb_kf_store_host* h) {
       (h->kf_slot_point && h->n_kf_slots < ns) || (h->cov_kf && h->n_cov < nc) || ((h->conn_kf || h->conn_w) && h->n_conn < nn))
     return lorb::set_error(ctx, LORB_E_INVALID, "an output array is smaller than the store's count (%d kf, %d points, %d obs, "
                            "%d slots, %d cov, %d conn)", nk, np, no, ns, nc, nn);
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    return bytes && dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-  };
-  LORB_HIP(ctx, down(h->pos, S->pos, (size_t)np * 12)); LORB_HIP(ctx, down(h->normal, S->normal, (size_t)np * 12));
-  LORB_HIP(ctx, down(h->max_dist, S->max_dist, (size_t)np * 4)); LORB_HIP(ctx, down(h->min_dist, S->min_dist, (size_t)np * 4));
-  LORB_HIP(ctx, down(h->desc, S->desc, (size_t)np * 32)); LORB_HIP(ctx, down(h->locked, S->locked, (size_t)np));
-  LORB_HIP(ctx, down(h->is_bad, S->is_bad, (size_t)np)); LORB_HIP(ctx, down(h->obs_off, S->obs_off, ((size_t)np + 1) * 4));
-  LORB_HIP(ctx, down(h->obs_kf, S->obs_kf, (size_t)no * 4)); LORB_HIP(ctx, down(h->kf_bad, S->kf_bad, (size_t)nk));
-  LORB_HIP(ctx, down(h->kf_slot_off, S->kf_slot_off, ((size_t)nk + 1) * 4));
-  LORB_HIP(ctx, down(h->kf_slot_point, S->kf_slot_point, (size_t)ns * 4));
-  LORB_HIP(ctx, down(h->cov_off, S->cov_off, ((size_t)nk + 1) * 4)); LORB_HIP(ctx, down(h->cov_kf, S->cov_kf, (size_t)nc * 4));
+  const struct { void* host; const void* dev; size_t bytes; } cols[] = {
+      {h->pos, S->pos, (size_t)np * 12}, {h->normal, S->normal, (size_t)np * 12}, {h->max_dist, S->max_dist, (size_t)np * 4},
+      {h->min_dist, S->min_dist, (size_t)np * 4}, {h->desc, S->desc, (size_t)np * 32}, {h->locked, S->locked, (size_t)np},
+      {h->is_bad, S->is_bad, (size_t)np}, {h->obs_off, S->obs_off, ((size_t)np + 1) * 4}, {h->obs_kf, S->obs_kf, (size_t)no * 4},
+      {h->kf_bad, S->kf_bad, (size_t)nk}, {h->kf_slot_off, S->kf_slot_off, ((size_t)nk + 1) * 4},
+      {h->kf_slot_point, S->kf_slot_point, (size_t)ns * 4}, {h->cov_off, S->cov_off, ((size_t)nk + 1) * 4},
+      {h->cov_kf, S->cov_kf, (size_t)nc * 4}};
+  for (const auto& c : cols) LORB_HIP(ctx, lorb::kf_down(S, c.host, c.dev, c.bytes));
   const bool conn = h->conn_off || h->conn_kf || h->conn_w;
   const size_t stride = (size_t)S->cap.max_kf;
   std::vector<int32_t> rn, rk, rw;
   if (conn && nk > 0) {
     rn.resize(nk); rk.resize(nk * stride); rw.resize(nk * stride);
-    LORB_HIP(ctx, down(rn.data(), S->conn_n, (size_t)nk * 4));
-    LORB_HIP(ctx, down(rk.data(), S->conn_kf, nk * stride * 4)); LORB_HIP(ctx, down(rw.data(), S->conn_w, nk * stride * 4));
+    LORB_HIP(ctx, lorb::kf_down(S, rn.data(), S->conn_n, (size_t)nk * 4));
+    LORB_HIP(ctx, lorb::kf_down(S, rk.data(), S->conn_kf, nk * stride * 4));
+    LORB_HIP(ctx, lorb::kf_down(S, rw.data(), S->conn_w, nk * stride * 4));
   }
-  LORB_HIP(ctx, hipStreamSynchronize(st));
+  LORB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (conn) {
     int at = 0;
     for (int k = 0; k < nk; ++k) {
@@ -803,8 +825,8 @@ int lorb_kf_store_insert_dev(lorb_ctx* ctx, lorb_kf_store* S, const lorb_frame_p
                              int32_t n_max_cur, const lorb_frame_slots* d_cur_slots, int32_t* d_cur_slot_gid,
                              const lorb_frame_pose* d_cur_pose, const int32_t* d_src_status, int32_t gate,
                              int32_t* d_refer_kf, lorb_local_map_result* d_update, lorb_kf_insert_result* d_result) {
-  if (!ctx || !S || !frame || !d_cur || !d_cur_slots || !d_cur_slot_gid || !d_cur_pose || !d_result) return LORB_E_INVALID;
-  if (S->ctx != ctx) return lorb::set_error(ctx, LORB_E_INVALID, "the keyframe store belongs to another context");
+  if (!frame || !d_cur || !d_cur_slots || !d_cur_slot_gid || !d_cur_pose || !d_result) return LORB_E_INVALID;
+  LORB_TRY(lorb::kf_enter(ctx, S));
   const int nk = n_max_cur;
   if (nk < 1) return lorb::set_error(ctx, LORB_E_INVALID, "bound %d must be positive", nk);
   if (nk > S->cap.max_kf_slots)

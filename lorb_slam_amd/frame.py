@@ -435,8 +435,29 @@ class KeyframeStore:
     appearance: the views of kf_slot_desc, kf_slot_octave and kf_center (read_appearance / write_appearance; a store
     made with keyframes needs write_appearance before keyframe_refresh)."""
     COUNTS =("n_kf", "n_points", "n_obs", "n_kf_slots", "n_cov", "n_conn")
-    _COLS = dict(pos=(np.float32, 3), normal=(np.float32, 3), max_dist=(np.float32, 1), min_dist=(np.float32, 1),
-                 desc=(np.uint8, 32), locked=(np.uint8, 1), is_bad=(np.uint8, 1))
+    # The four groups of arrays.  host: the ctypes struct of host addresses the read / write entry points take; view:
+    # the entry point that fills a struct of device addresses, and that struct; fault: write's message for an array of
+    # the wrong length; cols: per column (dtype, width, the count it runs over, rows beyond that count).
+    GROUPS = dict(
+        main=dict(host=A.KfStoreHost, view=("lorb_kf_store_view", A.MapStore), read="lorb_kf_store_read", cols=dict(
+            pos=(np.float32, 3, "n_points", 0), normal=(np.float32, 3, "n_points", 0), max_dist=(np.float32, 1, "n_points", 0),
+            min_dist=(np.float32, 1, "n_points", 0), desc=(np.uint8, 32, "n_points", 0), locked=(np.uint8, 1, "n_points", 0),
+            is_bad=(np.uint8, 1, "n_points", 0), obs_off=(np.int32, 1, "n_points", 1), obs_kf=(np.int32, 1, "n_obs", 0),
+            kf_bad=(np.uint8, 1, "n_kf", 0), kf_slot_off=(np.int32, 1, "n_kf", 1), kf_slot_point=(np.int32, 1, "n_kf_slots", 0),
+            cov_off=(np.int32, 1, "n_kf", 1), cov_kf=(np.int32, 1, "n_cov", 0), conn_off=(np.int32, 1, "n_kf", 1),
+            conn_kf=(np.int32, 1, "n_conn", 0), conn_w=(np.int32, 1, "n_conn", 0))),
+        geometry=dict(host=A.KfStoreGeomHost, view=("lorb_kf_store_geom_view", A.KfStoreGeomHost), read="lorb_kf_store_geom_read",
+                      cols=dict(kf_pose=(np.float32, 6, "n_kf", 0), kf_slot_uv=(np.float32, 2, "n_kf_slots", 0),
+                                obs_slot=(np.int32, 1, "n_obs", 0))),
+        life=dict(host=A.KfStoreLifeHost, view=("lorb_kf_store_life_view", A.KfStoreLifeHost), read="lorb_kf_store_life_read",
+                  write="lorb_kf_store_life_write", fault="life: {} has {} entries", cols=dict(
+                      visible=(np.int32, 1, "n_points", 0), found=(np.int32, 1, "n_points", 0),
+                      first_fid=(np.int32, 1, "n_points", 0), recent=(np.uint8, 1, "n_points", 0), kf_fid=(np.int32, 1, "n_kf", 0))),
+        appearance=dict(host=A.KfStoreAppearHost, view=("lorb_kf_store_appear_view", A.KfStoreAppearHost),
+                        read="lorb_kf_store_appear_read", write="lorb_kf_store_appear_write", fault="appearance: {} has {} rows",
+                        cols=dict(kf_slot_desc=(np.uint8, 32, "n_kf_slots", 0), kf_slot_octave=(np.int32, 1, "n_kf_slots", 0),
+                                  kf_center=(np.float32, 3, "n_kf", 0))))
+    _COLS = tuple(k for k, (_, _, n, plus) in GROUPS["main"]["cols"].items() if n == "n_points" and not plus)  # a point's row
 
     def __init__(self, ctx, max_kf, max_points, max_obs, max_kf_slots, init=None, geom=None):
         self.ctx = ctx
@@ -452,48 +473,74 @@ class KeyframeStore:
             g, gkeep = self._geom_host(geom)
             ctx.check(lib().lorb_kf_store_create_geom(ctx.handle, C.byref(self.caps), C.byref(h) if h is not None else None,
                                                       C.byref(g), C.byref(self._p)), "lorb_kf_store_create_geom")
-        v = self.view()
-        cap = dict(n_points=self.caps.max_points, n_kf=self.caps.max_kf)
+        self.arrays, self.geometry = self._views("main"), self._geometry_views()
+        self.life, self.appearance = self._life_views(), self._appearance_views()
 
-        def arr(addr, n, dt, w=1):
-            return DeviceArrayView(ctx, addr, (n, w) if w > 1 else (n,), dt)
+    def _views(self, group):
+        """The group's view entry point (no wait): a DeviceArrayView over the whole capacity of every column the view's
+        struct has (lorb_map_store keeps the point columns in .points and has no weight maps)."""
+        g = self.GROUPS[group]
+        v = g["view"][1]()
+        self.ctx.check(getattr(lib(), g["view"][0])(self._p, C.byref(v)), g["view"][0])
+        cap = dict(n_kf=self.caps.max_kf, n_points=self.caps.max_points, n_obs=self.caps.max_obs,
+                   n_kf_slots=self.caps.max_kf_slots, n_cov=self.max_cov)
+        at = {k: getattr(v, k, None) or getattr(getattr(v, "points", None), k, None) for k in g["cols"]}
+        return {k: DeviceArrayView(self.ctx, at[k], (cap[n] + plus, w) if w > 1 else (cap[n] + plus,), dt)
+                for k, (dt, w, n, plus) in g["cols"].items() if at[k]}
 
-        self.arrays = {k: arr(getattr(v.points, k), cap["n_points"], dt, w) for k, (dt, w) in self._COLS.items()}
-        self.arrays.update(obs_off=arr(v.obs_off, cap["n_points"] + 1, np.int32), obs_kf=arr(v.obs_kf, self.caps.max_obs, np.int32),
-                           kf_bad=arr(v.kf_bad, cap["n_kf"], np.uint8), kf_slot_off=arr(v.kf_slot_off, cap["n_kf"] + 1, np.int32),
-                           kf_slot_point=arr(v.kf_slot_point, self.caps.max_kf_slots, np.int32),
-                           cov_off=arr(v.cov_off, cap["n_kf"] + 1, np.int32), cov_kf=arr(v.cov_kf, self.max_cov, np.int32))
-        self.geometry = self._geometry_views()
-        self.life = self._life_views()
-        self.appearance = self._appearance_views()
+    def _host_struct(self, group, n, arrays):
+        """The group's host struct with the counts `n` and the addresses of `arrays`."""
+        T = self.GROUPS[group]["host"]
+        h = T(**{f: int(n[f]) for f, _ in T._fields_ if f in n})
+        for k, v in arrays.items():
+            setattr(h, k, v.ctypes.data)
+        return h
+
+    def _read(self, group):
+        """The group's read entry point (waits): (the six true counts, every column's true rows)."""
+        g, n = self.GROUPS[group], self.counts()
+        a = {k: np.zeros((n[c] + plus, w) if w > 1 else n[c] + plus, dt) for k, (dt, w, c, plus) in g["cols"].items()}
+        self.ctx.check(getattr(lib(), g["read"])(self._p, C.byref(self._host_struct(group, n, a))), g["read"])
+        return n, a
+
+    def _write(self, group, src, **counts):
+        """The group's write entry point (waits): the true rows replaced by every column `src` gives.  counts: the row
+        counts the caller states (None: the true ones); an array must have as many rows."""
+        g, n = self.GROUPS[group], self.counts()
+        n.update({k: int(v) for k, v in counts.items() if v is not None})
+        keep = {k: np.ascontiguousarray(src[k], dt).reshape((-1, w) if w > 1 else -1)
+                for k, (dt, w, _, _) in g["cols"].items() if src.get(k) is not None}
+        for k, v in keep.items():
+            if len(v) != n[g["cols"][k][2]]:
+                raise LorbError(g["fault"].format(k, len(v)))
+        self.ctx.check(getattr(lib(), g["write"])(self._p, C.byref(self._host_struct(group, n, keep))), g["write"])
+
+    def _fill(self, group, views, counts, value, skip=()):
+        """`value` bytes in every view of the group, but those in skip, past the given true counts."""
+        for k, arr in views.items():
+            if k in skip:
+                continue
+            _, _, n, plus = self.GROUPS[group]["cols"][k]
+            at = (counts[n] + plus) * (arr.nbytes // arr.shape[0])
+            if at < arr.nbytes:
+                self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
+                                                     C.c_size_t(arr.nbytes - at)), "memset")
 
     def _appearance_views(self):
         """lorb_kf_store_appear_view: kf_slot_desc, kf_slot_octave and kf_center over their whole capacity (no wait)."""
-        g = A.KfStoreAppearHost()
-        self.ctx.check(lib().lorb_kf_store_appear_view(self._p, C.byref(g)), "lorb_kf_store_appear_view")
-        return dict(kf_slot_desc=DeviceArrayView(self.ctx, g.kf_slot_desc, (g.n_kf_slots, 32), np.uint8),
-                    kf_slot_octave=DeviceArrayView(self.ctx, g.kf_slot_octave, (g.n_kf_slots,), np.int32),
-                    kf_center=DeviceArrayView(self.ctx, g.kf_center, (g.n_kf, 3), np.float32))
+        return self._views("appearance")
 
     def _life_views(self):
         """lorb_kf_store_life_view / _frame_word_view: visible, found, first_fid, recent, kf_fid over their whole
         capacity and the one-word frame_word (no wait)."""
-        g, w = A.KfStoreLifeHost(), C.c_void_p()
-        self.ctx.check(lib().lorb_kf_store_life_view(self._p, C.byref(g)), "lorb_kf_store_life_view")
+        out, w = self._views("life"), C.c_void_p()
         self.ctx.check(lib().lorb_kf_store_frame_word_view(self._p, C.byref(w)), "lorb_kf_store_frame_word_view")
-        out = {k: DeviceArrayView(self.ctx, getattr(g, k), (g.n_points,), np.int32) for k in ("visible", "found", "first_fid")}
-        out.update(recent=DeviceArrayView(self.ctx, g.recent, (g.n_points,), np.uint8),
-                   kf_fid=DeviceArrayView(self.ctx, g.kf_fid, (g.n_kf,), np.int32),
-                   frame_word=DeviceArrayView(self.ctx, w.value, (1,), np.int32))
+        out["frame_word"] = DeviceArrayView(self.ctx, w.value, (1,), np.int32)
         return out
 
     def _geometry_views(self):
         """lorb_kf_store_geom_view: kf_pose, kf_slot_uv and obs_slot over their whole capacity (no wait)."""
-        g = A.KfStoreGeomHost()
-        self.ctx.check(lib().lorb_kf_store_geom_view(self._p, C.byref(g)), "lorb_kf_store_geom_view")
-        return dict(kf_pose=DeviceArrayView(self.ctx, g.kf_pose, (g.n_kf, 6), np.float32),
-                    kf_slot_uv=DeviceArrayView(self.ctx, g.kf_slot_uv, (g.n_kf_slots, 2), np.float32),
-                    obs_slot=DeviceArrayView(self.ctx, g.obs_slot, (g.n_obs,), np.int32))
+        return self._views("geometry")
 
     @staticmethod
     def _geom_host(g):
@@ -511,7 +558,8 @@ class KeyframeStore:
     @staticmethod
     def _host(s):
         n = len(s["pos"])
-        keep = {k: np.ascontiguousarray(s[k], dt).reshape(-1) for k, (dt, _) in KeyframeStore._COLS.items() if s.get(k) is not None}
+        cols = KeyframeStore.GROUPS["main"]["cols"]
+        keep = {k: np.ascontiguousarray(s[k], cols[k][0]).reshape(-1) for k in KeyframeStore._COLS if s.get(k) is not None}
         (keep["obs_off"], keep["obs_kf"]), (keep["kf_slot_off"], keep["kf_slot_point"]) = _csr(s["obs"]), _csr(s["kf_slots"])
         keep["cov_off"], keep["cov_kf"] = _csr(s["cov"])
         conn = s.get("conn") or [{} for _ in s["kf_bad"]]
@@ -544,17 +592,7 @@ class KeyframeStore:
     def read(self):
         """lorb_kf_store_read (waits): dict(the six counts; the point columns; obs, kf_slots, cov as lists per row;
         kf_bad; conn: per keyframe {keyframe: weight}; csr: the raw offset / index arrays)."""
-        n = self.counts()
-        nk, np_ = n["n_kf"], n["n_points"]
-        a = {k: np.zeros((np_, w) if w > 1 else np_, dt) for k, (dt, w) in self._COLS.items()}
-        a.update(obs_off=np.zeros(np_ + 1, np.int32), obs_kf=np.zeros(n["n_obs"], np.int32), kf_bad=np.zeros(nk, np.uint8),
-                 kf_slot_off=np.zeros(nk + 1, np.int32), kf_slot_point=np.zeros(n["n_kf_slots"], np.int32),
-                 cov_off=np.zeros(nk + 1, np.int32), cov_kf=np.zeros(n["n_cov"], np.int32), conn_off=np.zeros(nk + 1, np.int32),
-                 conn_kf=np.zeros(n["n_conn"], np.int32), conn_w=np.zeros(n["n_conn"], np.int32))
-        h = A.KfStoreHost(*(n[k] for k in self.COUNTS))
-        for k, v in a.items():
-            setattr(h, k, v.ctypes.data)
-        self.ctx.check(lib().lorb_kf_store_read(self._p, C.byref(h)), "lorb_kf_store_read")
+        n, a = self._read("main")
         out = dict(n)
         out.update({k: a[k] for k in self._COLS})
         out.update(kf_bad=a["kf_bad"], obs=_uncsr(a["obs_off"], a["obs_kf"]), kf_slots=_uncsr(a["kf_slot_off"], a["kf_slot_point"]),
@@ -566,96 +604,42 @@ class KeyframeStore:
     def read_geometry(self):
         """lorb_kf_store_geom_read (waits): dict(kf_pose: n_kf x 6, kf_slot_uv: n_kf_slots x 2, obs_slot: n_obs) -- the
         true rows, flat as the store keeps them."""
-        n = self.counts()
-        a = dict(kf_pose=np.zeros((n["n_kf"], 6), np.float32), kf_slot_uv=np.zeros((n["n_kf_slots"], 2), np.float32),
-                 obs_slot=np.zeros(n["n_obs"], np.int32))
-        h = A.KfStoreGeomHost(n["n_kf"], n["n_kf_slots"], n["n_obs"])
-        for k, v in a.items():
-            setattr(h, k, v.ctypes.data)
-        self.ctx.check(lib().lorb_kf_store_geom_read(self._p, C.byref(h)), "lorb_kf_store_geom_read")
-        return a
-
-    _LIFE = dict(visible=np.int32, found=np.int32, first_fid=np.int32, recent=np.uint8, kf_fid=np.int32)
+        return self._read("geometry")[1]
 
     def read_life(self):
         """lorb_kf_store_life_read (waits): dict(visible, found, first_fid, recent: n_points; kf_fid: n_kf) -- the true
         rows -- and frame_word, the id of the frame the tracker last observed."""
-        n = self.counts()
-        a = {k: np.zeros(n["n_kf"] if k == "kf_fid" else n["n_points"], dt) for k, dt in self._LIFE.items()}
-        h = A.KfStoreLifeHost(n["n_kf"], n["n_points"])
-        for k, v in a.items():
-            setattr(h, k, v.ctypes.data)
-        self.ctx.check(lib().lorb_kf_store_life_read(self._p, C.byref(h)), "lorb_kf_store_life_read")
+        a = self._read("life")[1]
         a["frame_word"] = int(self.life["frame_word"].numpy()[0])
         return a
 
     def write_life(self, life, n_kf=None, n_points=None):
         """lorb_kf_store_life_write (waits): replaces the true rows by every array of `life` that is given (keys of
         read_life but frame_word).  n_kf / n_points default to the true counts; they must equal them."""
-        n = self.counts()
-        keep = {k: np.ascontiguousarray(life[k], dt) for k, dt in self._LIFE.items() if life.get(k) is not None}
-        h = A.KfStoreLifeHost(n["n_kf"] if n_kf is None else int(n_kf), n["n_points"] if n_points is None else int(n_points))
-        for k, v in keep.items():
-            if len(v) != (h.n_kf if k == "kf_fid" else h.n_points):
-                raise LorbError(f"life: {k} has {len(v)} entries")
-            setattr(h, k, v.ctypes.data)
-        self.ctx.check(lib().lorb_kf_store_life_write(self._p, C.byref(h)), "lorb_kf_store_life_write")
+        self._write("life", life, n_kf=n_kf, n_points=n_points)
 
     def fill_life(self, counts, value=ORB_SENTINEL):
         """fill() for the life arrays: `value` bytes past the given true counts (the frame word is left alone)."""
-        for k, arr in self.life.items():
-            if k == "frame_word":
-                continue
-            at = counts["n_kf" if k == "kf_fid" else "n_points"] * arr.dtype.itemsize
-            if at < arr.nbytes:
-                self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
-                                                     C.c_size_t(arr.nbytes - at)), "memset")
-
-    _APPEAR = dict(kf_slot_desc=(np.uint8, 32), kf_slot_octave=(np.int32, 1), kf_center=(np.float32, 3))
+        self._fill("life", self.life, counts, value, skip=("frame_word",))
 
     def read_appearance(self):
         """lorb_kf_store_appear_read (waits): dict(kf_slot_desc: n_kf_slots x 32, kf_slot_octave: n_kf_slots, kf_center:
         n_kf x 3) -- the true rows, flat as the store keeps them."""
-        n = self.counts()
-        rows = dict(kf_slot_desc=n["n_kf_slots"], kf_slot_octave=n["n_kf_slots"], kf_center=n["n_kf"])
-        a = {k: np.zeros((rows[k], w) if w > 1 else rows[k], dt) for k, (dt, w) in self._APPEAR.items()}
-        h = A.KfStoreAppearHost(n["n_kf"], n["n_kf_slots"])
-        for k, v in a.items():
-            setattr(h, k, v.ctypes.data)
-        self.ctx.check(lib().lorb_kf_store_appear_read(self._p, C.byref(h)), "lorb_kf_store_appear_read")
-        return a
+        return self._read("appearance")[1]
 
     def write_appearance(self, app, n_kf=None, n_kf_slots=None):
         """lorb_kf_store_appear_write (waits): replaces the true rows by every array of `app` that is given (keys of
         read_appearance).  n_kf / n_kf_slots default to the true counts; they must equal them.  A store created with
         keyframes has no appearance until one call has given all three."""
-        n = self.counts()
-        keep = {k: np.ascontiguousarray(app[k], dt).reshape((-1, w) if w > 1 else -1) for k, (dt, w) in self._APPEAR.items()
-                if app.get(k) is not None}
-        h = A.KfStoreAppearHost(n["n_kf"] if n_kf is None else int(n_kf), n["n_kf_slots"] if n_kf_slots is None else int(n_kf_slots))
-        for k, v in keep.items():
-            if len(v) != (h.n_kf if k == "kf_center" else h.n_kf_slots):
-                raise LorbError(f"appearance: {k} has {len(v)} rows")
-            setattr(h, k, v.ctypes.data)
-        self.ctx.check(lib().lorb_kf_store_appear_write(self._p, C.byref(h)), "lorb_kf_store_appear_write")
+        self._write("appearance", app, n_kf=n_kf, n_kf_slots=n_kf_slots)
 
     def fill_appearance(self, counts, value=ORB_SENTINEL):
         """fill() for the appearance arrays: `value` bytes past the given true counts."""
-        start = dict(kf_slot_desc=counts["n_kf_slots"], kf_slot_octave=counts["n_kf_slots"], kf_center=counts["n_kf"])
-        for k, arr in self.appearance.items():
-            at = start[k] * (arr.nbytes // arr.shape[0])
-            if at < arr.nbytes:
-                self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
-                                                     C.c_size_t(arr.nbytes - at)), "memset")
+        self._fill("appearance", self.appearance, counts, value)
 
     def fill_geometry(self, counts, value=ORB_SENTINEL):
         """fill() for the geometry arrays: `value` bytes past the given true counts."""
-        start = dict(kf_pose=counts["n_kf"], kf_slot_uv=counts["n_kf_slots"], obs_slot=counts["n_obs"])
-        for k, arr in self.geometry.items():
-            at = start[k] * (arr.nbytes // arr.shape[0])
-            if at < arr.nbytes:
-                self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
-                                                     C.c_size_t(arr.nbytes - at)), "memset")
+        self._fill("geometry", self.geometry, counts, value)
 
     def ba_window(self, result=None):
         """lorb_kf_ba_window_read (waits): the last gathered window as a dict -- local_kf, fixed_kf, l2g, pose_init,
@@ -677,16 +661,7 @@ class KeyframeStore:
     def fill(self, counts, value=ORB_SENTINEL):
         """Every array of the view but is_bad / kf_bad set to `value` bytes past the given true counts (a dict as
         counts() returns): what a test does before a call to see afterwards what the call wrote."""
-        start = dict(obs_off=counts["n_points"] + 1, obs_kf=counts["n_obs"], kf_slot_off=counts["n_kf"] + 1,
-                     kf_slot_point=counts["n_kf_slots"], cov_off=counts["n_kf"] + 1, cov_kf=counts["n_cov"])
-        for k, arr in self.arrays.items():
-            if k in ("is_bad", "kf_bad"):
-                continue
-            row = arr.nbytes // arr.shape[0]
-            at = start.get(k, counts["n_points"]) * row
-            if at < arr.nbytes:
-                self.ctx.check(lib().lorb_memset_dev(self.ctx.handle, C.c_void_p(arr.ptr.value + at), C.c_int(value),
-                                                     C.c_size_t(arr.nbytes - at)), "memset")
+        self._fill("main", self.arrays, counts, value, skip=("is_bad", "kf_bad"))
 
     def compact(self, record, tables=(), d_src_status=None, d_map=None):
         """lorb_kf_store_compact_dev enqueued and nothing else: the store's dead point rows -- bad, unobserved, named
@@ -734,9 +709,19 @@ def keyframe_insert(ctx, store, fp, cur, cur_slots, slot_gid, cur_pose, record, 
         update_record.ptr if update_record is not None else None, record.ptr), "lorb_kf_store_insert_dev")
 
 
+def _record(ctx, T):
+    """A device buffer for a record of ctypes type T: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
+    return _sentinel(ctx, C.sizeof(T) + ORB_GUARD, np.uint8)
+
+
+def _result(record, T):
+    """The T in a device record buffer (waits for the stream)."""
+    return T.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(T)])
+
+
 def keyframe_ba_record(ctx):
     """A device buffer for an A.KfBaResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
-    return _sentinel(ctx, C.sizeof(A.KfBaResult) + ORB_GUARD, np.uint8)
+    return _record(ctx, A.KfBaResult)
 
 
 def keyframe_local_ba(ctx, store, fp, d_kf, record, d_src_status=None, opt=None, gather_only=False, summary=False):
@@ -764,12 +749,12 @@ def keyframe_local_ba(ctx, store, fp, d_kf, record, d_src_status=None, opt=None,
 
 def keyframe_ba_result(record):
     """The A.KfBaResult in a device record buffer (waits for the stream)."""
-    return A.KfBaResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfBaResult)])
+    return _result(record, A.KfBaResult)
 
 
 def keyframe_refresh_record(ctx):
     """A device buffer for an A.KfRefreshResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
-    return _sentinel(ctx, C.sizeof(A.KfRefreshResult) + ORB_GUARD, np.uint8)
+    return _record(ctx, A.KfRefreshResult)
 
 
 def keyframe_refresh(ctx, store, fp, ba_record, record, what=A.LORB_KF_REFRESH_ALL):
@@ -785,12 +770,12 @@ def keyframe_refresh(ctx, store, fp, ba_record, record, what=A.LORB_KF_REFRESH_A
 
 def keyframe_refresh_result(record):
     """The A.KfRefreshResult in a device record buffer (waits for the stream)."""
-    return A.KfRefreshResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfRefreshResult)])
+    return _result(record, A.KfRefreshResult)
 
 
 def keyframe_observe_record(ctx):
     """A device buffer for an A.KfObserveResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
-    return _sentinel(ctx, C.sizeof(A.KfObserveResult) + ORB_GUARD, np.uint8)
+    return _record(ctx, A.KfObserveResult)
 
 
 def keyframe_observe(ctx, store, frame_id, cur, cur_slots, slot_gid, slot_id, lmap, update_record, in_view, record,
@@ -810,12 +795,12 @@ def keyframe_observe(ctx, store, frame_id, cur, cur_slots, slot_gid, slot_id, lm
 
 def keyframe_observe_result(record):
     """The A.KfObserveResult in a device record buffer (waits for the stream)."""
-    return A.KfObserveResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfObserveResult)])
+    return _result(record, A.KfObserveResult)
 
 
 def keyframe_cull_record(ctx):
     """A device buffer for an A.KfCullResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
-    return _sentinel(ctx, C.sizeof(A.KfCullResult) + ORB_GUARD, np.uint8)
+    return _record(ctx, A.KfCullResult)
 
 
 def keyframe_cull(ctx, store, d_kf, record, d_src_status=None, params=A.LORB_KF_CULL_REFERENCE, cur=None, cur_slots=None,
@@ -835,22 +820,22 @@ def keyframe_cull(ctx, store, d_kf, record, d_src_status=None, params=A.LORB_KF_
 
 def keyframe_cull_result(record):
     """The A.KfCullResult in a device record buffer (waits for the stream)."""
-    return A.KfCullResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfCullResult)])
+    return _result(record, A.KfCullResult)
 
 
 def keyframe_compact_record(ctx):
     """A device buffer for an A.KfCompactResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
-    return _sentinel(ctx, C.sizeof(A.KfCompactResult) + ORB_GUARD, np.uint8)
+    return _record(ctx, A.KfCompactResult)
 
 
 def keyframe_compact_result(record):
     """The A.KfCompactResult in a device record buffer (waits for the stream)."""
-    return A.KfCompactResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfCompactResult)])
+    return _result(record, A.KfCompactResult)
 
 
 def keyframe_insert_result(record):
     """The A.KfInsertResult in a device record buffer (waits for the stream)."""
-    return A.KfInsertResult.from_buffer_copy(record.numpy().tobytes()[:C.sizeof(A.KfInsertResult)])
+    return _result(record, A.KfInsertResult)
 
 
 def Tcw_to_pose(Tcw):

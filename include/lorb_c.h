@@ -1593,6 +1593,94 @@ typedef struct lorb_kf_refresh_result {   /* device memory, like every record of
 int lorb_kf_store_refresh_dev(lorb_ctx* ctx, lorb_kf_store* store, const lorb_frame_params* frame,
                               const lorb_kf_ba_result* d_ba_result, int32_t what, lorb_kf_refresh_result* d_result);
 
+/* ----------------------------------------------------------------------------------------
+ * Retiring keyframes: Frame::SetBadFlag (src/frame.cpp:684-714) on the keyframe store, with Frame::EraseConnection
+ * and its re-sort (:791-798, :754-774) and MapPoint::EraseObservation with the mpRefKF hand-over and the cascade into
+ * MapPoint::SetBadFlag (src/map_point.cpp:141-153, :184-199).  The reference's KeyFramesCulling is empty
+ * (src/local_mapping.cpp:110-113): it has the mechanism and no rule, so the call takes the keyframes to retire as a
+ * list in device memory -- a later rule kernel or the host can both supply it without a wait.  The mapper step
+ * becomes lorb_kf_store_insert_dev -> _cull_dev -> _local_ba_dev -> _refresh_dev -> _retire_dev -> _compact_dev.  The
+ * call renumbers nothing, so it is also legal anywhere between two frames, and a live lorb_local_map keeps valid
+ * indices.
+ * -------------------------------------------------------------------------------------- */
+#define LORB_KF_RETIRE_MAX_LIST 1024
+#define LORB_KF_RETIRE_MAX_PROTECT 4
+typedef struct lorb_kf_retire_result {   /* device memory, like every record of the chain */
+  int32_t status;            /* 0; 1: a source status, *d_n_list outside [0, n_max_list] or a damaged count of the
+                                store: nothing else was written */
+  int32_t n_skip_range;      /* list entries outside [0, true n_kf) */
+  int32_t n_skip_dup;        /* ... equal to an earlier entry */
+  int32_t n_skip_bad;        /* ... whose kf_bad is already set */
+  int32_t n_skip_first;      /* ... whose kf_fid is 0 (src/frame.cpp:686-687) */
+  int32_t n_skip_protected;  /* ... equal to a protected word */
+  int32_t n_retired;         /* the set V */
+  int32_t n_obs_erased;      /* entries removed from the lists of points that live on */
+  int32_t n_points_bad;      /* points the cascade ran on (MapPoint::SetBadFlag) */
+  int32_t n_obs_removed;     /* all entries that left the observation CSR */
+  int32_t n_slots_erased;    /* slots of keyframes outside V set to -1 by the cascade */
+  int32_t n_obs_bad_slot;    /* observations of such points, keyframe outside V, whose keyframe or slot is outside the
+                                store or holds another point (a damaged store): skipped */
+  int32_t n_conn_erased;     /* weight-map entries removed from keyframes outside V */
+  int32_t n_rows_reordered;  /* keyframes outside V whose ordered list was rebuilt */
+  int32_t n_obs, n_cov, n_conn;   /* the store after the call */
+} lorb_kf_retire_result;
+
+/* d_list holds n_max_list device int32 keyframe indices, *d_n_list (a device word) of them in use.  d_protect
+ * (NULL with n_protect = 0) holds up to LORB_KF_RETIRE_MAX_PROTECT device words: a listed keyframe equal to one of
+ * them is skipped -- in the loop the d_refer_kf word and &d_insert_result->kf, which the host cannot know without a
+ * wait.  d_src_status is nullable.  The store must have its geometry (the cascade needs obs_slot).  On the device, in
+ * this order:
+ *   a. Status: *d_src_status != 0, *d_n_list outside [0, n_max_list], or a true count outside its capacity stores
+ *      status = 1 and NOTHING else.
+ *   b. The set V.  Every list entry is classified in this order, one counter of the record per class: 1. outside
+ *      [0, true n_kf); 2. equal to an earlier entry; 3. kf_bad already set; 4. kf_fid[f] == 0 -- the reference's
+ *      if(mnId == 0) return; (src/frame.cpp:686-687): a store fresh from create has kf_fid = 0 everywhere and
+ *      nothing in it can be retired until lorb_kf_store_life_write says otherwise; 5. protected.  What remains is V
+ *      (n_retired).  With an empty V the call ends here: NOT A BYTE of the store changes.
+ *   c. Observations (:696-703, src/map_point.cpp:141-153).  For every p < n_points, bad or not, r = the entries of
+ *      its list whose keyframe is in V.  r == 0: untouched.  r > 0 and len - r > 2: the entries are removed, order
+ *      kept, obs_kf and obs_slot together; mpRefKF stays "the first entry of the list", which is
+ *      mObservations.begin()->first (:147-148) because lists ascend by keyframe index, and which is how
+ *      lorb_kf_store_refresh_dev reads it.  r > 0 and len - r <= 2: MapPoint::SetBadFlag exactly as
+ *      lorb_kf_store_cull_dev step c does it -- is_bad = 1; every remaining observation (f, s), f outside V, with f
+ *      inside the store, s inside f's row and kf_slot_point[kf_slot_off[f] + s] == p sets that entry to -1
+ *      (n_slots_erased), the others are counted in n_obs_bad_slot; the whole list leaves the CSR; recent, locked,
+ *      pos, normal, the distances and desc stay (the reference's list keeps the pointer, and the next cull's verdict 1
+ *      drops it).  An observation of a keyframe of V is counted in neither: step e clears that row whole.  The
+ *      verdict is taken from the lists alone, whatever a retired keyframe's row says; on a sound store (the invariant
+ *      kf_slot_point[kf_slot_off[f] + obs_slot[o]] == p) that is the reference's slot loop.  The CSR is rebuilt by
+ *      count, scan and scatter over 1024-point tiles, and the true n_obs drops.
+ *   d. Connections (:690-693, :791-798).  For every f in V and every key g of f's weight map with g not in V: if
+ *      g's weight map has the key f that entry is removed, the row keeps ascending key order, and g's ordered list is
+ *      rebuilt from ALL of g's weight map, ascending by (weight, index), entries below 3 included (:754-774), as the
+ *      insertion's step f does for a touched neighbour.  A g whose map names f while f's map does not name g keeps
+ *      that entry: the reference iterates f's map.
+ *   e. The retired keyframes (:705-711).  For each f in V: conn_n[f] = 0, ord_n[f] = 0, kf_bad[f] = 1, and its whole
+ *      slot row becomes -1 (a divergence, DESIGN section 7: the reference leaves mvpMapPoints of an erased frame
+ *      alone and nothing reads it again; here a row that still named dead points would hold them against
+ *      lorb_kf_store_compact_dev for ever).  kf_pose, kf_slot_uv, the appearance rows, kf_fid and kf_center stay.
+ *      cov_off / cov_kf are rebuilt from the first changed row on; the true n_cov and n_conn follow.
+ *   f. The record.
+ * Order independence: the reference retires keyframes one after another, this call retires a set.  The two agree --
+ * for the list in any order -- because a point's count only falls and a retired keyframe's own maps are cleared
+ * whatever its neighbours did before.
+ * All counting is integer: no result depends on the order atomics arrive in.  Nothing at or past a true count is
+ * written.  Every per-point and per-keyframe scratch word at rest between calls (the insertion's owner, the BA's
+ * first position, the cull's mark, the compaction's hold, this call's per-keyframe mark) is at rest over the whole
+ * capacity when the call ends, on every path.  The host's bounds are not touched.  Keyframe rows are not reclaimed
+ * and keyframes are not renumbered.
+ * LORB_E_INVALID, before anything is enqueued: a null required argument (ctx, store, d_list, d_n_list, d_result), a
+ * store of another ctx, a store without geometry, n_max_list outside [1, LORB_KF_RETIRE_MAX_LIST], n_protect outside
+ * [0, LORB_KF_RETIRE_MAX_PROTECT], n_protect > 0 with a null d_protect.
+ * Asynchronous on the ctx stream: 6 kernel launches, no stream synchronise, no device-to-host read and no
+ * host-to-device copy.
+ * Out of scope: a culling rule (KeyFramesCulling); reclaiming or renumbering keyframe rows; the CSR form of the
+ * weight maps; a caller's lorb_frame_pose block or slot set of a retired reference keyframe (d_protect exists so that
+ * it is not retired); lorb_map_step_dev; a host-array form or a C++ adapter. */
+int lorb_kf_store_retire_dev(lorb_ctx* ctx, lorb_kf_store* store, const int32_t* d_list, const int32_t* d_n_list,
+                             int32_t n_max_list, const int32_t* d_protect, int32_t n_protect,
+                             const int32_t* d_src_status, lorb_kf_retire_result* d_result);
+
 /* (a13) BA::LocalPoseOptimization: poses + points, MPCost for out-of-window (fixed) frames,
  * PoseMPCost for window frames.  One window per problem; batched over windows.
  * obs_frame[k] >= 0 : optimised pose index (PoseMPCost, src/bundle_adjust.cpp:293-301)

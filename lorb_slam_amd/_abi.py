@@ -334,6 +334,17 @@ class KfCompactResult(C.Structure):  # lorb_kf_compact_result
                 ("n_bad_kept", C.c_int32), ("n_kf_slots_mapped", C.c_int32), ("n_gids_mapped", C.c_int32)]
 
 
+LORB_KF_RETIRE_MAX_LIST, LORB_KF_RETIRE_MAX_PROTECT = 1024, 4
+
+
+class KfRetireResult(C.Structure):  # lorb_kf_retire_result
+    _fields_ = [("status", C.c_int32), ("n_skip_range", C.c_int32), ("n_skip_dup", C.c_int32), ("n_skip_bad", C.c_int32),
+                ("n_skip_first", C.c_int32), ("n_skip_protected", C.c_int32), ("n_retired", C.c_int32),
+                ("n_obs_erased", C.c_int32), ("n_points_bad", C.c_int32), ("n_obs_removed", C.c_int32),
+                ("n_slots_erased", C.c_int32), ("n_obs_bad_slot", C.c_int32), ("n_conn_erased", C.c_int32),
+                ("n_rows_reordered", C.c_int32), ("n_obs", C.c_int32), ("n_cov", C.c_int32), ("n_conn", C.c_int32)]
+
+
 LORB_KF_REFRESH_CENTERS, LORB_KF_REFRESH_NORMAL_DEPTH, LORB_KF_REFRESH_DESCRIPTOR, LORB_KF_REFRESH_ALL = 1, 2, 4, 7
 
 

@@ -1,8 +1,10 @@
 // lorb_kfstore.h -- the keyframe store's object and what its units share.  The units: lorb_kfstore.hip (create /
 // read / insertion, and the shared host helpers declared at the end of this file), lorb_kfba.hip (the local bundle
 // adjustment fed from the store), lorb_kfcull.hip (the points' life and MapPointsCulling), lorb_kfcompact.hip
-// (reclaiming the dead point rows) and lorb_kfrefresh.hip (the appearance and the refresh of the window's points).
-// Shared on the device: clampi, kf_range (a clamped CSR row), tile_base_1024 (the earlier tiles' sum), kKfTile and
+// (reclaiming the dead point rows), lorb_kfrefresh.hip (the appearance and the refresh of the window's points) and
+// lorb_kfretire.hip (Frame::SetBadFlag: retiring keyframes).
+// Shared on the device: clampi, kf_range (a clamped CSR row), tile_base_1024 (the earlier tiles' sum),
+// kf_sort_keys_1024 (a weight map's (weight, index) keys sorted in LDS), kKfTile and
 // KfPointRows -- THE list of the per-point arrays: a new per-point array of the store is added there.
 #pragma once
 
@@ -43,6 +45,27 @@ __device__ __forceinline__ int tile_base_1024(const int* tile, int n, int* wsum)
   for (int i = threadIdx.x; i < n; i += kKfTile) s += tile[i];
   block_excl_scan_1024(s, wsum, &base);
   return base;
+}
+
+// s_key[0 .. np2), np2 a power of two, sorted ascending in LDS by a 1024-thread workgroup (bitonic): the (weight,
+// index) keys of one weight map, padded with ~0.  Every thread calls it; the keys are written and a barrier passed
+// before the call, and it ends on a barrier.
+__device__ __forceinline__ void kf_sort_keys_1024(unsigned long long* s_key, int np2) {
+  const int t = threadIdx.x;
+  for (int k = 2; k <= np2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int q = t; q < np2; q += 1024) {
+        const int x = q ^ j;
+        if (x > q) {
+          const unsigned long long u = s_key[q], v = s_key[x];
+          if ((u > v) == ((q & k) == 0)) {
+            s_key[q] = v;
+            s_key[x] = u;
+          }
+        }
+      }
+      __syncthreads();
+    }
 }
 
 // The row of a point: every per-point array of the store, live (lorb_kf_store::point_rows) or a compaction's
@@ -104,6 +127,15 @@ struct KfCullCtl {
   int kf, cur;      // K and kf_fid[K]
   int nk, P, O, S;  // the true counts on entry
   int n_culled;     // points culled by this call: 0 makes the kernels after the verdicts return at once
+};
+
+// k_kf_retire_head's verdict and the counts a retirement's later kernels read (lorb_kfretire.hip)
+struct KfRetireCtl {
+  int go;           // the set V is not empty and the call runs
+  int nk, P, O, S;  // the true counts on entry
+  int n_v;          // keyframes in V (rt_v[0 .. n_v), in list order)
+  int n_affected;   // points that lose an observation: 0 makes the scatter return at once
+  int first_row;    // the lowest keyframe whose ordered list changes (integer min): the covisibility CSR is rebuilt from it
 };
 
 // k_kf_compact_head's verdict and the counts a compaction's later kernels read (lorb_kfcompact.hip)
@@ -198,6 +230,12 @@ struct lorb_kf_store {
   int* kf_slot_octave = nullptr;
   float* kf_center = nullptr;
   lorb::KfRefreshStat* rf_stat = nullptr;
+  // a retirement's scratch (lorb_kfretire.hip): membership of V per keyframe, at rest (0) between calls; V itself
+  // (LORB_KF_RETIRE_MAX_LIST words).  The points' marks ride in cull_mark, the CSR copy in off2 / kf2 / slot2, the
+  // tile counts in tile_cnt.
+  uint8_t* rt_mark = nullptr;
+  int* rt_v = nullptr;
+  lorb::KfRetireCtl* rt_ctl = nullptr;
   lorb::PlanSlots plans;
   // the point rows where they live, and a compaction's staging of them
   lorb::KfPointRows point_rows() const {

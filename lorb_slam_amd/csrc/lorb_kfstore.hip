@@ -417,20 +417,7 @@ __global__ __launch_bounds__(1024) void k_kf_order(const Ctl* ctl, const int* to
       s_key[q] = key;
     }
     __syncthreads();
-    for (int k = 2; k <= np2; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int q = t; q < np2; q += 1024) {
-          const int x = q ^ j;
-          if (x > q) {
-            const unsigned long long u = s_key[q], v = s_key[x];
-            if ((u > v) == ((q & k) == 0)) {
-              s_key[q] = v;
-              s_key[x] = u;
-            }
-          }
-        }
-        __syncthreads();
-      }
+    lorb::kf_sort_keys_1024(s_key, np2);
     const int len = own ? ctl->n_connected : m;  // K's keys outside the pairs sorted to the end
     for (int q = t; q < len; q += 1024) ord_kf[row + q] = (int)(unsigned)(s_key[q] & 0xffffffffull);
     if (t == 0) ord_n[r] = len;
@@ -680,6 +667,8 @@ int create_store(lorb_ctx* ctx, const lorb_kf_store_caps* caps, const lorb_kf_st
   A.add(&S->cp_map, np); A.add(&S->cp_hold, np); A.add(&S->cp_ctl, (size_t)1);
   // the appearance and the refresh's verdicts (lorb_kfrefresh.hip)
   A.add(&S->kf_slot_desc, ns * 32); A.add(&S->kf_slot_octave, ns); A.add(&S->kf_center, nk * 3); A.add(&S->rf_stat, np);
+  // a retirement's scratch (lorb_kfretire.hip)
+  A.add(&S->rt_mark, nk); A.add(&S->rt_v, (size_t)LORB_KF_RETIRE_MAX_LIST); A.add(&S->rt_ctl, (size_t)1);
   LORB_HIP(ctx, A.commit());
   {
     const lorb::KfLife life(S->life, caps->max_points, caps->max_kf);

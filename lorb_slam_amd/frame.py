@@ -432,6 +432,7 @@ class KeyframeStore:
     kept apart from arrays.  life: the views of visible, found, first_fid, recent, kf_fid and the one-word
     frame_word (read_life / write_life; keyframe_observe and keyframe_cull work on them).  compact() reclaims the
     rows of dead points (lorb_kf_store_compact_dev); the views stay valid, the indices in them change.
+    keyframe_retire sets kf_bad of the keyframes it is given and takes them out of every list; nothing is renumbered.
     appearance: the views of kf_slot_desc, kf_slot_octave and kf_center (read_appearance / write_appearance; a store
     made with keyframes needs write_appearance before keyframe_refresh)."""
     COUNTS =("n_kf", "n_points", "n_obs", "n_kf_slots", "n_cov", "n_conn")
@@ -831,6 +832,33 @@ def keyframe_compact_record(ctx):
 def keyframe_compact_result(record):
     """The A.KfCompactResult in a device record buffer (waits for the stream)."""
     return _result(record, A.KfCompactResult)
+
+
+def keyframe_retire_record(ctx):
+    """A device buffer for an A.KfRetireResult: ORB_SENTINEL bytes with ORB_GUARD bytes behind it."""
+    return _record(ctx, A.KfRetireResult)
+
+
+def keyframe_retire(ctx, store, d_list, d_n_list, record, n_max_list=None, protect=None, n_protect=None, d_src_status=None):
+    """lorb_kf_store_retire_dev enqueued and nothing else: Frame::SetBadFlag of a set of keyframes of a KeyframeStore,
+    behind keyframe_refresh and in front of KeyframeStore.compact, or anywhere between two frames.  d_list: a
+    DeviceArray of int32 keyframe indices (n_max_list defaults to its length, at most A.LORB_KF_RETIRE_MAX_LIST);
+    d_n_list: a DeviceArray holding the number in use, or its device address; protect: None, or a DeviceArray (or
+    the device address) of up to A.LORB_KF_RETIRE_MAX_PROTECT words (n_protect defaults to the array's length) -- a listed keyframe equal to one of
+    them is skipped; d_src_status: a device address or None; record: a device buffer for the A.KfRetireResult
+    (keyframe_retire_record)."""
+    nl = int(d_list.shape[0]) if n_max_list is None else int(n_max_list)
+    npr = (0 if protect is None else int(protect.shape[0])) if n_protect is None else int(n_protect)
+    p_at = None if protect is None else (protect.ptr if hasattr(protect, "ptr") else C.c_void_p(protect))
+    n_at = d_n_list.ptr if hasattr(d_n_list, "ptr") else C.c_void_p(d_n_list)
+    ctx.check(lib().lorb_kf_store_retire_dev(
+        ctx.handle, store._p, d_list.ptr, n_at, C.c_int32(nl), p_at, C.c_int32(npr),
+        C.c_void_p(d_src_status) if d_src_status else None, record.ptr), "lorb_kf_store_retire_dev")
+
+
+def keyframe_retire_result(record):
+    """The A.KfRetireResult in a device record buffer (waits for the stream)."""
+    return _result(record, A.KfRetireResult)
 
 
 def keyframe_insert_result(record):

@@ -336,8 +336,12 @@ struct lorb_map {
   // Overlap (lorb_map_set_overlap, default off): a step's match and append touch only the map's
   // point descriptors, its new slots / points and counts, its own key buffers -- nothing the previous
   // step's LM solve and write-back read or write -- so they run on a side stream as soon as the
-  // previous step's plan build has read the map (ev_built), concurrently with that solve; the slide
-  // waits for both.  The caller's keyframe arrays must be complete when the step is called (the side
+  // previous step's plan build has read the map (ev_built), concurrently with that solve; so do the
+  // slide's cull and scans (flags and scans only, see map_prepare), and the compaction waits for both
+  // streams: ev_app is recorded behind the side stream's last kernel and the ctx stream waits for it
+  // inside the same call, so a host wait on the ctx stream (lorb_map_read, lorb_map_counts,
+  // map_build_fail, lorb_map_destroy) covers the side stream's work of every step called so far.
+  // The caller's keyframe arrays must be complete when the step is called (the side
   // stream is not ordered after work the caller still has queued, lorb_c.h).
   bool overlap = false;
   hipStream_t side = nullptr;
@@ -418,15 +422,24 @@ lorb_ba_window_dev window_of(const lorb_map* M) {
   return w;
 }
 
+// the structural half of a slide to window [t0, ...): the keep flags and their tile scans, on stream st
+void map_cull_scans(lorb_map* M, hipStream_t st, int t0, int Pb, int Kb, int K0) {
+  const MapDev& m = M->m;
+  hipLaunchKernelGGL(k_map_cull, dim3(lorb::ceil_div(Kb + 1, 256)), dim3(256), 0, st, m, Kb, std::min(K0, Kb), t0);
+  const int ntP = lorb::ceil_div(Pb + 1, lorb::kScanTile), ntK = lorb::ceil_div(Kb + 1, lorb::kScanTile);
+  hipLaunchKernelGGL(k_map_scans, dim3(2 * ntP + ntK), dim3(1024), 0, st, m, Pb, Kb, ntP);
+}
+
 // slide to window [t0, t0 + W): cull points no window keyframe observes, drop observations by
-// keyframes older than the fixed ones, compact (stable), rebuild the BA slots and window poses
-int map_slide(lorb_map* M, int t0, int Pb, int Kb, int K0, int P0, const int* pt_off) {
+// keyframes older than the fixed ones, compact (stable), rebuild the BA slots and window poses.
+// culled: map_cull_scans has been enqueued for this slide already (the side stream, map_prepare) and
+// the ctx stream waits for it.
+int map_slide(lorb_map* M, int t0, int Pb, int Kb, int K0, int P0, const int* pt_off, bool culled = false) {
   lorb_ctx* ctx = M->ctx;
   hipStream_t s = ctx->stream;
   MapDev& m = M->m;
-  hipLaunchKernelGGL(k_map_cull, dim3(lorb::ceil_div(Kb + 1, 256)), dim3(256), 0, s, m, Kb, std::min(K0, Kb), t0);
-  const int ntP = lorb::ceil_div(Pb + 1, lorb::kScanTile), ntK = lorb::ceil_div(Kb + 1, lorb::kScanTile);
-  hipLaunchKernelGGL(k_map_scans, dim3(2 * ntP + ntK), dim3(1024), 0, s, m, Pb, Kb, ntP);
+  if (!culled) map_cull_scans(M, s, t0, Pb, Kb, K0);
+  const int ntP = lorb::ceil_div(Pb + 1, lorb::kScanTile);
   const int nmax = std::max(std::max(Pb, Kb), 1);
   hipLaunchKernelGGL(k_map_compact, dim3(lorb::ceil_div(nmax, 256)), dim3(256), 0, s, m, Pb, Kb, std::min(K0, Kb), P0, t0,
                      ntP, pt_off);
@@ -522,6 +535,9 @@ int lorb_map_create(lorb_ctx* ctx, const lorb_map_init* in, lorb_map** out) {
 }  // extern "C"
 
 namespace {
+
+// a switch of the map step, read at every step
+bool map_env(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
 
 // LORB_MAP_PROFILE: host wall time since the last mark into phase i, after a stream sync
 int map_mark(lorb_map* M, int i) {
@@ -625,15 +641,33 @@ int map_prepare(lorb_map* M, const lorb_frame_params* frame, const float pose[6]
     M->broken = true;
     return lorb::set_error(ctx, LORB_E_DEVICE, "k_map_append launch failed; the map is unusable");
   }
+  // Capacity: n keypoints add at most n points and n observations.  When that bound does not fit,
+  // read the append's verdict before anything else changes: a refused append leaves the map as it
+  // was (no ring write, no slide, no cull), so the map stays usable after the error.
+  const bool cap_check = M->h_P + n > m.P_cap || M->h_K + n > m.K_cap;
+  const int Pb = std::min(M->h_P + n, m.P_cap), Kb = std::min(M->h_K + n, m.K_cap);
+  // The slide's cull and scans follow the append on the side stream, under the previous solve
+  // (LORB_NO_SIDE_CULL=1, read at every step, keeps them on the ctx stream; so do a split build and
+  // the capacity branch, which reads the verdict before any flag is written).
+  //   k_map_cull   reads  cnt[1], obs_pt, obs_kf, flag_new (the append's, this stream) and its
+  //                       arguments Kb, K0, t0 (host values of this call);
+  //                writes flag_obs[0, Kb], flag_pt.
+  //   k_map_scans  reads  flag_pt, flag_new, flag_obs;  writes newid, newnew, newpos, tile_tot.
+  // Still in flight on the ctx stream behind ev_built: the previous step's solve (also one enqueued
+  // again after a speculation miss: ev_built is then the event recorded behind the second gather),
+  // which works on the plan's own buffers, and its k_db_result, which writes the ring and pos.
+  // Neither kernel reads the ring, pos or a plan buffer, and nothing in flight reads a flag or a
+  // scan: their only readers are this step's k_map_compact (behind ev_app, below) and the previous
+  // step's, which ran before its build's gather, so before ev_built (it left flag_pt and flag_new
+  // clear).  k_map_compact stays on the ctx stream: it gathers pos, which k_db_result writes.
+  const bool side_cull = ovl && !split && !cap_check && !map_env("LORB_NO_SIDE_CULL");
+  if (side_cull) map_cull_scans(M, ms, M->t0 + 1, Pb, Kb, M->h_K);
   if (ovl) {  // the rest of the step follows the previous step's write-back on the main stream
     LORB_HIP(ctx, hipEventRecord(M->ev_app, ms));
     LORB_HIP(ctx, hipStreamWaitEvent(s, M->ev_app, 0));
   }
   M->last_n = n;
-  // Capacity: n keypoints add at most n points and n observations.  When that bound does not fit,
-  // read the append's verdict before anything else changes: a refused append leaves the map as it
-  // was (no ring write, no slide, no cull), so the map stays usable after the error.
-  if (M->h_P + n > m.P_cap || M->h_K + n > m.K_cap) {
+  if (cap_check) {
     LORB_HIP(ctx, hipMemcpyAsync(M->pinned, m.cnt, sizeof(int) * 8, hipMemcpyDeviceToHost, s));
     LORB_HIP(ctx, hipStreamSynchronize(s));
     if (M->pinned[2] & 1)
@@ -642,8 +676,8 @@ int map_prepare(lorb_map* M, const lorb_frame_params* frame, const float pose[6]
   }
   LORB_TRY(mark(2));
   // 4. slide the window by one keyframe; cull and compact
-  LORB_TRY(map_slide(M, M->t0 + 1, std::min(M->h_P + n, m.P_cap), std::min(M->h_K + n, m.K_cap), M->h_K, M->h_P,
-                      M->plan_ok ? lorb::ba_plan_point_offsets(M->plan) : nullptr));
+  LORB_TRY(map_slide(M, M->t0 + 1, Pb, Kb, M->h_K, M->h_P,
+                      M->plan_ok ? lorb::ba_plan_point_offsets(M->plan) : nullptr, side_cull));
   LORB_TRY(mark(3));
   // 5. BA plan of the slid window; its one readback carries the window's live counts too (split:
   //    only the build's first phase and readback are queued here, map_build_finish completes it)

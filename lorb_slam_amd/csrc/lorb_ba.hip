@@ -1624,23 +1624,19 @@ int red_threads(const lorb_ba_plan* P) {
   if (P->grid_bp <= 256 || cand >= 128.0) return 1024;
   return P->grid_bp <= 1024 ? 512 : 256;
 }
-template <int MODE>
-void launch_red(const lorb_ba_plan* P, hipStream_t s, const BaDev& d, const LMOpt& o) {
-  const int rt = red_threads(P);
-  if (rt == 1024) hipLaunchKernelGGL((k_ba_red<MODE, 1024>), dim3(P->grid_bp), dim3(1024), 0, s, d, o);
-  else if (rt == 512) hipLaunchKernelGGL((k_ba_red<MODE, 512>), dim3(P->grid_bp), dim3(512), 0, s, d, o);
-  else hipLaunchKernelGGL((k_ba_red<MODE, 256>), dim3(P->grid_bp), dim3(256), 0, s, d, o);
+// the same rule over a plan group's k_ba_red_g, a launch of nb blocks: 1024 where a member that shares
+// the GPU (> 256 blocks of its own) has that many candidates (the sums do not depend on the width;
+// for n = 1 this is red_threads(plans[0]))
+int red_threads(lorb_ba_plan* const* plans, int n, int nb) {
+  bool wide = nb <= 256;
+  for (int k = 0; k < n; ++k) wide = wide || (red_threads(plans[k]) == 1024 && plans[k]->grid_bp > 256);
+  return wide ? 1024 : nb <= 1024 ? 512 : 256;
 }
 
-// the linearisation: one workgroup per point group, or per partial run (k_ba_ls_sup)
-// (d.fold: the previous iteration's tail in its prologue, ls_group)
-void launch_ls(const lorb_ba_plan* P, hipStream_t s, const BaDev& d, const LMOpt& o) {
-  lorb::KernelTimer kt(P->ctx, LORB_K_BA_LINEARIZE);
-  if (P->has_super) {
-    if (P->grid_sg) hipLaunchKernelGGL(k_ba_ls_sup, dim3(P->grid_sg), dim3(kLsThreads), 0, s, d, o);
-  } else if (P->grid_pblk) {
-    hipLaunchKernelGGL(k_ba_ls, dim3(P->grid_pblk), dim3(kLsThreads), 0, s, d, o);
-  }
+// k_ba_init's blocks for one plan
+int init_blocks(const lorb_ba_plan* P) {
+  const int n = std::max(std::max(std::max(P->W, P->Ctot), P->NF), std::min(3 * P->pt_launch, 256 * 1024));
+  return lorb::ceil_div(std::max(n, 1), 256);
 }
 
 // LORB_NO_FOLD=1 (read at every solve): every iteration ends with the k_ba_lm_end kernel.  Else the
@@ -1650,16 +1646,25 @@ void launch_ls(const lorb_ba_plan* P, hipStream_t s, const BaDev& d, const LMOpt
 // trip and a redundant evaluation in every workgroup: it pays where k_ba_ls is one round of
 // workgroups (two per CU: the C4 window's 346), and costs where the launch fills the GPU several
 // times over (8 C4 windows in one plan or in concurrent groups: -1.7 % / -2.8 %, profiles/r11/), so
-// launches of more than kFoldMaxGroups workgroups keep the kernel.
+// launches of more than kFoldMaxGroups workgroups keep the kernel.  The plans of one set of
+// launches (a plan; the members of a fused group) fold together or not at all.
 constexpr int kFoldMaxGroups = 512;
-bool fold_of(const lorb_ba_plan* P) {
-  if (env_flag("LORB_NO_FOLD") || no_fuse() || P->comm || P->has_super || chol_kind_of(P) != 2) return false;
-  for (const BaWin& w : P->hwin)
-    if (w.n_poses > 0 && w.n_pblk == 0) return false;
-  return P->grid_pblk > 0 && P->grid_pblk <= kFoldMaxGroups;
+bool fold_of(lorb_ba_plan* const* plans, size_t n) {
+  int groups = 0;
+  for (size_t k = 0; k < n; ++k) {
+    const lorb_ba_plan* P = plans[k];
+    if (env_flag("LORB_NO_FOLD") || no_fuse() || P->comm || P->has_super || chol_kind_of(P) != 2) return false;
+    for (const BaWin& w : P->hwin)
+      if (w.n_poses > 0 && w.n_pblk == 0) return false;
+    if (P->grid_pblk <= 0) return false;
+    groups += P->grid_pblk;
+  }
+  return groups <= kFoldMaxGroups;
 }
+bool fold_of(lorb_ba_plan* P) { return fold_of(&P, 1); }
 
-lorb_ba_plan::GraphKey graph_key(const lorb_ba_plan* P) {
+// the launch shape of a solve of P's fields as they are, folding or not
+lorb_ba_plan::GraphKey graph_key(const lorb_ba_plan* P, bool fold) {
   lorb_ba_plan::GraphKey k;
   k.kind = chol_kind_of(P);
   k.lds = k.kind >= 1 ? P->max_env_w : P->max_env + 1000000 * P->max_bw;
@@ -1670,111 +1675,165 @@ lorb_ba_plan::GraphKey graph_key(const lorb_ba_plan* P) {
   k.red_wide = red_threads(P);
   k.sup = P->has_super ? 1 : 0;
   k.grid_sg = P->grid_sg;
-  k.fold = P->fold ? 1 : 0;
+  k.fold = fold ? 1 : 0;
   return k;
 }
 
-// one LM iteration (K1..K8) on the ctx stream
-int enqueue_linearize(lorb_ba_plan* P, const LMOpt& o) {
-  hipStream_t s = P->ctx->stream;
-  const BaDev& d = P->dev;
-  // the group partials, then the camera terms of the head
-  launch_ls(P, s, d, o);
-  if (P->grid_bp) {
-    lorb::KernelTimer kt(P->ctx, LORB_K_BA_SCHUR);
-    launch_red<0>(P, s, d, o);
-  }
-  if (P->comm) {  // exchange 1: camera blocks + cost / |x|^2 (sum), gradient max (max)
-    hipLaunchKernelGGL(k_ba_win_reduce<0>, dim3(P->W), dim3(64), 0, s, d);
-    {
-      lorb::KernelTimer kt(P->ctx, LORB_K_ALLREDUCE);
-      LORB_TRY(lorb::comm_allreduce(P->comm, d.U_part, d.U, (size_t)P->Ctot * 27 + 2 * P->W, LORB_OP_SUM));
-      LORB_TRY(lorb::comm_allreduce(P->comm, d.wmax_part, d.wmax, (size_t)P->W, LORB_OP_MAX));
-    }
-    hipLaunchKernelGGL(k_ba_lm_begin<true>, dim3(P->W), dim3(64), 0, s, d, o);
-  } else {
-    hipLaunchKernelGGL(k_ba_lm_begin<false>, dim3(P->W), dim3(64), 0, s, d, o);
-  }
-  return LORB_OK;
-}
-
-// one LM iteration on the ctx stream.  first: k_ba_ls -> k_ba_red<0> (camera terms) -> k_ba_lm_begin
-// -> k_ba_red<1> -> Cholesky -> k_ba_bs2 -> k_ba_lm_end.  Later iterations of an unsharded plan on
-// the two-sided Cholesky run fused: k_ba_red<2> writes the band, rhs and camera terms at once (the
-// Jacobi scale is iteration 0's) and the head runs inside the Cholesky (k_ba_lm_begin's work), so
-// k_ba_ls -> k_ba_red<2> -> k_ba_chol_2s<true> -> k_ba_bs2 -> k_ba_lm_end: five launches.
-// A folding plan (lorb_ba_plan::fold) drops k_ba_lm_end from every iteration but the last (fold_out:
-// a fused iteration follows and runs the tail in its k_ba_ls, fold_in), four launches: the decided
-// state goes to st2, which k_ba_red<2> and the Cholesky's head read (their BaDev has fold set).
-int enqueue_iteration(lorb_ba_plan* P, const LMOpt& o, bool first, bool last) {
-  lorb_ctx* ctx = P->ctx;
-  hipStream_t s = ctx->stream;
-  const bool fused = !first && chol_kind_of(P) == 2 && !no_fuse();
-  const bool fold_in = P->fold && fused, fold_out = P->fold && !last;
-  BaDev d = P->dev;
-  d.fold = fold_in ? (P->W == 1 ? 2 : 1) : 0;
-  if (fused) {
-    launch_ls(P, s, d, o);
-  } else {
-    LORB_TRY(enqueue_linearize(P, o));
-  }
-  // The LDS Cholesky never writes env, and k_ba_red rewrites every stored entry of
-  // every block each iteration, so the band's structural zeros (set at plan creation) persist; the
-  // in-place global variant needs them restored.
+// The band's structural zeros (set at plan creation) persist under the LDS Cholesky, which never
+// writes env (k_ba_red rewrites every stored entry of every block each iteration); the in-place
+// global variant needs them restored.
+int restore_band(const lorb_ba_plan* P, hipStream_t s) {
   const bool chol_in_lds = sizeof(double) * (size_t)P->max_env <= (size_t)kLdsBudget;
-  if (P->env_total && !chol_in_lds && !P->comm) LORB_HIP(ctx, hipMemsetAsync(d.env, 0, sizeof(double) * P->env_total, s));
-  if (P->grid_bp) {
-    lorb::KernelTimer kt(ctx, LORB_K_BA_SCHUR);
-    if (fused) launch_red<2>(P, s, d, o);
-    else launch_red<1>(P, s, d, o);
-  }
-  if (P->comm && fused) {
-    // the fused sharded iteration: the point partials of the head, then exchanges 1 and 2 as one
-    // sum over the contiguous [U | V | cost, |x|^2 | pad | band | rhs | failure flags] (the band's
-    // camera blocks and the rhs carry -a / -r only: the Cholesky adds the global U sc sc^T + D^2 and
-    // V sc as it stages them) and the gradient max
-    hipLaunchKernelGGL(k_ba_win_reduce<0>, dim3(P->W), dim3(64), 0, s, d);
-    lorb::KernelTimer kt(ctx, LORB_K_ALLREDUCE);
-    LORB_TRY(lorb::comm_allreduce(P->comm, d.U_part, d.U, P->fx_n, LORB_OP_SUM));
-    LORB_TRY(lorb::comm_allreduce(P->comm, d.wmax_part, d.wmax, (size_t)P->W, LORB_OP_MAX));
-  } else if (P->comm) {  // exchange 2: reduced camera system, rhs, point-block failure flags
-    lorb::KernelTimer kt(ctx, LORB_K_ALLREDUCE);
-    LORB_TRY(lorb::comm_allreduce(P->comm, P->x2_send, P->x2_recv, x2_count(P), LORB_OP_SUM));
-  }
-  const int kind = chol_kind_of(P);
-  P->chol_kind = kind;
-  if (kind >= 0) {  // (-1: no cameras)
-    lorb::KernelTimer kt(ctx, LORB_K_BA_CHOLESKY);
-    launch_chol(kind, CholShape{P->W, P->max_env, P->max_env_w, P->max_bw}, s, d, o, fused);
-  }
-  if (P->grid_pblk) hipLaunchKernelGGL(k_ba_bs2, dim3(P->grid_pblk), dim3(kGB), 0, s, d);
-  if (P->comm) {  // exchange 3: model cost change, candidate cost, point |step|^2
-    hipLaunchKernelGGL(k_ba_win_reduce<1>, dim3(P->W), dim3(64), 0, s, d);
-    {
-      lorb::KernelTimer kt(ctx, LORB_K_ALLREDUCE);
-      LORB_TRY(lorb::comm_allreduce(P->comm, d.wstep_part, d.wstep, 3 * (size_t)P->W, LORB_OP_SUM));
-    }
-    hipLaunchKernelGGL(k_ba_lm_end<true>, dim3(P->W), dim3(64), 0, s, d, o);
-  } else if (!fold_out) {
-    hipLaunchKernelGGL(k_ba_lm_end<false>, dim3(P->W), dim3(64), 0, s, d, o);
-  }
-  LORB_CHECK_LAUNCH(ctx);
+  if (P->env_total && !chol_in_lds && !P->comm) LORB_HIP(P->ctx, hipMemsetAsync(P->dev.env, 0, sizeof(double) * P->env_total, s));
   return LORB_OK;
 }
 
-// the whole solve: x <- initial values, max_iter LM iterations (k_ba_lm_end closes the solve when
-// the budget is spent: no final linearisation)
-int enqueue_solve(lorb_ba_plan* P, const LMOpt& o) {
-  lorb_ctx* ctx = P->ctx;
-  {
-    const int n = std::max(std::max(std::max(P->W, P->Ctot), P->NF), std::min(3 * P->pt_launch, 256 * 1024));
-    hipLaunchKernelGGL(k_ba_init, dim3(lorb::ceil_div(std::max(n, 1), 256)), dim3(256), 0, ctx->stream, P->dev, P->W,
-                       P->Ctot, P->pt_launch, P->NF, o);
+// The exchanges of a sharded plan.  1: camera blocks + cost / |x|^2 (sum over n = 27 Ctot + 2 W
+// doubles), gradient max (max).  A fused iteration sums exchanges 1 and 2 at once, n = P->fx_n: the
+// contiguous [U | V | cost, |x|^2 | pad | band | rhs | failure flags] (the band's camera blocks and the
+// rhs carry -a / -r only: the Cholesky adds the global U sc sc^T + D^2 and V sc as it stages them).
+int exchange_1(const lorb_ba_plan* P, hipStream_t s, size_t n) {
+  hipLaunchKernelGGL(k_ba_win_reduce<0>, dim3(P->W), dim3(64), 0, s, P->dev);
+  lorb::KernelTimer kt(P->ctx, LORB_K_ALLREDUCE);
+  LORB_TRY(lorb::comm_allreduce(P->comm, P->dev.U_part, P->dev.U, n, LORB_OP_SUM));
+  return lorb::comm_allreduce(P->comm, P->dev.wmax_part, P->dev.wmax, (size_t)P->W, LORB_OP_MAX);
+}
+// 2: reduced camera system, rhs, point-block failure flags
+int exchange_2(const lorb_ba_plan* P) {
+  lorb::KernelTimer kt(P->ctx, LORB_K_ALLREDUCE);
+  return lorb::comm_allreduce(P->comm, P->x2_send, P->x2_recv, x2_count(P), LORB_OP_SUM);
+}
+// 3: model cost change, candidate cost, point |step|^2
+int exchange_3(const lorb_ba_plan* P, hipStream_t s) {
+  hipLaunchKernelGGL(k_ba_win_reduce<1>, dim3(P->W), dim3(64), 0, s, P->dev);
+  lorb::KernelTimer kt(P->ctx, LORB_K_ALLREDUCE);
+  return lorb::comm_allreduce(P->comm, P->dev.wstep_part, P->dev.wstep, 3 * (size_t)P->W, LORB_OP_SUM);
+}
+
+// block prefix of one group launch: f(P) workgroups per member
+template <typename F>
+GrpGrid grp_grid(lorb_ba_plan* const* plans, int n, F f) {
+  GrpGrid g{};
+  for (int k = 0; k < n; ++k) g.pre[k + 1] = g.pre[k] + f(plans[k]);
+  for (int k = n + 1; k <= kGrpMax; ++k) g.pre[k] = g.pre[n];
+  return g;
+}
+
+// What enqueue_solve launches on: one plan (its own kernels on the grids its fields give), or the
+// members of a fused group (the k_ba_*_g kernels, a block range per member; group_fused: never
+// sharded, always the two-sided Cholesky, no partial runs).  A plan is not a group of one.
+struct LmTarget {
+  lorb_ba_plan* const* plans;
+  int n;
+  bool grouped, fold;  // fold: this solve folds (fold_of)
+  lorb_ctx* ctx;
+  hipStream_t s;
+  // the kernels' argument (the plan's / the group's); [1]: fold set, for the k_ba_ls, k_ba_red<2> and
+  // Cholesky of a folding iteration
+  BaDev d[2]{};
+  BaGrp g[2]{};
+  LmTarget(lorb_ba_plan* const* plans_, int n_, bool grouped_, bool fold_)
+      : plans(plans_), n(n_), grouped(grouped_), fold(fold_), ctx(plans_[0]->ctx), s(ctx->stream) {
+    bool one_win = true;
+    for (int k = 0; k < n; ++k) one_win = one_win && plans[k]->W == 1;
+    d[0] = d[1] = plans[0]->dev;
+    d[1].fold = one_win ? 2 : 1;
+    if (!grouped) return;
+    g[0].n = g[1].n = n;
+    for (int k = 0; k < n; ++k) {
+      g[0].d[k] = g[1].d[k] = plans[k]->dev;
+      g[1].d[k].fold = d[1].fold;
+    }
   }
-  LORB_CHECK_LAUNCH(ctx);
-  // no iterations: one linearisation (cost, termination) as the head of a first iteration
-  if (o.max_iter <= 0) return enqueue_linearize(P, o);
-  for (int it = 0; it < o.max_iter; ++it) LORB_TRY(enqueue_iteration(P, o, it == 0, it + 1 == o.max_iter));
+  // one stage: the plan's kernel on its grid (a field of the plan), or the group's on every member's
+  template <typename KP, typename KG, typename... A>
+  void launch(KP plan_kernel, KG group_kernel, int lorb_ba_plan::*grid, int block, bool folding, const A&... a) const {
+    if (!grouped) {
+      const int nb = plans[0]->*grid;
+      if (nb) hipLaunchKernelGGL(plan_kernel, dim3(nb), dim3(block), 0, s, d[folding], a...);
+      return;
+    }
+    const GrpGrid gg = grp_grid(plans, n, [&](const lorb_ba_plan* P) { return P->*grid; });
+    if (gg.pre[n]) hipLaunchKernelGGL(group_kernel, dim3(gg.pre[n]), dim3(block), 0, s, g[folding], gg, a...);
+  }
+  void init(const LMOpt& o) const {
+    const lorb_ba_plan* P = plans[0];
+    if (!grouped) {
+      hipLaunchKernelGGL(k_ba_init, dim3(init_blocks(P)), dim3(256), 0, s, d[0], P->W, P->Ctot, P->pt_launch, P->NF, o);
+      return;
+    }
+    GrpInit a{};
+    for (int k = 0; k < n; ++k) {
+      P = plans[k];
+      a.W[k] = P->W; a.ctot[k] = P->Ctot; a.n_pt[k] = P->pt_launch; a.nf[k] = P->NF;
+    }
+    const GrpGrid gg = grp_grid(plans, n, init_blocks);
+    hipLaunchKernelGGL(k_ba_init_g, dim3(gg.pre[n]), dim3(256), 0, s, g[0], gg, a, o);
+  }
+  // k_ba_red in its mode's and width's instance, if there are block pairs
+  template <int MODE>
+  void red(bool folding, const LMOpt& o) const {
+    int nb = 0;
+    for (int k = 0; k < n; ++k) nb += plans[k]->grid_bp;
+    if (!nb) return;
+    lorb::KernelTimer kt(ctx, LORB_K_BA_SCHUR);
+    const int rt = red_threads(plans, n, nb);
+    if (rt == 1024) launch(k_ba_red<MODE, 1024>, k_ba_red_g<MODE, 1024>, &lorb_ba_plan::grid_bp, 1024, folding, o);
+    else if (rt == 512) launch(k_ba_red<MODE, 512>, k_ba_red_g<MODE, 512>, &lorb_ba_plan::grid_bp, 512, folding, o);
+    else launch(k_ba_red<MODE, 256>, k_ba_red_g<MODE, 256>, &lorb_ba_plan::grid_bp, 256, folding, o);
+  }
+  void chol(int kind, bool folding, const LMOpt& o, bool head) const {
+    lorb::KernelTimer kt(ctx, LORB_K_BA_CHOLESKY);
+    const lorb_ba_plan* P = plans[0];
+    if (!grouped) return launch_chol(kind, CholShape{P->W, P->max_env, P->max_env_w, P->max_bw}, s, d[folding], o, head);
+    size_t lds = 0;
+    for (int k = 0; k < n; ++k) lds = std::max(lds, sizeof(double) * (size_t)plans[k]->max_env_w);
+    launch_chol_2s_g(s, g[folding], grp_grid(plans, n, [](const lorb_ba_plan* Q) { return Q->W; }), o, head, lds);
+  }
+};
+
+// The whole LM solve on the ctx stream, for a plan and for a fused group: x <- initial values, then
+// max_iter iterations (k_ba_lm_end closes the solve when the budget is spent: no final linearisation).
+// First iteration: k_ba_ls -> k_ba_red<0> (camera terms) -> k_ba_lm_begin -> k_ba_red<1> -> Cholesky
+// -> k_ba_bs2 -> k_ba_lm_end.  Later iterations on the two-sided Cholesky run fused (LORB_NO_FUSE:
+// none does): k_ba_red<2> writes the band, rhs and camera terms at once (the Jacobi scale is
+// iteration 0's) and the head runs inside the Cholesky (k_ba_lm_begin's work), so k_ba_ls ->
+// k_ba_red<2> -> k_ba_chol_2s<true> -> k_ba_bs2 -> k_ba_lm_end: five launches.
+// A folding solve drops k_ba_lm_end from every iteration but the last (fold_out: a fused iteration
+// follows and runs the tail in its k_ba_ls, fold_in), four launches: the decided state goes to st2,
+// which k_ba_red<2> and the Cholesky's head read (those three get the argument with fold set).
+// No iterations: one linearisation (cost, termination), the head of a first iteration.
+int enqueue_solve(const LmTarget& t, const LMOpt& o) {
+  using P = lorb_ba_plan;
+  const P* X = !t.grouped && t.plans[0]->comm ? t.plans[0] : nullptr;  // the sharded plan
+  const bool sup = !t.grouped && t.plans[0]->has_super;  // k_ba_ls per partial run
+  const int kind = chol_kind_of(t.plans[0]);  // (-1: no cameras; a group: 2 for every member)
+  t.init(o);
+  LORB_CHECK_LAUNCH(t.ctx);
+  for (int it = 0; it < std::max(o.max_iter, 1); ++it) {
+    const bool fused = it > 0 && kind == 2 && !no_fuse();
+    const bool fold_in = t.fold && fused, fold_out = t.fold && it + 1 < o.max_iter;
+    {  // (fold_in: the previous iteration's tail in the prologue, ls_group)
+      lorb::KernelTimer kt(t.ctx, LORB_K_BA_LINEARIZE);
+      t.launch(sup ? k_ba_ls_sup : k_ba_ls, k_ba_ls_g, sup ? &P::grid_sg : &P::grid_pblk, kLsThreads, fold_in, o);
+    }
+    if (!fused) {  // the head as kernels: the group partials' camera terms, exchange 1, k_ba_lm_begin
+      t.red<0>(false, o);
+      if (X) LORB_TRY(exchange_1(X, t.s, (size_t)X->Ctot * 27 + 2 * X->W));
+      t.launch(X ? k_ba_lm_begin<true> : k_ba_lm_begin<false>, k_ba_lm_begin_g, &P::W, 64, false, o);
+      if (o.max_iter <= 0) break;
+    }
+    for (int k = 0; k < t.n; ++k) LORB_TRY(restore_band(t.plans[k], t.s));  // (a memset, or nothing)
+    if (fused) t.red<2>(fold_in, o);
+    else t.red<1>(false, o);
+    if (X) LORB_TRY(fused ? exchange_1(X, t.s, X->fx_n) : exchange_2(X));
+    if (kind >= 0) t.chol(kind, fold_in, o, fused);
+    t.launch(k_ba_bs2, k_ba_bs2_g, &P::grid_pblk, kGB, false);
+    if (X) LORB_TRY(exchange_3(X, t.s));
+    if (!fold_out) t.launch(X ? k_ba_lm_end<true> : k_ba_lm_end<false>, k_ba_lm_end_g, &P::W, 64, false, o);
+    for (int k = 0; k < t.n; ++k) t.plans[k]->chol_kind = kind;
+    LORB_CHECK_LAUNCH(t.ctx);
+  }
   return LORB_OK;
 }
 
@@ -1784,12 +1843,12 @@ int plan_solve(lorb_ba_plan* P, const lorb_lm_options* opt) {
   P->fold = fold_of(P);
   // per-kernel events cannot live inside a graph, and neither can a host-transport exchange
   const bool timing = ctx->ktime || no_graph() || (P->comm && !P->comm->rccl);
-  const lorb_ba_plan::GraphKey key = graph_key(P);
+  const lorb_ba_plan::GraphKey key = graph_key(P, P->fold);
   P->skey = key;
-  if (timing) return enqueue_solve(P, o);
+  const auto enqueue = [&] { return enqueue_solve(LmTarget(&P, 1, false, P->fold), o); };
+  if (timing) return enqueue();
   const bool same = key == P->gkey && same_opt(P->graph_opt, o);
-  return P->cache.replay_or_capture(ctx, same, [&] { return enqueue_solve(P, o); },
-                                    [&] { P->gkey = key; P->graph_opt = o; });
+  return P->cache.replay_or_capture(ctx, same, enqueue, [&] { P->gkey = key; P->graph_opt = o; });
 }
 
 int plan_read(lorb_ba_plan* P, double* const* pose_out, double* const* point_out,
@@ -1832,11 +1891,7 @@ int plan_read(lorb_ba_plan* P, double* const* pose_out, double* const* point_out
 namespace lorb {
 // plan_solve's host-side choices on the plan's fields as they are now against the last solve's
 bool ba_plan_solve_key_same(lorb_ba_plan* P) {
-  const bool fold_was = P->fold;
-  P->fold = fold_of(P);
-  const bool same = graph_key(P) == P->skey;
-  P->fold = fold_was;
-  return same;
+  return graph_key(P, fold_of(P)) == P->skey;
 }
 }  // namespace lorb
 
@@ -1866,102 +1921,6 @@ bool group_fused(const lorb_ba_group* G) {
   return true;
 }
 
-// block prefix of one launch: f(P) workgroups per member
-template <typename F>
-GrpGrid grp_grid(const lorb_ba_group* G, F f) {
-  GrpGrid g{};
-  for (size_t k = 0; k < G->plans.size(); ++k) g.pre[k + 1] = g.pre[k] + f(G->plans[k]);
-  for (size_t k = G->plans.size() + 1; k <= (size_t)kGrpMax; ++k) g.pre[k] = g.pre[G->plans.size()];
-  return g;
-}
-
-template <int MODE>
-void launch_red_g(const lorb_ba_group* G, hipStream_t s, const BaGrp& bg, const LMOpt& o) {
-  const GrpGrid gg = grp_grid(G, [](const lorb_ba_plan* P) { return P->grid_bp; });
-  const int n = (int)G->plans.size(), nb = gg.pre[n];
-  if (nb == 0) return;
-  // the width rule of red_threads over the whole launch (the sums do not depend on it)
-  bool wide = nb <= 256;
-  for (const lorb_ba_plan* P : G->plans) wide = wide || (red_threads(P) == 1024 && P->grid_bp > 256);
-  const int rt = wide ? 1024 : nb <= 1024 ? 512 : 256;
-  if (rt == 1024) hipLaunchKernelGGL((k_ba_red_g<MODE, 1024>), dim3(nb), dim3(1024), 0, s, bg, gg, o);
-  else if (rt == 512) hipLaunchKernelGGL((k_ba_red_g<MODE, 512>), dim3(nb), dim3(512), 0, s, bg, gg, o);
-  else hipLaunchKernelGGL((k_ba_red_g<MODE, 256>), dim3(nb), dim3(256), 0, s, bg, gg, o);
-}
-
-// the group's whole solve on the ctx stream (enqueue_solve / enqueue_iteration of every member at once)
-int enqueue_group_solve(lorb_ba_group* G, const LMOpt& o) {
-  lorb_ctx* ctx = G->ctx;
-  hipStream_t s = ctx->stream;
-  const int n = (int)G->plans.size();
-  BaGrp bg{};
-  bg.n = n;
-  for (int k = 0; k < n; ++k) bg.d[k] = G->plans[k]->dev;
-  {
-    GrpInit a{};
-    for (int k = 0; k < n; ++k) {
-      const lorb_ba_plan* P = G->plans[k];
-      a.W[k] = P->W; a.ctot[k] = P->Ctot; a.n_pt[k] = P->pt_launch; a.nf[k] = P->NF;
-    }
-    const GrpGrid gg = grp_grid(G, [](const lorb_ba_plan* P) {
-      const int m = std::max(std::max(std::max(P->W, P->Ctot), P->NF), std::min(3 * P->pt_launch, 256 * 1024));
-      return lorb::ceil_div(std::max(m, 1), 256);
-    });
-    hipLaunchKernelGGL(k_ba_init_g, dim3(gg.pre[n]), dim3(256), 0, s, bg, gg, a, o);
-  }
-  const GrpGrid g_pb = grp_grid(G, [](const lorb_ba_plan* P) { return P->grid_pblk; });
-  const GrpGrid g_w = grp_grid(G, [](const lorb_ba_plan* P) { return P->W; });
-  size_t lds = 0;
-  for (const lorb_ba_plan* P : G->plans) lds = std::max(lds, sizeof(double) * (size_t)P->max_env_w);
-  // the folded iteration tail (enqueue_iteration): every member folds, or none
-  const bool fold = G->plans[0]->fold;
-  bool one_win = true;
-  for (const lorb_ba_plan* P : G->plans) one_win = one_win && P->W == 1;
-  BaGrp bgf = bg;  // for k_ba_ls, k_ba_red<2> and the Cholesky's head of a folding iteration
-  for (int k = 0; k < n; ++k) bgf.d[k].fold = one_win ? 2 : 1;
-  auto linearise = [&](bool fold_in) {
-    lorb::KernelTimer kt(ctx, LORB_K_BA_LINEARIZE);
-    if (g_pb.pre[n]) hipLaunchKernelGGL(k_ba_ls_g, dim3(g_pb.pre[n]), dim3(kLsThreads), 0, s, fold_in ? bgf : bg, g_pb, o);
-  };
-  if (o.max_iter <= 0) {  // one linearisation (cost, termination) as the head of a first iteration
-    linearise(false);
-    launch_red_g<0>(G, s, bg, o);
-    hipLaunchKernelGGL(k_ba_lm_begin_g, dim3(g_w.pre[n]), dim3(64), 0, s, bg, g_w, o);
-    LORB_CHECK_LAUNCH(ctx);
-    return LORB_OK;
-  }
-  for (int it = 0; it < o.max_iter; ++it) {
-    const bool first = it == 0;
-    const bool fold_in = fold && !first, fold_out = fold && it + 1 < o.max_iter;
-    const BaGrp& bi = fold_in ? bgf : bg;
-    linearise(fold_in);
-    if (first) {
-      {
-        lorb::KernelTimer kt(ctx, LORB_K_BA_SCHUR);
-        launch_red_g<0>(G, s, bg, o);
-      }
-      hipLaunchKernelGGL(k_ba_lm_begin_g, dim3(g_w.pre[n]), dim3(64), 0, s, bg, g_w, o);
-    }
-    for (const lorb_ba_plan* P : G->plans)  // (the two-sided Cholesky holds its band in LDS: none)
-      if (P->env_total && sizeof(double) * (size_t)P->max_env > (size_t)kLdsBudget)
-        LORB_HIP(ctx, hipMemsetAsync(P->dev.env, 0, sizeof(double) * P->env_total, s));
-    {
-      lorb::KernelTimer kt(ctx, LORB_K_BA_SCHUR);
-      if (first) launch_red_g<1>(G, s, bg, o);
-      else launch_red_g<2>(G, s, bi, o);
-    }
-    {
-      lorb::KernelTimer kt(ctx, LORB_K_BA_CHOLESKY);
-      launch_chol_2s_g(s, bi, g_w, o, !first, lds);
-    }
-    if (g_pb.pre[n]) hipLaunchKernelGGL(k_ba_bs2_g, dim3(g_pb.pre[n]), dim3(kGB), 0, s, bg, g_pb);
-    if (!fold_out) hipLaunchKernelGGL(k_ba_lm_end_g, dim3(g_w.pre[n]), dim3(64), 0, s, bg, g_w, o);
-  }
-  for (lorb_ba_plan* P : G->plans) P->chol_kind = 2;
-  LORB_CHECK_LAUNCH(ctx);
-  return LORB_OK;
-}
-
 int group_solve(lorb_ba_group* G, const lorb_lm_options* opt) {
   lorb_ctx* ctx = G->ctx;
   if (!group_fused(G)) {
@@ -1970,23 +1929,21 @@ int group_solve(lorb_ba_group* G, const lorb_lm_options* opt) {
     return LORB_OK;
   }
   const LMOpt o = to_dev_opt(opt);
-  bool fold = true;
-  int groups = 0;
-  for (const lorb_ba_plan* P : G->plans) { fold = fold && fold_of(P); groups += P->grid_pblk; }
-  fold = fold && groups <= kFoldMaxGroups;
+  const bool fold = fold_of(G->plans.data(), G->plans.size());
   for (lorb_ba_plan* P : G->plans) P->fold = fold;  // (part of the members' graph keys)
+  const auto enqueue = [&] { return enqueue_solve(LmTarget(G->plans.data(), (int)G->plans.size(), true, fold), o); };
   if (no_graph() || ctx->ktime) {  // per-kernel timing: eager launches (events cannot live in a graph)
-    LORB_TRY(enqueue_group_solve(G, o));
+    LORB_TRY(enqueue());
     G->n_fused++;
     return LORB_OK;
   }
   bool same = same_opt(G->graph_opt, o) && G->gens.size() == G->plans.size();
   for (size_t k = 0; k < G->plans.size() && same; ++k)
-    same = G->gens[k] == G->plans[k]->gen && G->keys[k] == graph_key(G->plans[k]);
-  LORB_TRY(G->cache.replay_or_capture(ctx, same, [&] { return enqueue_group_solve(G, o); }, [&] {
+    same = G->gens[k] == G->plans[k]->gen && G->keys[k] == graph_key(G->plans[k], fold);
+  LORB_TRY(G->cache.replay_or_capture(ctx, same, enqueue, [&] {
     G->graph_opt = o;
     G->gens.clear(); G->keys.clear();
-    for (const lorb_ba_plan* P : G->plans) { G->gens.push_back(P->gen); G->keys.push_back(graph_key(P)); }
+    for (const lorb_ba_plan* P : G->plans) { G->gens.push_back(P->gen); G->keys.push_back(graph_key(P, fold)); }
   }));
   G->n_fused++;
   return LORB_OK;
